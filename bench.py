@@ -13,7 +13,8 @@ ranks (strong scaling: total work fixed at 32 views); every rank denoises its V/
 all-gather over xGMI gives every rank the full [V,4,64,64] noise prediction (what the replicated 3D update
 consumes).  value = steps/s of the whole 32-view job = 1 / max-over-ranks(step time).
 
-The JSON line also carries
+A plain run sets up, warms up, times the --steps steps, writes the last timed step's noise prediction when --dump-outputs DIR is given,
+and prints the headline line (metric, value, unit, higher_is_better, dtype, ms_per_step, config).  With --full the JSON line also carries
   roofline     : the dominant kernel (k_gemm_pp: 3x3 implicit-GEMM conv + linear launches, MFMA bound): algorithmic FLOPs of all its
                  launches in one step / their summed HIP-event durations, recorded on the launch stream over the K timed steps REPEATED right
                  after the timed region (round 5: the events themselves cost ~2 ms of a 64 ms step, so the timed K steps carry none;
@@ -62,7 +63,15 @@ def parse():
     ap.add_argument('--no-op-timing', action='store_true', help='time the steps without per-op HIP events')
     ap.add_argument('--secondary-only', action='store_true', help='run only the render / reconstruct / VAE figures (the workload of the '
                     'rocprofv3 passes behind profiles/rNN_rocprof_render_*.txt) and print them')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true', help='everything beyond the headline figure: per-op event timing and the roofline, power / clock, '
+                    'collectives, cpu_baseline and parity, scaling projection, extra workloads, outer step, secondary figures (the --no-* switches '
+                    'trim this set).  Off: set up, warm up, time the steps, dump outputs if asked, print the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps, write the noise prediction of the last timed step '
+                    '(all views, float32) to DIR/noise_pred.npy')
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
+    return a
 
 
 def cpu_baseline(cfg, dtype=torch.float16, latent_hw=(LATENT, LATENT), B=1, n_img=1, repeats=3, x=None, ctx=None, t=499, zero123pp_passes=None):
@@ -193,14 +202,22 @@ def main():
     # The timed region: EXACTLY K steps, nothing but the workload (no per-op events: round 5 measured them at 2 ms of a 64 ms step -- 712 event records
     # per step keep kernel tails from overlapping the next launch).
     for i in range(args.steps):
-        step(False)
+        noise_last, _ = step(False)
     torch.cuda.synchronize()
     if use_dist:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        # what a caller of get_noise_pred receives from the last timed step: the CFG-combined noise prediction of every view
+        from mvedit_amd import parallel as PL
+        noise_all = PL.all_gather_views(noise_last, V, force=world == 1) if shards else noise_last
+        if rank == 0:
+            import numpy as np
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, 'noise_pred.npy'), noise_all.float().cpu().numpy())
     timed_rows = None
-    if rank == 0 and wl == 'mvedit32' and last_raw[0] is not None:
+    if args.full and rank == 0 and wl == 'mvedit32' and last_raw[0] is not None:
         # rows of the LAST TIMED step's batch for the checker leg: view 0's unconditional and text rows (rows 0 and v_loc of [uncond | text])
         timed_rows = ([0, v_loc], last_raw[0][[0, v_loc]].float().cpu())
     # The roofline's kernel durations: HIP events around every launch (mve_unet_forward's op_ms, recorded on the launch stream) over the SAME K steps
@@ -209,7 +226,7 @@ def main():
     per_op = None
     n_prof = 0
     ms_with_events = None
-    if not args.no_op_timing:
+    if args.full and not args.no_op_timing:
         n_ev = args.steps if world == 1 else 1
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -223,11 +240,11 @@ def main():
             dist.barrier()
     # socket power / clock: sampled over EXTRA untimed steps right after the timed region (rocm-smi queries the SMU; nothing that is not the
     # workload runs next to the timed steps).  Every rank runs the extra steps (they contain the step's collective); rank 0 samples.
-    sampler = PowerSampler() if rank == 0 else None
+    sampler = PowerSampler() if args.full and rank == 0 else None
     if sampler is not None:
         sampler.__enter__()
     t_extra = time.perf_counter()
-    while True:
+    while args.full:
         step(False)
         torch.cuda.synchronize()
         more = torch.tensor([1.0 if time.perf_counter() - t_extra < 2.5 else 0.0], device=dev)
@@ -253,7 +270,7 @@ def main():
     # and the drift-guard broadcast of the scene (parallel.sync_scene, ~56 MiB, once per OUTER step -- a second collective beyond
     # north_star's one), so that a scaling projection can carry them
     collectives = None
-    if use_dist and shards:
+    if args.full and use_dist and shards:
         def timed(fn, n=10):
             fn()
             torch.cuda.synchronize()
@@ -377,7 +394,7 @@ def main():
             line['op_timing'] = dict(ms_per_step_timed_region=round(ms_per_step, 3), ms_per_step_with_per_op_events=round(ms_with_events, 3), steps_with_events=n_prof,
                                      note='the timed K steps carry no events; the roofline / per-class durations are HIP events around every launch over the same '
                                           'steps repeated right after the timed region (the events cost ~2 ms of host + queue time per 64-image step)')
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             hw = (120, 80) if wl == 'zero123pp' else (LATENT, LATENT)
             if timed_rows is not None:
                 # the checker reads ROWS OF THE TIMED BATCH: the fp32 oracle runs the two items alone (B = 2, ~2 x 3 s per
@@ -417,13 +434,13 @@ def main():
         phases = os.environ.get('MVE_UPSAMPLE_PHASES', '1') != '0'
         line['config']['upsample2d'] = ('four 2x2 phase convs over the source (summed 3x3 taps rounded once to the storage type; 4/9 of the multiply-adds)'
                                         if phases else '3x3 conv over the nearest-upsampled image (as the reference)')
-        if world == 1 and wl == 'mvedit32' and not args.no_extra:
+        if args.full and world == 1 and wl == 'mvedit32' and not args.no_extra:
             # what one rank of an N-GPU job runs (32 views x CFG / N images), on this box: the projection the first real SCALE file is to be read against
             try:
                 line['scaling_projection'] = scaling_projection(eng, dev, dtype, ms_per_step)
             except Exception as e:
                 line['scaling_projection'] = {'error': repr(e)[:300]}
-        if world == 1 and not args.no_extra and wl == 'mvedit32' and dtype == torch.float16 and pair_mode:
+        if args.full and world == 1 and not args.no_extra and wl == 'mvedit32' and dtype == torch.float16 and pair_mode:
             # the other configurations BASELINE.json names, and the two other numeric modes, as compact driver-visible lines (3 steps each)
             del eng
             torch.cuda.empty_cache()
@@ -451,7 +468,7 @@ def main():
                 line['outer_step'] = outer_step(dev)
             except Exception as e:
                 line['outer_step'] = {'error': repr(e)[:300]}
-        if world == 1 and not args.no_secondary and wl == 'mvedit32':
+        if args.full and world == 1 and not args.no_secondary and wl == 'mvedit32':
             try:
                 line['secondary'] = secondary(dev)
             except Exception as e:      # a secondary figure must never take the headline line with it

@@ -15,7 +15,11 @@ def test_default_arguments_are_the_drivers(monkeypatch):
     monkeypatch.setattr(sys, 'argv', ['bench.py'])
     a = bench.parse()
     assert (a.gpus, a.steps, a.warmup, a.dtype, a.workload, a.views) == (1, 5, 2, 'fp16', 'mvedit32', 32)
-    assert not a.plain_stream and not a.no_extra and not a.no_cpu_baseline          # the default line is the default engine mode, with its checker
+    assert not a.plain_stream and not a.full and a.dump_outputs is None              # the default line is the default engine mode, headline only
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--dump-outputs', 'out'])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == 'out' and not a.plain_stream
+    assert not a.no_extra and not a.no_cpu_baseline and not a.no_secondary and not a.no_op_timing   # --full: every figure, with its checker
 
 
 def test_passes_of_every_workload():

@@ -2,9 +2,9 @@
 
 The reference cannot be imported here (diffusers / mmcv / tinycudann / nvdiffrast are absent), so the hook is exercised on a SKELETON of the
 reference's package -- same module paths, class and function names, import statements and constructor keyword names, bodies that record what they
-were given -- written to a temporary directory, imported as `lib`, and driven the way lib/apis/adapter3d.py:971-975 drives the real one.  Where the
-reference tree is present (the build container) a second test checks with `ast` that every module path, name and constructor keyword the hook
-relies on exists there, so the skeleton cannot drift from the real thing; and the rebound `get_noise_pred` is run on the stand-in networks against
+were given -- written to a temporary directory, imported as `lib`, and driven the way lib/apis/adapter3d.py:971-975 drives the real one.  A second
+test checks that every module path, name and constructor keyword the hook relies on exists in the reference (read out of its tree with `ast` into
+tests/golden/dropin_ref_names.json), so the skeleton cannot drift from the real thing; and the rebound `get_noise_pred` is run on the stand-in networks against
 the golden output of the REFERENCE's own method (tests/golden/mixin_ref.npz, tests/golden/make_mixin_golden.py).  Host logic only: no GPU."""
 import ast
 import os
@@ -173,44 +173,67 @@ def test_rebound_get_noise_pred_reproduces_the_reference_method(lib, skeleton):
         np.testing.assert_allclose(out.numpy(), G[name], rtol=1e-5, atol=1e-6)
 
 
-REF = '/root/reference'
+NAMES_GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'dropin_ref_names.json')
+ATTRS = {'lib/models/decoders/image_space_ss.py': [f'self.{a} = {a}' for a in ('num_in_ch', 'num_out_ch', 'num_feat', 'num_conv', 'upscale', 'act_type')],
+         'lib/models/decoders/mesh_renderer/base_mesh_renderer.py': [f'self.{a} = {a}' for a in ('near', 'far', 'ssaa', 'texture_filter')],
+         'lib/models/decoders/ingp_decoder.py': ['self.encoder = tcnn.Encoding', 'self.mlp = MLP', 'self.n_levels = n_levels', 'self.max_resolution = max_resolution',
+                                                 'self.blob_density', 'self.blob_radius', 'self.sigmoid_saturation']}
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference tree not present (GPU box)')
-def test_the_names_the_hook_relies_on_exist_in_the_reference():
-    from mvedit_amd import dropin
-
+def _reference_names(ref):
+    """What the hook relies on, read with `ast` out of the reference tree at `ref`: module-level names, class methods, constructor keywords and
+    bases of the pipelines, and which of the attribute assignments in ATTRS the decoders' sources contain."""
     def tree(rel):
-        return ast.parse(open(os.path.join(REF, rel)).read())
+        return ast.parse(open(os.path.join(ref, rel)).read())
 
     def assigned_all(t):
         for n in t.body:
             if isinstance(n, ast.Assign) and any(isinstance(x, ast.Name) and x.id == '__all__' for x in n.targets):
                 return [e.value for e in n.value.elts]
-    assert assigned_all(tree('lib/ops/raymarching/__init__.py')) == list(dropin.RAYMARCHING_NAMES)
-    star = [n.module for n in tree('lib/ops/__init__.py').body if isinstance(n, ast.ImportFrom) and n.names[0].name == '*']
-    assert 'raymarching' in star and 'shencoder' in star
-    assert 'SHEncoder' in [a.name for n in tree('lib/ops/shencoder/__init__.py').body if isinstance(n, ast.ImportFrom) for a in n.names]
     mix = [n for n in tree('lib/pipelines/adapter3d_mixin.py').body if isinstance(n, ast.ClassDef) and n.name == 'Adapter3DMixin'][0]
-    assert set(dropin.MIXIN_METHODS) <= {f.name for f in mix.body if isinstance(f, ast.FunctionDef)}
-    assert {'unet_enc', 'unet_dec'} <= {f.name for f in tree('lib/models/architecture/diffusers.py').body if isinstance(f, ast.FunctionDef)}
-    exported = assigned_all(tree('lib/pipelines/__init__.py'))
-    assert sorted(exported) == sorted(dropin.PIPELINE_CLASSES.values())
-    for mod, cls, base, names in PIPELINES:
-        t = tree(f'lib/pipelines/{mod}.py')
-        c = [n for n in t.body if isinstance(n, ast.ClassDef) and n.name == cls][0]
+    pipelines = {}
+    for mod, cls, _, _ in PIPELINES:
+        c = [n for n in tree(f'lib/pipelines/{mod}.py').body if isinstance(n, ast.ClassDef) and n.name == cls][0]
         init = [f for f in c.body if isinstance(f, ast.FunctionDef) and f.name == '__init__'][0]
-        assert [a.arg for a in init.args.args][1:] == names, (cls, [a.arg for a in init.args.args])
+        pipelines[f'{mod}.{cls}'] = dict(init_args=[a.arg for a in init.args.args][1:], bases=[ast.unparse(b) for b in c.bases])
+    return dict(
+        raymarching_all=assigned_all(tree('lib/ops/raymarching/__init__.py')),
+        ops_star_imports=[n.module for n in tree('lib/ops/__init__.py').body if isinstance(n, ast.ImportFrom) and n.names[0].name == '*'],
+        shencoder_imports=[a.name for n in tree('lib/ops/shencoder/__init__.py').body if isinstance(n, ast.ImportFrom) for a in n.names],
+        mixin_methods=[f.name for f in mix.body if isinstance(f, ast.FunctionDef)],
+        diffusers_functions=[f.name for f in tree('lib/models/architecture/diffusers.py').body if isinstance(f, ast.FunctionDef)],
+        pipelines_all=assigned_all(tree('lib/pipelines/__init__.py')),
+        pipelines=pipelines,
+        attributes={rel: [a for a in attrs if a in open(os.path.join(ref, rel)).read()] for rel, attrs in ATTRS.items()})
+
+
+def test_the_names_the_hook_relies_on_exist_in_the_reference():
+    """Every module path, name and constructor keyword the hook relies on exists in the reference, so that the skeleton cannot drift from the real
+    thing.  The names were read out of the reference tree by _reference_names and are stored in tests/golden/dropin_ref_names.json
+    (`python tests/test_dropin.py <reference tree>` rewrites it)."""
+    import json
+    from mvedit_amd import dropin
+    r = json.load(open(NAMES_GOLD))
+    assert r['raymarching_all'] == list(dropin.RAYMARCHING_NAMES)
+    assert 'raymarching' in r['ops_star_imports'] and 'shencoder' in r['ops_star_imports']
+    assert 'SHEncoder' in r['shencoder_imports']
+    assert set(dropin.MIXIN_METHODS) <= set(r['mixin_methods'])
+    assert {'unet_enc', 'unet_dec'} <= set(r['diffusers_functions'])
+    assert sorted(r['pipelines_all']) == sorted(dropin.PIPELINE_CLASSES.values())
+    for mod, cls, base, names in PIPELINES:
+        p = r['pipelines'][f'{mod}.{cls}']
+        assert p['init_args'] == names, (cls, p['init_args'])
         assert dropin.PIPELINE_CLASSES[f'lib.pipelines.{mod}'] == cls
-        assert base == 'object' or base in [ast.unparse(b) for b in c.bases], (cls, [ast.unparse(b) for b in c.bases])
+        assert base == 'object' or base in p['bases'], (cls, p['bases'])
     # the attributes the makers read off the loaded modules
-    src = open(os.path.join(REF, 'lib/models/decoders/image_space_ss.py')).read()
-    for a in ('num_in_ch', 'num_out_ch', 'num_feat', 'num_conv', 'upscale', 'act_type'):
-        assert f'self.{a} = {a}' in src, a
-    src = open(os.path.join(REF, 'lib/models/decoders/mesh_renderer/base_mesh_renderer.py')).read()
-    for a in ('near', 'far', 'ssaa', 'texture_filter'):
-        assert f'self.{a} = {a}' in src, a
-    src = open(os.path.join(REF, 'lib/models/decoders/ingp_decoder.py')).read()
-    for a in ('self.encoder = tcnn.Encoding', 'self.mlp = MLP', 'self.n_levels = n_levels', 'self.max_resolution = max_resolution', 'self.blob_density', 'self.blob_radius',
-              'self.sigmoid_saturation'):
-        assert a in src, a
+    for rel, attrs in ATTRS.items():
+        for a in attrs:
+            assert a in r['attributes'][rel], a
+
+
+if __name__ == '__main__':
+    import json
+    with open(NAMES_GOLD, 'w') as f:
+        json.dump(_reference_names(sys.argv[1]), f, indent=1)
+        f.write('\n')
+    print('wrote', NAMES_GOLD)

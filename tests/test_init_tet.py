@@ -1,6 +1,6 @@
 """NeRF -> DMTet hand-over (`mvedit_amd.pipelines.utils.init_tet`) against the REFERENCE'S OWN FUNCTION executed on the CPU
 (lib/pipelines/utils.py:156-184, cut out with `ast`; its file download / np.load / device='cuda' are stood in for, the density comes from an
-analytic stand-in decoder).  Golden for boxes without /root/reference: tests/golden/init_tet_ref.npz (`python tests/test_init_tet.py`)."""
+analytic stand-in decoder), stored in tests/golden/init_tet_ref.npz (`python tests/test_init_tet.py` rewrites it from the reference tree)."""
 import ast
 import os
 import types
@@ -55,7 +55,7 @@ def _reference(vertices, indices):
 def test_init_tet_equals_reference_function():
     vertices, indices = _grid()
     got = [t.numpy() for t in init_tet(_Decoder(), vertices, indices, density_thresh=5.0)]
-    ref = _reference(vertices, indices) if os.path.exists(REF) else [np.load(GOLD)[k] for k in ('verts', 'indices', 'sdf')]
+    ref = [np.load(GOLD)[k] for k in ('verts', 'indices', 'sdf')]
     assert got[1].dtype == np.int64 and np.array_equal(got[1], ref[1])
     assert np.array_equal(got[0], ref[0]) and np.array_equal(got[2], ref[2])
     assert (got[2] == -1).any() and (got[2] > 0).any() and (np.abs(got[2]) < 1).any()      # outside the cube / inside the blob / the band

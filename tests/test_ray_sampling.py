@@ -1,7 +1,7 @@
-"""`ray_sample` / `get_raybatch_inds` mirrors (mvedit_amd/pipelines/ray_sampling.py) against the REFERENCE'S OWN METHODS executed here on the
+"""`ray_sample` / `get_raybatch_inds` mirrors (mvedit_amd/pipelines/ray_sampling.py) against the REFERENCE'S OWN METHODS executed on the
 CPU (lib/models/autoencoders/base_nerf.py:245-322, cut out of the class with `ast` because the module imports mmcv / mmgen): same seed ->
-the same rays, patches and targets, bit for bit.  Where /root/reference is absent (GPU box) the committed golden holds the reference's
-outputs (tests/golden/ray_sampling_ref.npz, written by this file's `python tests/test_ray_sampling.py`)."""
+the same rays, patches and targets, bit for bit.  The reference's outputs are stored in tests/golden/ray_sampling_ref.npz, written from the
+reference tree by this file's `python tests/test_ray_sampling.py`."""
 import ast
 import os
 import types
@@ -53,11 +53,8 @@ def _mirror(ps):
 def test_mirror_equals_reference_methods(k):
     c = CASES[k]
     got, nb = _run(*_mirror(c['ps']), c, seed=k)
-    if os.path.exists(REF):
-        ref, nb_ref = _run(*_reference_methods(c['ps']), c, seed=k)
-    else:
-        g = np.load(GOLD)
-        ref, nb_ref = [g[f'c{k}_{i}'] for i in range(int(g[f'c{k}_n']))], (int(g[f'c{k}_nb']) or None)
+    g = np.load(GOLD)
+    ref, nb_ref = [g[f'c{k}_{i}'] for i in range(int(g[f'c{k}_n']))], (int(g[f'c{k}_nb']) or None)
     assert nb == nb_ref and len(got) == len(ref)
     for a, b in zip(got, ref):
         assert a.shape == b.shape and np.array_equal(a, b)

@@ -1,6 +1,6 @@
 """Outer-loop schedules (mvedit_amd/pipelines/schedules.py) against the reference's own module-level functions
-(lib/pipelines/mvedit_3d_pipeline.py:41-78) executed on a progress grid; committed golden for boxes without /root/reference
-(`python tests/test_schedules.py` rewrites it).  Bit-equal: same float expressions."""
+(lib/pipelines/mvedit_3d_pipeline.py:41-78) executed on a progress grid, stored in tests/golden/schedules_ref.npz
+(`python tests/test_schedules.py` rewrites it from the reference tree).  Bit-equal: same float expressions."""
 import ast
 import os
 
@@ -32,7 +32,7 @@ def _reference():
 
 
 def test_schedules_equal_reference_functions():
-    ref = _reference() if os.path.exists(REF) else dict(np.load(GOLD))
+    ref = dict(np.load(GOLD))
     got = _table({n: getattr(S, n) for n in NAMES})
     for n in NAMES:
         assert np.array_equal(got[n], ref[n]), n

@@ -226,22 +226,12 @@ def test_mconv_vs_torch(lib, dtype, B, H, W, Cin, N, k, pad, dil, gate, res, act
     assert torch.equal(one, out[sl])
 
 
-def test_do_segmentation_host_logic_equals_reference_function():
-    """mvedit_amd.pipelines.utils.do_segmentation / Adapter3DMixin.get_tgt_masks against the reference's own functions EXECUTED
-    (lib/pipelines/utils.py:73-107, adapter3d_mixin.py:14-19, cut out with ast) over a stand-in segmentor; skipped where /root/reference is absent."""
-    import ast
-    import types
-    import torch.nn.functional as F
-    ref = '/root/reference/lib/pipelines/utils.py'
-    if not os.path.exists(ref):
-        pytest.skip('reference tree not present (GPU box)')
-    ns = dict(np=np, torch=torch, F=F)
-    for node in ast.parse(open(ref).read()).body:
-        if isinstance(node, ast.FunctionDef) and node.name == 'do_segmentation':
-            exec(compile(ast.Module([node], []), ref, 'exec'), ns)
-    from mvedit_amd.pipelines.utils import do_segmentation
-    from mvedit_amd.pipelines.adapter3d_mixin import Adapter3DMixin
+SEG_GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'segmentation_ref.npz')
+SEG_CASES = ((0, None), (4, None), (3, (1.0, 1.0, 1.0)))
 
+
+def _segmentation_inputs():
+    """The stand-in segmentor and images both the test and the golden writer run."""
     class Seg(torch.nn.Module):
         def __init__(self):
             super().__init__()
@@ -249,15 +239,49 @@ def test_do_segmentation_host_logic_equals_reference_function():
 
         def forward(self, x):
             return torch.sigmoid((x * self.w.view(1, 3, 1, 1)).sum(1, keepdim=True) * 3 - 1)
-    seg = Seg()
     x = torch.rand(3, 3, 20, 24, generator=torch.Generator().manual_seed(0))
     x[0, :, :8] = 1.0                                    # a white (background-coloured) band
-    for pad, bg in ((0, None), (4, None), (3, (1.0, 1.0, 1.0))):
-        want = ns['do_segmentation'](x, seg, padding=pad, bg_color=bg)
-        got = do_segmentation(x, seg, padding=pad, bg_color=bg)
-        assert torch.equal(got, want), (pad, bg)
-    host = types.SimpleNamespace(segmentation=seg, bg_color=(1.0, 1.0, 1.0))
-    imgs = x.permute(0, 2, 3, 1)[None] * 1.2 - 0.1
-    got = Adapter3DMixin.get_tgt_masks(host, imgs, 3)
-    want = ns['do_segmentation'](imgs.squeeze(0).clip(min=0, max=1).permute(0, 3, 1, 2), seg, padding=3, bg_color=(1.0, 1.0, 1.0))[:, 3][None, ..., None]
-    assert torch.equal(got, want) and got.shape == (1, 3, 20, 24, 1)
+    return Seg(), x, x.permute(0, 2, 3, 1)[None] * 1.2 - 0.1
+
+
+def _reference_segmentation(utils_py):
+    """Outputs of the reference's own do_segmentation (lib/pipelines/utils.py:73-107, cut out with ast and executed) over the stand-in
+    segmentor, for every case of SEG_CASES and for the call of Adapter3DMixin.get_tgt_masks (adapter3d_mixin.py:14-19)."""
+    import ast
+    import torch.nn.functional as F
+    ns = dict(np=np, torch=torch, F=F)
+    for node in ast.parse(open(utils_py).read()).body:
+        if isinstance(node, ast.FunctionDef) and node.name == 'do_segmentation':
+            exec(compile(ast.Module([node], []), utils_py, 'exec'), ns)
+    seg, x, imgs = _segmentation_inputs()
+    out = {}
+    with torch.no_grad():
+        for i, (pad, bg) in enumerate(SEG_CASES):
+            out[f'case{i}'] = ns['do_segmentation'](x, seg, padding=pad, bg_color=bg).numpy()
+        out['tgt_masks'] = ns['do_segmentation'](imgs.squeeze(0).clip(min=0, max=1).permute(0, 3, 1, 2), seg, padding=3,
+                                                 bg_color=(1.0, 1.0, 1.0))[:, 3][None, ..., None].numpy()
+    return out
+
+
+def test_do_segmentation_host_logic_equals_reference_function():
+    """mvedit_amd.pipelines.utils.do_segmentation / Adapter3DMixin.get_tgt_masks against the reference's own functions EXECUTED
+    (lib/pipelines/utils.py:73-107, adapter3d_mixin.py:14-19) over a stand-in segmentor: their outputs are stored in
+    tests/golden/segmentation_ref.npz (`PYTHONPATH=. python tests/test_segmentor.py <reference tree>` rewrites it)."""
+    import types
+    from mvedit_amd.pipelines.utils import do_segmentation
+    from mvedit_amd.pipelines.adapter3d_mixin import Adapter3DMixin
+    g = np.load(SEG_GOLD)
+    seg, x, imgs = _segmentation_inputs()
+    with torch.no_grad():
+        for i, (pad, bg) in enumerate(SEG_CASES):
+            got = do_segmentation(x, seg, padding=pad, bg_color=bg)
+            assert torch.equal(got, torch.from_numpy(g[f'case{i}'])), (pad, bg)
+        host = types.SimpleNamespace(segmentation=seg, bg_color=(1.0, 1.0, 1.0))
+        got = Adapter3DMixin.get_tgt_masks(host, imgs, 3)
+    assert torch.equal(got, torch.from_numpy(g['tgt_masks'])) and got.shape == (1, 3, 20, 24, 1)
+
+
+if __name__ == '__main__':
+    import sys
+    np.savez_compressed(SEG_GOLD, **_reference_segmentation(os.path.join(sys.argv[1], 'lib', 'pipelines', 'utils.py')))
+    print('wrote', SEG_GOLD, os.path.getsize(SEG_GOLD))
