@@ -739,6 +739,24 @@ MVE_API int mve_depth_to_normal(const float* d_depth, const float* d_alpha, int 
 MVE_API int mve_normalize_depth(const float* d_depths, const float* d_alphas, int n_views, int hw, float far_depth,
                                 float alpha_clip, float eps, float* d_out, void* stream);
 
+/* Stand-alone tinycudann HashGrid encoding (the `tcnn.Encoding` of lib/models/decoders/ingp_decoder.py:62-74 and
+ * triplane_ingp_decoder.py:102-114; Python: mvedit_amd.tinycudann.Encoding).  d_x [N,3] f32 already in the unit cube (no bound applied);
+ * d_table [n_rows][n_features] f32; level_* HOST arrays [n_levels] as mve_hashgrid_mlp_decode takes them, every level inside the
+ * n_rows-row table and a hashed level 2^k rows; n_features in {1, 2, 4, 8}, 1 <= n_levels <= 16; interpolation MVE_INTERP_*.
+ * Forward: d_out [N, n_levels * n_features] f32, row-major (level-major inside a row).  N = 0 is a no-op. */
+#define MVE_INTERP_LINEAR 0
+#define MVE_INTERP_SMOOTHSTEP 1
+MVE_API int mve_hashgrid_encode(const float* d_x, uint32_t N, const float* d_table, uint32_t n_rows, int n_features, int n_levels,
+                                const float* level_scale, const uint32_t* level_res, const uint32_t* level_offset,
+                                const uint32_t* level_size, int interpolation, float* d_out, void* stream);
+/* Backward of mve_hashgrid_encode for d_grad_enc = dL/denc [N, n_levels * n_features]: d_grad_table [n_rows][n_features] is
+ * ACCUMULATED into (float atomics, as tiny-cuda-nn; same-cell neighbours are summed first); d_grad_x [N,3] = dL/dx is written when
+ * not NULL (then d_table is read; Smoothstep's d w/dx = 6 t (1 - t) scale, Linear's = scale).  No second-order terms. */
+MVE_API int mve_hashgrid_encode_backward(const float* d_x, uint32_t N, const float* d_table, uint32_t n_rows, int n_features,
+                                         int n_levels, const float* level_scale, const uint32_t* level_res,
+                                         const uint32_t* level_offset, const uint32_t* level_size, int interpolation,
+                                         const float* d_grad_enc, float* d_grad_table, float* d_grad_x, void* stream);
+
 /* =========================================================================
  * 5. Texture-space ops of the mesh path.
  * ========================================================================= */

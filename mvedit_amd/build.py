@@ -32,6 +32,7 @@ EXTRA_FLAGS = {
     'attention.hip': ['-fno-honor-nans'],
     'raymarching.hip': ['-ffp-contract=off'],
     'nerf.hip': ['-ffp-contract=off'],
+    'hashgrid_encode.hip': ['-ffp-contract=off'],
     'raster.hip': ['-ffp-contract=off'],
     'dmtet.hip': ['-ffp-contract=off'],
     'shading.hip': ['-ffp-contract=off'],

@@ -25,6 +25,23 @@ struct DecoderParams {
     HashGridMeta g;
 };
 
+// grid_index of tiny-cuda-nn as the kernels below spell it inline: a level is hashed unless dense strides x + y R + z R^2 fit its rows
+__host__ __device__ __forceinline__ bool level_is_hashed(uint32_t res, uint32_t size) {
+    const bool s1 = res <= size;
+    const bool s2 = s1 && (uint64_t)res * res <= size;
+    const uint64_t stride3 = (uint64_t)res * res * (s2 ? res : 1u);
+    return s2 ? (size < stride3) : true;
+}
+// row of corner c inside its level: a hashed level has 2^k rows (mask = size - 1); a dense index of an in-range point is below 2 * size,
+// anything else (points outside the unit cube) takes the slow path -- the same value as idx % size either way
+__device__ __forceinline__ uint32_t level_row(const uint32_t (&c)[3], bool hashed, uint32_t res, uint32_t size) {
+    if (hashed) return ((c[0] * 1u) ^ (c[1] * 2654435761u) ^ (c[2] * 805459861u)) & (size - 1u);
+    uint32_t idx = c[0] + c[1] * res + c[2] * res * res;
+    if (idx >= size) idx -= size;
+    if (idx >= size) idx %= size;
+    return idx;
+}
+
 // tiny-cuda-nn HashGrid, Smoothstep interpolation, 2 features per level (see oracle/nerf_oracle.py for the restated spec)
 template <int NL>
 __device__ __forceinline__ void hash_encode(const DecoderParams& p, float x, float y, float z, float (&enc)[2 * NL]) {

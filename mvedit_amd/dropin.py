@@ -17,6 +17,9 @@ What `install()` rebinds -- the operator seams of SURVEY.md section 8(b), nothin
      `pipe.image_enhancer`, `pipe.segmentation` and `pipe.mesh_renderer` are replaced by engines built from those modules' own configs and
      state dicts, and `pipe.nerf.render` by the native renderer.  Engines are cached on the source module (`Adapter3DRunner` builds a pipeline
      object per request from the same loaded modules), and rebuilt when the module's parameters have been replaced.
+  4. `tinycudann` (CUDA-only, imported by lib/models/decoders/ingp_decoder.py:5-8 and triplane_ingp_decoder.py:5-8): seeded in `sys.modules`
+     with `Encoding` bound to `mvedit_amd.tinycudann.Encoding`, so the reference's decoders construct and train unchanged.  Decoder
+     modules imported before `install()` (their `tcnn` is None after the failed import) get `tcnn` rebound.
 
 Nothing here computes: every replacement is one of the engines / mirrors INTEGRATION.md documents seam by seam, and a conversion that fails
 raises -- there is no fallback to the torch module.  `uninstall()` restores everything (tests).
@@ -29,6 +32,8 @@ import types
 RAYMARCHING_NAMES = ('near_far_from_aabb', 'sph_from_ray', 'morton3D', 'morton3D_invert', 'packbits', 'march_rays_train',
                      'composite_rays_train', 'march_rays', 'composite_rays', 'batch_near_far_from_aabb', 'batch_composite_rays_train')
 SHENCODER_NAMES = ('SHEncoder', 'sh_encode')
+TCNN_NAMES = ('Encoding',)
+TCNN_DECODERS = ('lib.models.decoders.ingp_decoder', 'lib.models.decoders.triplane_ingp_decoder')
 MIXIN_METHODS = ('get_noise_pred', 'get_noise_pred_p1', 'get_noise_pred_p2')
 PIPELINE_CLASSES = {'lib.pipelines.mvedit_3d_pipeline': 'MVEdit3DPipeline',
                     'lib.pipelines.mvedit_texture_pipeline': 'MVEditTexturePipeline',
@@ -206,8 +211,13 @@ def _patch_pipeline(mod):
     _set(cls, '__init__', __init__)
 
 
+def _patch_tcnn_decoder(mod):
+    _set(mod, 'tcnn', sys.modules['tinycudann'])
+
+
 PATCHERS = {'lib.pipelines.adapter3d_mixin': _patch_mixin, 'lib.models.architecture.diffusers': _patch_arch_diffusers}
 PATCHERS.update({k: _patch_pipeline for k in PIPELINE_CLASSES})
+PATCHERS.update({k: _patch_tcnn_decoder for k in TCNN_DECODERS})
 
 
 class _PostImport(importlib.abc.MetaPathFinder):
@@ -263,9 +273,10 @@ def install():
     """Idempotent.  Call before the reference's modules are imported (already-imported ones are patched in place)."""
     if _state['installed']:
         return
-    from . import raymarching, shencoder
+    from . import raymarching, shencoder, tinycudann
     _seed_module('lib.ops.raymarching', RAYMARCHING_NAMES, raymarching)
     _seed_module('lib.ops.shencoder', SHENCODER_NAMES, shencoder)
+    _seed_module('tinycudann', TCNN_NAMES, tinycudann)
     for name, patch in PATCHERS.items():
         if name in sys.modules:
             patch(sys.modules[name])

@@ -20,7 +20,13 @@ from . import _lib
 def grid_meta(n_levels=12, base_resolution=16, max_resolution=320, bound=1.0, log2_hashmap_size=19):
     """tiny-cuda-nn HashGrid level table: (scale f32, resolution, row offset, rows) per level + total rows."""
     pls = np.exp2(np.log2(max_resolution * bound / base_resolution) / (n_levels - 1))     # ingp_decoder.py:71
-    log2_pls = np.float32(np.log2(np.float32(pls)))
+    return level_table(n_levels, base_resolution, pls, log2_hashmap_size)
+
+
+def level_table(n_levels, base_resolution, per_level_scale, log2_hashmap_size=19):
+    """The level table of a tiny-cuda-nn HashGrid given its `per_level_scale` (float32 arithmetic, as tiny-cuda-nn):
+    scale_l = exp2(l * log2(per_level_scale)) * base - 1, resolution ceil(scale_l) + 1, rows min(next_multiple(res^3, 8), 2^log2)."""
+    log2_pls = np.float32(np.log2(np.float32(per_level_scale)))
     meta, off = [], 0
     for lvl in range(n_levels):
         scale = np.float32(np.exp2(np.float32(lvl) * log2_pls, dtype=np.float32) * np.float32(base_resolution) - np.float32(1.0))
