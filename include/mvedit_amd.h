@@ -949,6 +949,27 @@ MVE_API int mve_antialias_backward_pos(const float* d_color, const float* d_grad
                                        const float* d_pos, int V, const int32_t* d_tri, int F, const int32_t* d_opp, float* d_grad_pos,
                                        void* stream);
 
+/* Geometry gradient of the texture path (csrc/texture_grad.hip; what mvedit_amd.nvdiffrast.torch adds to the ops above): the derivative
+ * of the forward formulas of csrc/texmip_core.h with the tap indices, the level pair and every pixel's triangle held fixed.
+ *   texture_grad_uv         d <g_out, dr.texture(tex, uv, uv_da)> / d uv -> d_g_uv [n,h,w,2] and / d uv_da -> d_g_uv_da [n,h,w,4] (either may be
+ *                           NULL).  d_uv_da NULL: filter_mode='linear' (d_mips / max_level unused, d_g_uv_da must be NULL); otherwise
+ *                           'linear-mipmap-linear' with the level stack of mve_mip_build.  d_g_uv_da is 0 where the level is clamped
+ *                           (magnification, top level); at an exactly isotropic footprint the square root's term is taken as 0.  No rast
+ *                           argument: every pixel is differentiated at its uv.  Bt = 1 broadcasts; any C.  Gathers only, no atomics.
+ *   interpolate_da_backward from d_g_da [B,npix,2C]: d_g_rast_db [B,npix,4] is overwritten (0 on empty pixels); d_g_attr [attr_batch,V,C] is
+ *                           ADDED to with float atomics (the buffer mve_interpolate_backward adds into).  Either may be NULL.
+ *   rasterize_db_backward   from d_g_db [B,H,W,4]: the direct dependence of rast_db on the triangle's clip (x, y, w) is ADDED to d_g_pos
+ *                           [B,V,4] with float atomics; its dependence on the stored (b0, b1) overwrites d_g_rast [B,H,W,4] (channels 2, 3
+ *                           zero), to be added to the gradient of rast and passed to mve_rasterize_backward.  Either may be NULL. */
+MVE_API int mve_texture_grad_uv(const float* d_tex0, const float* d_mips, int Bt, int H, int W, int C, int max_level, const float* d_uv,
+                                const float* d_uv_da, const float* d_g_out, int n, int h, int w, float* d_g_uv, float* d_g_uv_da,
+                                void* stream);
+MVE_API int mve_interpolate_da_backward(const float* d_attr, int attr_batch, int V, int C, const float* d_rast, const float* d_rast_db, int B,
+                                        int npix, const int32_t* d_tri, int F, const float* d_g_da, float* d_g_rast_db, float* d_g_attr,
+                                        void* stream);
+MVE_API int mve_rasterize_db_backward(const float* d_pos, int B, int V, const int32_t* d_tri, int F, const float* d_rast, int H, int W,
+                                      const float* d_g_db, float* d_g_pos, float* d_g_rast, void* stream);
+
 /* TRACER-B7 foreground segmentor (lib/models/segmentors/tracer_b7.py:16-73, called once per denoise step from
  * lib/pipelines/adapter3d_mixin.py:14-19; EfficientNet-B7 encoder lib/models/architecture/tracerb7/efficientnet.py + TRACER decoder
  * tracer.py / att_modules.py / conv_modules.py): the operators the GEMM / 3x3-conv entry points do not cover.  Activations are NHWC

@@ -41,6 +41,7 @@ EXTRA_FLAGS = {
     'blur.hip': ['-ffp-contract=off'],
     'sh.hip': ['-ffp-contract=off'],
     'triplane.hip': ['-ffp-contract=off'],
+    'texture_grad.hip': ['-ffp-contract=off'],
 }
 
 

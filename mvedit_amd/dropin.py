@@ -20,6 +20,10 @@ What `install()` rebinds -- the operator seams of SURVEY.md section 8(b), nothin
   4. `tinycudann` (CUDA-only, imported by lib/models/decoders/ingp_decoder.py:5-8 and triplane_ingp_decoder.py:5-8): seeded in `sys.modules`
      with `Encoding` bound to `mvedit_amd.tinycudann.Encoding`, so the reference's decoders construct and train unchanged.  Decoder
      modules imported before `install()` (their `tcnn` is None after the failed import) get `tcnn` rebound.
+  5. `nvdiffrast` and `nvdiffrast.torch` (CUDA-only, imported at module level by lib/models/decoders/mesh_renderer/base_mesh_renderer.py:5, whose
+     MeshRenderer the runner constructs and calls itself, lib/apis/adapter3d.py:88): seeded in `sys.modules` with `mvedit_amd.nvdiffrast` and
+     `mvedit_amd.nvdiffrast.torch` (parent first), so `import nvdiffrast.torch as dr` resolves and `dr.*` computes on the native kernels.  A
+     base_mesh_renderer imported before `install()` gets `dr` rebound.
 
 Nothing here computes: every replacement is one of the engines / mirrors INTEGRATION.md documents seam by seam, and a conversion that fails
 raises -- there is no fallback to the torch module.  `uninstall()` restores everything (tests).
@@ -34,6 +38,7 @@ RAYMARCHING_NAMES = ('near_far_from_aabb', 'sph_from_ray', 'morton3D', 'morton3D
 SHENCODER_NAMES = ('SHEncoder', 'sh_encode')
 TCNN_NAMES = ('Encoding',)
 TCNN_DECODERS = ('lib.models.decoders.ingp_decoder', 'lib.models.decoders.triplane_ingp_decoder')
+NVDR_RENDERER = 'lib.models.decoders.mesh_renderer.base_mesh_renderer'
 MIXIN_METHODS = ('get_noise_pred', 'get_noise_pred_p1', 'get_noise_pred_p2')
 PIPELINE_CLASSES = {'lib.pipelines.mvedit_3d_pipeline': 'MVEdit3DPipeline',
                     'lib.pipelines.mvedit_texture_pipeline': 'MVEditTexturePipeline',
@@ -215,9 +220,14 @@ def _patch_tcnn_decoder(mod):
     _set(mod, 'tcnn', sys.modules['tinycudann'])
 
 
+def _patch_nvdr_renderer(mod):
+    _set(mod, 'dr', sys.modules['nvdiffrast.torch'])
+
+
 PATCHERS = {'lib.pipelines.adapter3d_mixin': _patch_mixin, 'lib.models.architecture.diffusers': _patch_arch_diffusers}
 PATCHERS.update({k: _patch_pipeline for k in PIPELINE_CLASSES})
 PATCHERS.update({k: _patch_tcnn_decoder for k in TCNN_DECODERS})
+PATCHERS[NVDR_RENDERER] = _patch_nvdr_renderer
 
 
 class _PostImport(importlib.abc.MetaPathFinder):
@@ -269,14 +279,22 @@ def _seed_module(name, names, source):
                 _set(parent, n, getattr(source, n))
 
 
+def _seed_as(name, module):
+    """`module` itself under the reference's name (a package with a submodule: the objects are shared, not copied)."""
+    _state['seeded'].append((name, sys.modules.get(name)))
+    sys.modules[name] = module
+
+
 def install():
     """Idempotent.  Call before the reference's modules are imported (already-imported ones are patched in place)."""
     if _state['installed']:
         return
-    from . import raymarching, shencoder, tinycudann
+    from . import nvdiffrast, raymarching, shencoder, tinycudann
     _seed_module('lib.ops.raymarching', RAYMARCHING_NAMES, raymarching)
     _seed_module('lib.ops.shencoder', SHENCODER_NAMES, shencoder)
     _seed_module('tinycudann', TCNN_NAMES, tinycudann)
+    _seed_as('nvdiffrast', nvdiffrast)                  # parent first: `import nvdiffrast.torch as dr` looks both up
+    _seed_as('nvdiffrast.torch', nvdiffrast.torch)
     for name, patch in PATCHERS.items():
         if name in sys.modules:
             patch(sys.modules[name])
