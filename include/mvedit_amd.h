@@ -372,6 +372,12 @@ MVE_API int mve_nhwc_to_nchw(int dst_dtype, int src_dtype, const void* d_x, int 
                              void* d_y, void* stream);
 /* diffusers Timesteps(dim, flip_sin_to_cos=True, downscale_freq_shift=0): out[b] = [cos(t*f_k) | sin(t*f_k)] */
 MVE_API int mve_timestep_embedding(int dtype, const float* d_t, int B, int dim, void* d_out, void* stream);
+/* The operand row of add_embedding.linear_1 under addition_embed_type='text_time' (diffusers 0.27.2 UNet2DConditionModel.get_aug_embed):
+ *   out[b] = cat([text_embeds[b], Timesteps(time_embed_dim, flip_sin_to_cos=True, freq_shift=0)(time_ids[b]).flatten()]).to(dtype)
+ * i.e. [B, text_dim + n_ids * time_embed_dim] in `dtype` (f16 | bf16): the converted text_embeds (text_dtype: f32 | f16 | bf16), then per time id
+ * time_embed_dim values, cosines first, then sines.  d_time_ids is f32 [B, n_ids]. */
+MVE_API int mve_text_time_embedding(int dtype, const void* d_text_embeds, int text_dtype, int text_dim, const float* d_time_ids, int n_ids,
+                                    int time_embed_dim, int B, void* d_out, void* stream);
 MVE_API int mve_silu(int dtype, const void* d_x, void* d_y, size_t n, void* stream);
 MVE_API int mve_axpy(int dtype, const void* d_a, const void* d_b, float alpha, void* d_y, size_t n, void* stream); /* y = a + alpha*b */
 /* probs[m][:N] = softmax(scores[m][:N]) (fp32 in, `dtype` out): the softmax of the VAE mid-block attention (diffusers Attention with
@@ -674,6 +680,25 @@ MVE_API int mve_unet_set_attention(void* handle, int ip_tokens, float ip_scale, 
  * 4 more bytes per stream element and pass.  pair = 0 (default): the single 16-bit tensors of rounds 1-3.  Negative: query.  Returns the previous
  * mode; the mode is part of the plan key. */
 MVE_API int mve_unet_set_residual_mode(void* handle, int pair);
+/* SDXL added-condition embedding of a UNet or ControlNet handle (diffusers 0.27.2 UNet2DConditionModel / ControlNetModel with
+ * addition_embed_type='text_time'; the reference passes `added_cond_kwargs` to both, lib/pipelines/adapter3d_mixin.py:99-125).  Mirrors
+ *   time_embeds = self.add_time_proj(time_ids.flatten())                       # Timesteps(addition_time_embed_dim, True, 0), fp32
+ *   add_embeds  = torch.concat([text_embeds, time_embeds.reshape(B, -1)], -1).to(emb.dtype)   # [B, projection_input_dim]
+ *   emb         = emb + self.add_embedding(add_embeds)                         # TimestepEmbedding: linear_1, SiLU, linear_2
+ * where `emb` is the output of time_embedding.linear_2.
+ * mve_unet_set_addition_embed declares it: addition_type 1 = 'text_time' (0 = none), projection_input_dim = the in_features of
+ * add_embedding.linear_1.  Call it after mve_unet_create / mve_controlnet_create and BEFORE the first mve_unet_load_param (MVE_ERR_STATE
+ * afterwards): it adds add_embedding.linear_{1,2}.{weight,bias} to the parameter table and to the required names.  The addition type is
+ * part of the plan key. */
+MVE_API int mve_unet_set_addition_embed(void* handle, int addition_type, int addition_time_embed_dim, int projection_input_dim);
+/* Binds the added conditions of the following forwards (mve_unet_forward phases 0 / 1, mve_controlnet_forward) of a 'text_time' handle:
+ * caller-owned device memory d_text_embeds [B, text_dim] (text_dtype: f32 | f16 | bf16) and d_time_ids [B, n_ids] (f32), which are read by
+ * every forward until the next call, so they must stay valid; text_dim + n_ids * addition_time_embed_dim must equal projection_input_dim
+ * and B the forward's batch.  Both pointers NULL: unbind.  A 'text_time' handle run without a binding returns MVE_ERR_STATE (it never
+ * embeds zeros); a binding on a handle without the embedding is MVE_ERR_STATE too.  Under mve_unet_graph the bound pointers and
+ * widths are part of the graph key. */
+MVE_API int mve_unet_bind_added_cond(void* handle, const void* d_text_embeds, int text_dtype, int text_dim, const float* d_time_ids, int n_ids,
+                                     int B);
 MVE_API size_t mve_unet_ref_store_bytes(void* handle, int B, int ref_H, int ref_W, int ref_skip);
 
 /* (No reference counterpart: executor introspection, the source of bench.py's per-kernel roofline figures.)

@@ -5,6 +5,8 @@ lib/pipelines/adapter3d_mixin.py:101-116, :173-186, :279-287) on top of the nati
         sample, t, encoder_hidden_states=..., controlnet_cond=[img, depth], conditioning_scale=[w0, w1],
         guess_mode=False, added_cond_kwargs=None, return_dict=False)
 
+`added_cond_kwargs={'text_embeds', 'time_ids'}` (SDXL ControlNets, addition_embed_type='text_time') is bound on every net.
+
 The returned tensors have the reference's logical shape [B, C, h, w] but live in channels-last memory in the engine dtype:
 `UNet2DConditionEngine` recognises that and consumes them without a layout conversion; everything else treats them as ordinary
 tensors.  MultiControlNetEngine sums the nets' outputs natively (each net accumulates into the same buffers)."""
@@ -36,6 +38,7 @@ class ControlNetEngine(UNet2DConditionEngine):
                   arr(c['block_out_channels']), c['layers_per_block'], arr(c['down_attn']), arr(c['num_heads']),
                   arr(c['transformer_layers']), c['cross_attention_dim'], c['norm_num_groups'], float(c['norm_eps']),
                   int(c['use_linear_projection']))
+        self._declare_addition_embed()
         self._ws = None
         self._ip = (0, 1.0)
         self._ref_keep = None
@@ -59,8 +62,9 @@ class ControlNetEngine(UNet2DConditionEngine):
 
     shares_cond = True        # run() takes B / R conditioning images for a batch of B (pipelines/adapter3d_mixin.py: the CFG halves share theirs)
 
-    def run(self, sample, timestep, encoder_hidden_states, cond, scale, down, mid, accumulate, profile=False):
+    def run(self, sample, timestep, encoder_hidden_states, cond, scale, down, mid, accumulate, profile=False, added_cond_kwargs=None):
         B, _, H, W = sample.shape
+        self._bind_added_cond(added_cond_kwargs, B)
         io = encoder_hidden_states.dtype
         ctx = encoder_hidden_states.to(self.device).contiguous()
         sample = sample.to(device=self.device, dtype=io).contiguous()
@@ -91,11 +95,10 @@ class ControlNetEngine(UNet2DConditionEngine):
     def __call__(self, sample, timestep, encoder_hidden_states, controlnet_cond, conditioning_scale=1.0, guess_mode=False,
                  added_cond_kwargs=None, return_dict=False, **unused):
         assert not guess_mode, 'guess_mode is never enabled on this path (adapter3d_mixin.py:107)'
-        if added_cond_kwargs:
-            raise NotImplementedError('added_cond_kwargs (SDXL) has no reference implementation in MVEdit (SURVEY.md F9)')
         B, _, H, W = sample.shape
         down, mid = self.new_outputs(B, H, W)
-        self.run(sample, timestep, encoder_hidden_states, controlnet_cond, conditioning_scale, down, mid, False)
+        self.run(sample, timestep, encoder_hidden_states, controlnet_cond, conditioning_scale, down, mid, False,
+                 added_cond_kwargs=added_cond_kwargs)
         if not self.channels_last:
             return [d.contiguous() for d in down], mid.contiguous()
         return down, mid
@@ -114,8 +117,9 @@ class MultiControlNetEngine:
         assert len(controlnet_cond) == len(conditioning_scale) == len(self.nets)
         B, _, H, W = sample.shape
         down, mid = self.nets[0].new_outputs(B, H, W)
+        ack = {} if added_cond_kwargs is None else dict(added_cond_kwargs=added_cond_kwargs)      # every net gets the same added conditions
         for i, (net, cond, scale) in enumerate(zip(self.nets, controlnet_cond, conditioning_scale)):
-            net.run(sample, timestep, encoder_hidden_states, cond, scale, down, mid, accumulate=i > 0)
+            net.run(sample, timestep, encoder_hidden_states, cond, scale, down, mid, accumulate=i > 0, **ack)
         if not getattr(self.nets[0], 'channels_last', True):
             return [d.contiguous() for d in down], mid.contiguous()
         return down, mid

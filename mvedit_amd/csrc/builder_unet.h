@@ -9,6 +9,7 @@ int Builder::build(int B_, int H, int W, int n_img, int has_res, int io_dtype, i
     const int Bb = B_;   // lambdas below must not capture `this`
     { const AttnOpts keep = pl.ao; pl = Plan(); pl.ao = keep; }
     pl.B = Bb; pl.H = H; pl.W = W; pl.n_img = n_img; pl.has_res = has_res; pl.io_dtype = io_dtype; pl.res_nhwc = res_nhwc;
+    pl.add_type = c.add_type;
     const int e = 2, n = c.n_levels, L = c.layers_per_block, T = c.temb_dim();
     const int d = dt;
     ld_temb = u.sum_temb; ld_kv = u.sum_kv;
@@ -40,6 +41,29 @@ int Builder::build(int B_, int H, int W, int n_img, int has_res, int io_dtype, i
     Ref emb = ws((size_t)Bb * T * e);
     gemm(e1, T, wt("time.w2"), T, emb, T, Bb, T, T, wt("time.b2"), Ref(), 0, 0, Ref(), 0, 0, "time_embedding.linear_2");
     rel(e1);
+    if (c.add_type == 1) {
+        // addition_embed_type='text_time' (diffusers UNet2DConditionModel.get_aug_embed, ControlNetModel alike): emb += add_embedding(cat([text_embeds,
+        // add_time_proj(time_ids.flatten()).reshape(B, -1)])).  The sum is the second GEMM's fused residual: one rounding where the half modules round
+        // the embedding and the sum separately.
+        const int P = c.add_P, td = c.add_time_dim;
+        Ref row = ws((size_t)Bb * P * e);
+        op(OC_OTHER, 0, "add_embedding.text_time", [=](const Run& r) {
+            if (!r.add_text || !r.add_ids || r.add_text_dim + r.add_n_ids * td != P) {
+                mve_set_error("unet: a text_time engine needs text_embeds / time_ids (mve_unet_bind_added_cond) before every forward");
+                return (int)MVE_ERR_STATE;
+            }
+            return mve_text_time_embedding(d, r.add_text, r.add_text_dtype, r.add_text_dim, r.add_ids, r.add_n_ids, td, Bb, r.p(row), r.stream);
+        });
+        Ref a1 = ws((size_t)Bb * T * e);
+        gemm(row, P, wt("add.w1"), P, a1, T, Bb, T, P, wt("add.b1"), Ref(), 0, 0, Ref(), 0, 0, "add_embedding.linear_1");
+        rel(row);
+        op(OC_OTHER, 0, "silu", [=](const Run& r) { return mve_silu(d, r.p(a1), r.p(a1), (size_t)Bb * T, r.stream); });
+        Ref emb_sum = ws((size_t)Bb * T * e);
+        gemm(a1, T, wt("add.w2"), T, emb_sum, T, Bb, T, T, wt("add.b2"), Ref(), 0, 0, emb, T, 0, "add_embedding.linear_2");
+        rel(a1);
+        rel(emb);
+        emb = emb_sum;
+    }
     op(OC_OTHER, 0, "silu", [=](const Run& r) { return mve_silu(d, r.p(emb), r.p(emb), (size_t)Bb * T, r.stream); });
     tproj = ws((size_t)Bb * ld_temb * 4);
     gemm(emb, T, wt("temb_proj.w"), T, tproj, ld_temb, Bb, ld_temb, T, wt("temb_proj.b"), Ref(), 0, 0, Ref(), 0, MVE_GEMM_OUT_F32,

@@ -47,6 +47,30 @@ __global__ void k_timestep_embedding(const float* __restrict__ t, int B, int dim
     out[i] = Tag::from_f32(c < half ? cosf(arg) : sinf(arg));
 }
 
+// diffusers UNet2DConditionModel.get_aug_embed, addition_embed_type='text_time': the operand row of add_embedding.linear_1,
+//   cat([text_embeds, Timesteps(td, flip_sin_to_cos=True, freq_shift=0)(time_ids.flatten()).reshape(B, -1)], -1).to(emb.dtype)
+// out [B, P] with P = text_w + n_ids * td: the converted text_embeds row, then [cos | sin] halves of td values per time id.
+// Same frequency formula and accurate cosf / sinf as k_timestep_embedding (the ids are pixel sizes: 1024 rad and more).
+template <class Tag, class Src>
+__global__ __launch_bounds__(NT) void k_text_time_embedding(const Src* __restrict__ text, int text_w, const float* __restrict__ ids, int n_ids,
+                                                            int td, int B, typename Tag::T* __restrict__ out) {
+    const int P = text_w + n_ids * td;
+    const size_t i = (size_t)blockIdx.x * NT + threadIdx.x;
+    if (i >= (size_t)B * P) return;
+    const int b = (int)(i / P), c = (int)(i - (size_t)b * P);
+    float v;
+    if (c < text_w) {
+        v = (float)text[(size_t)b * text_w + c];
+    } else {
+        const int j = c - text_w, id = j / td, cc = j - id * td, half = td / 2;
+        const int k = cc < half ? cc : cc - half;
+        const float freq = expf(-9.210340371976184f * (float)k / (float)half);   // ln(10000)
+        const float arg = ids[(size_t)b * n_ids + id] * freq;
+        v = cc < half ? cosf(arg) : sinf(arg);
+    }
+    out[i] = Tag::from_f32(v);
+}
+
 template <class Tag>
 __global__ __launch_bounds__(NT) void k_silu(const typename Tag::T* __restrict__ x, typename Tag::T* __restrict__ y, size_t n8) {
     typedef typename Tag::V8 V8;
@@ -282,6 +306,30 @@ int mve_timestep_embedding(int dtype, const float* t, int B, int dim, void* out,
     if (dtype == MVE_F16) k_timestep_embedding<F16Tag><<<grid, 256, 0, (hipStream_t)stream>>>(t, B, dim, (f16*)out);
     else if (dtype == MVE_BF16) k_timestep_embedding<BF16Tag><<<grid, 256, 0, (hipStream_t)stream>>>(t, B, dim, (bf16*)out);
     else { mve_set_error("timestep_embedding: bad dtype"); return MVE_ERR_ARG; }
+    MVE_LAUNCH_CHECK();
+    return MVE_OK;
+}
+
+int mve_text_time_embedding(int dtype, const void* text_embeds, int text_dtype, int text_dim, const float* time_ids, int n_ids, int time_embed_dim,
+                            int B, void* out, void* stream) {
+    if (B == 0) return MVE_OK;
+    MVE_CHECK(text_embeds && time_ids && out && B > 0 && text_dim > 0 && n_ids > 0 && time_embed_dim > 0 && time_embed_dim % 2 == 0, MVE_ERR_ARG,
+              "text_time_embedding: bad arguments");
+    const unsigned grid = mve_cdiv((size_t)B * ((size_t)text_dim + (size_t)n_ids * time_embed_dim), NT);
+    hipStream_t s = (hipStream_t)stream;
+#define GO(TAG, T16, SRC) k_text_time_embedding<TAG, SRC><<<grid, NT, 0, s>>>((const SRC*)text_embeds, text_dim, time_ids, n_ids, time_embed_dim, B, (T16*)out)
+    if (dtype == MVE_F16) {
+        if (text_dtype == MVE_F32) GO(F16Tag, f16, float);
+        else if (text_dtype == MVE_F16) GO(F16Tag, f16, f16);
+        else if (text_dtype == MVE_BF16) GO(F16Tag, f16, bf16);
+        else { mve_set_error("text_time_embedding: bad text_embeds dtype"); return MVE_ERR_ARG; }
+    } else if (dtype == MVE_BF16) {
+        if (text_dtype == MVE_F32) GO(BF16Tag, bf16, float);
+        else if (text_dtype == MVE_F16) GO(BF16Tag, bf16, f16);
+        else if (text_dtype == MVE_BF16) GO(BF16Tag, bf16, bf16);
+        else { mve_set_error("text_time_embedding: bad text_embeds dtype"); return MVE_ERR_ARG; }
+    } else { mve_set_error("text_time_embedding: bad dtype"); return MVE_ERR_ARG; }
+#undef GO
     MVE_LAUNCH_CHECK();
     return MVE_OK;
 }

@@ -40,6 +40,7 @@ int mve_layernorm(int, const void*, int, void*, int, int, int, const float*, con
 int mve_nchw_to_nhwc(int, int, const void*, int, int, int, int, int, void*, void*);
 int mve_nhwc_to_nchw(int, int, const void*, int, int, int, int, int, void*, void*);
 int mve_timestep_embedding(int, const float*, int, int, void*, void*);
+int mve_text_time_embedding(int, const void*, int, int, const float*, int, int, int, void*, void*);
 int mve_silu(int, const void*, void*, size_t, void*);
 int mve_axpy(int, const void*, const void*, float, void*, size_t, void*);
 int mve_softmax_rows(int, const float*, size_t, int, int, void*, size_t, void*);
@@ -124,6 +125,9 @@ struct Config {
     int vae = 0;                       // AutoencoderKL half: 1 = post_quant_conv + Decoder, 2 = Encoder + quant_conv (no time embedding,
                                        // no transformers; in_ch / out_ch are the half's own input / output channels, both <= 8)
     int dtype, in_ch, out_ch, n_levels, layers_per_block, ctx_dim, groups, linear_proj;
+    // UNet2DConditionModel / ControlNetModel addition_embed_type (mve_unet_set_addition_embed): 0 none, 1 'text_time' (SDXL);
+    // add_time_dim = addition_time_embed_dim, add_P = projection_class_embeddings_input_dim (in_features of add_embedding.linear_1)
+    int add_type = 0, add_time_dim = 0, add_P = 0;
     float eps;
     int ch[MAX_LEVELS], attn[MAX_LEVELS], heads[MAX_LEVELS], tlayers[MAX_LEVELS];
     int temb_dim() const { return ch[0] * 4; }
@@ -153,6 +157,9 @@ struct Run {
     void* const* cn_out = nullptr;            // ControlNet: n_skips + 1 output tensors (NHWC, engine dtype)
     float cn_scale = 1.0f;                    // conditioning_scale
     int cn_accum = 0;                         // 1: add to what the outputs already hold (MultiControlNetModel's sum)
+    const void* add_text = nullptr;           // 'text_time': text_embeds [B, add_text_dim] (add_text_dtype), time_ids f32 [B, add_n_ids]
+    const float* add_ids = nullptr;           //              (mve_unet_bind_added_cond)
+    int add_text_dtype = 0, add_text_dim = 0, add_n_ids = 0;
     hipStream_t stream;
     void* p(const Ref& r) const {
         switch (r.kind) {
@@ -204,6 +211,7 @@ struct AttnOpts {
 
 struct Plan {
     int B = 0, H = 0, W = 0, n_img = 1, has_res = 0, io_dtype = 0, res_nhwc = 0, ctx_len = 0;
+    int add_type = 0;          // Config::add_type the plan was built for
     AttnOpts ao;
     size_t ref_store_bytes = 0;
     unsigned long long last_use = 0;
@@ -273,6 +281,8 @@ struct Unet {
     bool fuse_sc = false;                       // conv_shortcut folded into conv2's K loop (all widths multiples of 64)
     std::map<std::string, int> sc_cin;          // resnet prefix -> input width, for resnets with a shortcut
     std::string err;
+    // added conditions of a 'text_time' handle, bound by mve_unet_bind_added_cond (caller-owned device memory)
+    struct AddedCond { const void* text = nullptr; const float* ids = nullptr; int text_dtype = 0, text_dim = 0, n_ids = 0, B = 0; } added;
     // optional hipGraph replay of mve_unet_forward (mve_unet_graph): a call whose plan AND every pointer argument equal an earlier
     // call's is captured on its second sighting and replayed from then on (launch-bound small-batch forwards, e.g. 8 images per rank)
     struct GraphEntry {

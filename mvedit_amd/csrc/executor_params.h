@@ -224,6 +224,20 @@ void layout_params(Unet& u) {
     u.slab_bytes = sb.top;
 }
 
+// add_embedding (TimestepEmbedding(add_P, temb_dim)) of a 'text_time' handle: appended behind the existing slots, before the slab is allocated
+// (mve_unet_set_addition_embed)
+void layout_addition_embed(Unet& u) {
+    const Config& c = u.cfg;
+    SlabBuilder sb{u, u.slab_bytes};
+    const size_t T = c.temb_dim(), P = c.add_P;
+    auto need = [&](const std::string& n) { u.expected.push_back(n); };
+    sb.add("add.w1", T * P, false); need("add_embedding.linear_1.weight");
+    sb.add("add.b1", T, true); need("add_embedding.linear_1.bias");
+    sb.add("add.w2", T * T, false); need("add_embedding.linear_2.weight");
+    sb.add("add.b2", T, true); need("add_embedding.linear_2.bias");
+    u.slab_bytes = sb.top;
+}
+
 bool ends_with(const std::string& s, const std::string& suf) {
     return s.size() >= suf.size() && s.compare(s.size() - suf.size(), suf.size(), suf) == 0;
 }
@@ -364,6 +378,10 @@ int load_param(Unet& u, const std::string& name, const void* src, int src_dtype,
     else if (name == "time_embedding.linear_1.bias") rc = vec(P("time.b1"), 0, T, 1);
     else if (name == "time_embedding.linear_2.weight") rc = mat(P("time.w2"), 0, T, T, T);
     else if (name == "time_embedding.linear_2.bias") rc = vec(P("time.b2"), 0, T, 1);
+    else if (c.add_type && name == "add_embedding.linear_1.weight") rc = mat(P("add.w1"), 0, T, c.add_P, c.add_P);
+    else if (c.add_type && name == "add_embedding.linear_1.bias") rc = vec(P("add.b1"), 0, T, 1);
+    else if (c.add_type && name == "add_embedding.linear_2.weight") rc = mat(P("add.w2"), 0, T, T, T);
+    else if (c.add_type && name == "add_embedding.linear_2.bias") rc = vec(P("add.b2"), 0, T, 1);
     else if (name == "conv_norm_out.weight") rc = vec(P("norm_out.g"), 0, c.ch[0], 1);
     else if (name == "conv_norm_out.bias") rc = vec(P("norm_out.b"), 0, c.ch[0], 1);
     else if (name == "conv_out.weight") {

@@ -31,7 +31,7 @@ int ensure_plan(Unet& u, int B, int H, int W, int n_img, int has_res, int io_dty
     for (auto& pp : u.plans) {
         const Plan& p = *pp;
         if (p.B == B && p.H == H && p.W == W && p.n_img == n_img && p.has_res == has_res && p.io_dtype == io_dtype &&
-            p.res_nhwc == res_nhwc && p.ctx_len == ctx_len && p.ao == u.ao) {
+            p.res_nhwc == res_nhwc && p.ctx_len == ctx_len && p.add_type == u.cfg.add_type && p.ao == u.ao) {
             pp->last_use = u.tick;
             u.cur = pp.get();
             return MVE_OK;
@@ -55,6 +55,16 @@ int ensure_plan(Unet& u, int B, int H, int W, int n_img, int has_res, int io_dty
     }
     u.plans.push_back(std::move(np));
     u.cur = u.plans.back().get();
+    return MVE_OK;
+}
+
+// added conditions of a forward that runs the prologue: checked against the handle and the batch, then handed to the ops through Run
+int take_added_cond(const Unet& u, int B, Run& r, const char* who) {
+    if (!u.cfg.add_type) return MVE_OK;
+    const Unet::AddedCond& a = u.added;
+    MVE_CHECK(a.text && a.ids, MVE_ERR_STATE, "%s: addition_embed_type 'text_time' needs text_embeds / time_ids (mve_unet_bind_added_cond) before the forward", who);
+    MVE_CHECK(a.B == B, MVE_ERR_ARG, "%s: added conditions are bound for a batch of %d, the forward runs %d", who, a.B, B);
+    r.add_text = a.text; r.add_ids = a.ids; r.add_text_dtype = a.text_dtype; r.add_text_dim = a.text_dim; r.add_n_ids = a.n_ids;
     return MVE_OK;
 }
 
@@ -151,6 +161,8 @@ int mve_controlnet_forward(void* handle, const void* d_sample, int io_dtype, con
     r.down_res = nullptr; r.mid_res = nullptr; r.ref_store = nullptr;
     r.cn_cond = d_cond; r.cn_out = d_outputs; r.cn_scale = conditioning_scale; r.cn_accum = accumulate ? 1 : 0;
     r.stream = (hipStream_t)stream;
+    rc = take_added_cond(*u, B, r, "controlnet_forward");
+    if (rc) return rc;
     std::vector<hipEvent_t> ev;
     if (op_ms) {
         ev.resize(pl.ops.size() + 1);
@@ -442,6 +454,10 @@ int mve_unet_forward(void* handle, int phase, const void* d_sample, int io_dtype
     MVE_CHECK(pl.ref_store_bytes == 0 || (u->ref_store && u->ref_store_bytes >= pl.ref_store_bytes), MVE_ERR_NOMEM,
               "unet_forward: reference store %zu < required %zu bytes", u->ref_store_bytes, pl.ref_store_bytes);
     r.stream = (hipStream_t)stream;
+    if (phase != 2) {      // unet_dec reuses the emb of its unet_enc state
+        rc = take_added_cond(*u, B, r, "unet_forward");
+        if (rc) return rc;
+    }
     const size_t lo = phase == 2 ? pl.enc_end : 0, hi = phase == 1 ? pl.enc_end : pl.ops.size();
     if (u->graph_mode && !op_ms) {
         // hipGraph replay (opt-in): identical plan + pointers as an earlier call -> capture on the second sighting, replay afterwards
@@ -449,6 +465,10 @@ int mve_unet_forward(void* handle, int phase, const void* d_sample, int io_dtype
                   "unet_forward: hipGraph replay cannot capture the legacy default stream -- run under a non-default stream (torch.cuda.stream(...))");
         std::vector<const void*> key = {d_sample, d_timesteps, d_ctx, d_out, d_workspace, d_mid_residual, u->ref_store, stream};
         if (has_res) for (int i = 0; i < u->cfg.n_levels * (u->cfg.layers_per_block + 1); ++i) key.push_back(down_residuals[i]);
+        if (r.add_text) {      // bound added conditions: addresses and geometry (the graph's kernel arguments hold them)
+            key.push_back(r.add_text); key.push_back(r.add_ids);
+            key.push_back((const void*)(size_t)(((size_t)r.add_text_dim << 32) | ((size_t)r.add_n_ids << 8) | (size_t)r.add_text_dtype));
+        }
         Unet::GraphEntry* ge = nullptr;
         for (auto& g : u->graphs)
             if (g.plan_uid == pl.uid && g.phase == phase && g.ptrs == key) { ge = &g; break; }
@@ -532,6 +552,40 @@ int mve_unet_set_residual_mode(void* handle, int pair) {
     const int old = u->ao.residual_pair;
     if (pair >= 0) u->ao.residual_pair = pair ? 1 : 0;     // part of the plan key: plans of either mode stay cached side by side
     return old;
+}
+
+int mve_unet_set_addition_embed(void* handle, int addition_type, int addition_time_embed_dim, int projection_input_dim) {
+    MVE_CHECK(handle, MVE_ERR_ARG, "unet_set_addition_embed: null handle");
+    Unet* u = (Unet*)handle;
+    Config& c = u->cfg;
+    MVE_CHECK(!c.vae && !c.sr && !c.lpips, MVE_ERR_ARG, "unet_set_addition_embed: a UNet / ControlNet handle is needed");
+    MVE_CHECK(addition_type == 0 || addition_type == 1, MVE_ERR_ARG, "unet_set_addition_embed: addition type %d (0 = none, 1 = text_time)", addition_type);
+    MVE_CHECK(!u->slab && u->loaded.empty(), MVE_ERR_STATE, "unet_set_addition_embed: parameters are already loaded; declare the embedding right after create");
+    MVE_CHECK(!c.add_type, MVE_ERR_STATE, "unet_set_addition_embed: the handle already has an addition embedding");
+    if (addition_type == 0) return MVE_OK;
+    MVE_CHECK(addition_time_embed_dim > 0 && addition_time_embed_dim % 2 == 0, MVE_ERR_ARG, "unet_set_addition_embed: addition_time_embed_dim %d must be even",
+              addition_time_embed_dim);
+    MVE_CHECK(projection_input_dim > addition_time_embed_dim && projection_input_dim % 8 == 0, MVE_ERR_ARG,
+              "unet_set_addition_embed: projection input width %d must be a multiple of 8 above addition_time_embed_dim", projection_input_dim);
+    c.add_type = addition_type; c.add_time_dim = addition_time_embed_dim; c.add_P = projection_input_dim;
+    layout_addition_embed(*u);
+    return MVE_OK;
+}
+
+int mve_unet_bind_added_cond(void* handle, const void* d_text_embeds, int text_dtype, int text_dim, const float* d_time_ids, int n_ids, int B) {
+    MVE_CHECK(handle, MVE_ERR_ARG, "unet_bind_added_cond: null handle");
+    Unet* u = (Unet*)handle;
+    const Config& c = u->cfg;
+    MVE_CHECK(c.add_type == 1, MVE_ERR_STATE, "unet_bind_added_cond: the handle has no addition embedding (mve_unet_set_addition_embed)");
+    if (!d_text_embeds && !d_time_ids) { u->added = Unet::AddedCond(); return MVE_OK; }
+    MVE_CHECK(d_text_embeds && d_time_ids, MVE_ERR_ARG, "unet_bind_added_cond: text_embeds and time_ids come together");
+    MVE_CHECK(text_dtype == MVE_F32 || text_dtype == MVE_F16 || text_dtype == MVE_BF16, MVE_ERR_ARG, "unet_bind_added_cond: bad text_embeds dtype %d", text_dtype);
+    MVE_CHECK(B > 0 && text_dim > 0 && n_ids > 0, MVE_ERR_ARG, "unet_bind_added_cond: bad shape");
+    MVE_CHECK((long long)text_dim + (long long)n_ids * c.add_time_dim == c.add_P, MVE_ERR_ARG,
+              "unet_bind_added_cond: text width %d + %d time ids x %d != projection input width %d", text_dim, n_ids, c.add_time_dim, c.add_P);
+    u->added.text = d_text_embeds; u->added.ids = d_time_ids; u->added.text_dtype = text_dtype; u->added.text_dim = text_dim;
+    u->added.n_ids = n_ids; u->added.B = B;
+    return MVE_OK;
 }
 
 int mve_controlnet_set_cond_repeat(void* handle, int repeat) {

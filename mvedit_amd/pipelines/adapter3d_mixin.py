@@ -73,13 +73,15 @@ class Adapter3DMixin:
         if extra_control_batches is None:
             extra_control_batches = []
         same_shape = len({tuple(b.shape[1:]) for b in latent_batches}) == 1
-        fuse = self.fuse_chunks and same_shape and added_cond_kwargs_batches is None and len(latent_batches) > 1
+        fuse = self.fuse_chunks and same_shape and len(latent_batches) > 1
         if fuse:
             cat = lambda bs: None if bs[0] is None else torch.cat(list(bs), dim=0)
             cond = self._cat_shared_cond if self._controlnet_shares_cond() else cat
             noise_pred = self._unet_chunk(
                 cat(latent_batches), cat(prompt_embeds_batches), cond(ctrl_images_batches), cond(ctrl_depths_batches),
-                [cond(e) for e in extra_control_batches], t, tile_weight, depth_weight, None)
+                [cond(e) for e in extra_control_batches], t, tile_weight, depth_weight,
+                # SDXL added conditions ({'text_embeds': [chunks], 'time_ids': [chunks]}) are per item: concatenated like latents and prompts
+                None if added_cond_kwargs_batches is None else {k: cat(v) for k, v in added_cond_kwargs_batches.items()})
         else:
             outs = []
             for i, (lat, emb, ci, cd, *extra) in enumerate(zip(latent_batches, prompt_embeds_batches, ctrl_images_batches,

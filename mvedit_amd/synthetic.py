@@ -44,7 +44,8 @@ def _transformer_shapes(p, c, ctx, layers, linear):
 
 
 def param_shapes(cfg):
-    """Ordered {name: shape} of UNet2DConditionModel(**cfg).state_dict() in diffusers 0.27.2."""
+    """Ordered {name: shape} of UNet2DConditionModel(**cfg).state_dict() in diffusers 0.27.2 (add_embedding.* included when the config has
+    addition_embed_type='text_time'; controlnet_param_shapes inherits them)."""
     ch = cfg['block_out_channels']
     L = cfg['layers_per_block']
     temb = ch[0] * 4
@@ -53,6 +54,10 @@ def param_shapes(cfg):
     s = {'conv_in.weight': (ch[0], cfg['in_channels'], 3, 3), 'conv_in.bias': (ch[0],),
          'time_embedding.linear_1.weight': (temb, ch[0]), 'time_embedding.linear_1.bias': (temb,),
          'time_embedding.linear_2.weight': (temb, temb), 'time_embedding.linear_2.bias': (temb,)}
+    if cfg.get('addition_embed_type') == 'text_time':      # SDXL: add_embedding = TimestepEmbedding(projection_class_embeddings_input_dim, temb)
+        P = cfg['projection_class_embeddings_input_dim']
+        s.update({'add_embedding.linear_1.weight': (temb, P), 'add_embedding.linear_1.bias': (temb,),
+                  'add_embedding.linear_2.weight': (temb, temb), 'add_embedding.linear_2.bias': (temb,)})
     n = len(ch)
     cin = ch[0]
     for i, cout in enumerate(ch):

@@ -30,6 +30,18 @@ SD21_CONFIG = dict(
     down_attn=(True, True, True, False), num_heads=(5, 10, 20, 20), cross_attention_dim=1024, norm_num_groups=32,
     norm_eps=1e-5, transformer_layers=(1, 1, 1, 1), use_linear_projection=True)
 
+# Stable Diffusion XL base 1.0 topology, restated from the published unet/config.json of stabilityai/stable-diffusion-xl-base-1.0 (three levels, no
+# attention at level 0, transformer depth 2 / 10, head_dim 64, ctx 2048, linear projections, 'text_time' added-condition embedding of
+# 6 time ids x 256 + 1280 pooled text = 2816 -> 1280).  PARITY UNPINNED: diffusers is not importable here and the reference ships no SDXL pipeline
+# (SURVEY.md F9), so this topology is checked against the repository's own oracle only.  transformer_layers is 0 where down_attn is false.
+SDXL_CONFIG = dict(
+    in_channels=4, out_channels=4, block_out_channels=(320, 640, 1280), layers_per_block=2,
+    down_attn=(False, True, True), num_heads=(5, 10, 20), cross_attention_dim=2048, norm_num_groups=32,
+    norm_eps=1e-5, transformer_layers=(0, 2, 10), use_linear_projection=True,
+    addition_embed_type='text_time', addition_time_embed_dim=256, projection_class_embeddings_input_dim=2816)
+
+ADDITION_TYPES = {None: 0, 'text_time': 1}
+
 OP_CLASSES = ('conv3x3', 'linear', 'attention', 'norm', 'other')
 
 
@@ -42,10 +54,27 @@ def config_from_diffusers(cfg):
     heads = tuple(heads) if isinstance(heads, (list, tuple)) else (heads,) * n
     tl = g('transformer_layers_per_block', 1)
     tl = tuple(tl) if isinstance(tl, (list, tuple)) else (tl,) * n
+    down_types = tuple(g('down_block_types'))
+    up_types = g('up_block_types')
+    if up_types is not None and tuple('CrossAttn' in t for t in up_types) != tuple('CrossAttn' in t for t in reversed(down_types)):
+        raise NotImplementedError(f'up_block_types {tuple(up_types)} do not mirror down_block_types {down_types}')
+    for key in ('class_embed_type', 'encoder_hid_dim_type'):
+        if g(key) is not None:
+            raise NotImplementedError(f'{key}={g(key)!r} is not implemented by the engine')
+    add = g('addition_embed_type')
+    if add not in ADDITION_TYPES:
+        raise NotImplementedError(f'addition_embed_type={add!r} is not implemented by the engine (None and \'text_time\' are)')
+    down_attn = tuple('CrossAttn' in t for t in down_types)
+    # a level without attention has no transformer layers (the last entry stays: it is the mid block's depth too)
+    tl = tuple(int(l) if (a or i == n - 1) else 0 for i, (l, a) in enumerate(zip(tl, down_attn)))
+    extra = {}
+    if add == 'text_time':
+        extra = dict(addition_embed_type=add, addition_time_embed_dim=int(g('addition_time_embed_dim')),
+                     projection_class_embeddings_input_dim=int(g('projection_class_embeddings_input_dim')))
     return dict(in_channels=g('in_channels'), out_channels=g('out_channels'), block_out_channels=ch,
-                layers_per_block=g('layers_per_block'), down_attn=tuple('CrossAttn' in t for t in g('down_block_types')),
+                layers_per_block=g('layers_per_block'), down_attn=down_attn,
                 num_heads=heads, cross_attention_dim=g('cross_attention_dim'), norm_num_groups=g('norm_num_groups'),
-                norm_eps=g('norm_eps'), transformer_layers=tl, use_linear_projection=bool(g('use_linear_projection', False)))
+                norm_eps=g('norm_eps'), transformer_layers=tl, use_linear_projection=bool(g('use_linear_projection', False)), **extra)
 
 
 class UNet2DConditionEngine:
@@ -62,14 +91,56 @@ class UNet2DConditionEngine:
                   arr(c['block_out_channels']), c['layers_per_block'], arr(c['down_attn']), arr(c['num_heads']),
                   arr(c['transformer_layers']), c['cross_attention_dim'], c['norm_num_groups'], float(c['norm_eps']),
                   int(c['use_linear_projection']))
+        self._declare_addition_embed()
         self._ws = None
         self._ip = (0, 1.0)          # IP-Adapter: (num_tokens, scale); see set_ip_adapter
         self._ref_keep = None
         # the attributes the reference's pipelines / runner read from a diffusers model
         self.config = SimpleNamespace(in_channels=c['in_channels'], out_channels=c['out_channels'], sample_size=64,
-                                      center_input_sample=False, addition_embed_type=None, **{
+                                      center_input_sample=False, addition_embed_type=c.get('addition_embed_type'), **{
                                           'block_out_channels': c['block_out_channels'],
                                           'cross_attention_dim': c['cross_attention_dim']})
+
+    def _declare_addition_embed(self):
+        """Declare the SDXL 'text_time' added-condition embedding on the fresh native handle (before any parameter is loaded)."""
+        add = self.cfg.get('addition_embed_type')
+        if add not in ADDITION_TYPES:
+            raise NotImplementedError(f'addition_embed_type={add!r} is not implemented by the engine')
+        self._ack_keep = None
+        if add is not None:
+            _lib.call('mve_unet_set_addition_embed', self._h, ADDITION_TYPES[add], int(self.cfg['addition_time_embed_dim']),
+                      int(self.cfg['projection_class_embeddings_input_dim']))
+
+    def _bind_added_cond(self, added_cond_kwargs, B):
+        """Validate diffusers' added_cond_kwargs={'text_embeds': [B, D], 'time_ids': [B, n]} (any float dtype) and bind them for the forwards
+        that follow (mve_unet_bind_added_cond).  Tensors the kernel can read as they are (device, contiguous; text_embeds f32 / f16 / bf16,
+        time_ids f32) are bound in place, so a caller that updates them in place needs no new binding."""
+        add = self.cfg.get('addition_embed_type')
+        if add is None:
+            if added_cond_kwargs:
+                raise ValueError('added_cond_kwargs given to an engine without an addition embedding (config addition_embed_type is None)')
+            return
+        if not added_cond_kwargs:
+            raise ValueError("this engine has addition_embed_type='text_time': added_cond_kwargs={'text_embeds', 'time_ids'} is required")
+        for key in ('text_embeds', 'time_ids'):
+            if key not in added_cond_kwargs:
+                raise ValueError(f"added_cond_kwargs lacks '{key}' (addition_embed_type='text_time' needs text_embeds and time_ids)")
+        text, ids = added_cond_kwargs['text_embeds'], added_cond_kwargs['time_ids']
+        td, P = int(self.cfg['addition_time_embed_dim']), int(self.cfg['projection_class_embeddings_input_dim'])
+        for key, t in (('text_embeds', text), ('time_ids', ids)):
+            if not torch.is_tensor(t) or t.dim() != 2 or not t.is_floating_point():
+                raise ValueError(f"added_cond_kwargs['{key}'] must be a 2-D floating-point tensor [batch, width]")
+            if t.shape[0] != B:
+                raise ValueError(f"added_cond_kwargs['{key}'] has batch {t.shape[0]}, the sample has {B}")
+        if text.shape[1] + ids.shape[1] * td != P:
+            raise ValueError(f'added_cond_kwargs widths: text_embeds {text.shape[1]} + time_ids {ids.shape[1]} x {td} != '
+                             f'projection_class_embeddings_input_dim {P}')
+        if text.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            text = text.float()
+        text = text.to(self.device).contiguous()
+        ids = ids.to(device=self.device, dtype=torch.float32).contiguous()
+        self._ack_keep = (text, ids)
+        _lib.call('mve_unet_bind_added_cond', self._h, _lib.ptr(text), _dt(text), text.shape[1], _lib.ptr(ids), ids.shape[1], B)
 
     def __del__(self):
         h = getattr(self, '_h', None)
@@ -233,9 +304,7 @@ class UNet2DConditionEngine:
                  down_block_additional_residuals=None, mid_block_additional_residual=None, added_cond_kwargs=None,
                  return_dict=False, out=None, **unused):
         """diffusers UNet2DConditionModel.forward signature subset used by the reference."""
-        if added_cond_kwargs:
-            raise NotImplementedError('added_cond_kwargs (SDXL micro-conditioning) has no reference implementation '
-                                      'in MVEdit (SURVEY.md F9)')
+        self._bind_added_cond(added_cond_kwargs, sample.shape[0])
         n_img = int((cross_attention_kwargs or {}).get('num_cross_attn_imgs', 1))
         self._set_attention(cross_attention_kwargs, sample.shape[0], sample.shape[2], sample.shape[3])
         res = self._run(0, sample, timestep, encoder_hidden_states, n_img, down_block_additional_residuals,
@@ -246,16 +315,18 @@ class UNet2DConditionEngine:
 
     forward = __call__
 
-    def profile(self, sample, timestep, encoder_hidden_states, num_cross_attn_imgs=1):
+    def profile(self, sample, timestep, encoder_hidden_states, num_cross_attn_imgs=1, added_cond_kwargs=None):
         """-> (out, [(class, label, flops, ms)]) with HIP-event timing around every launch."""
+        self._bind_added_cond(added_cond_kwargs, sample.shape[0])
         self._set_attention(None, *[sample.shape[i] for i in (0, 2, 3)])
         out, ms = self._run(0, sample, timestep, encoder_hidden_states, num_cross_attn_imgs, None, None, None, profile=True)
         return out, [(c, lab, fl, m) for (ph, c, fl, lab), m in zip(self.op_table(), ms)]
 
     # 2-pass mode ---------------------------------------------------------------------------------------
-    def enc(self, sample, timestep, encoder_hidden_states, cross_attention_kwargs=None, workspace=None):
+    def enc(self, sample, timestep, encoder_hidden_states, cross_attention_kwargs=None, workspace=None, added_cond_kwargs=None):
         """unet_enc: runs conv_in + down blocks; the returned state handle owns the workspace holding
-        (emb, down_block_res_samples, sample) for a later dec()."""
+        (emb, down_block_res_samples, sample) for a later dec().  added_cond_kwargs (SDXL) enter here: dec() reuses the state's emb."""
+        self._bind_added_cond(added_cond_kwargs, sample.shape[0])
         n_img = int((cross_attention_kwargs or {}).get('num_cross_attn_imgs', 1))
         B, _, H, W = sample.shape
         self._set_attention(cross_attention_kwargs, B, H, W)
@@ -315,7 +386,7 @@ class UNet2DConditionEngine:
 def unet_enc(unet, sample, timestep, encoder_hidden_states, cross_attention_kwargs=None, added_cond_kwargs=None):
     """lib/models/architecture/diffusers.py:57-99.  Returns (emb, down_block_res_samples, sample) in the reference;
     here the three live inside one opaque state object, returned in the same 3-tuple positions for drop-in use."""
-    st = unet.enc(sample, timestep, encoder_hidden_states, cross_attention_kwargs)
+    st = unet.enc(sample, timestep, encoder_hidden_states, cross_attention_kwargs, added_cond_kwargs=added_cond_kwargs)
     return st, st, st
 
 
