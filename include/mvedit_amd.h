@@ -680,6 +680,20 @@ MVE_API int mve_unet_set_attention(void* handle, int ip_tokens, float ip_scale, 
  * 4 more bytes per stream element and pass.  pair = 0 (default): the single 16-bit tensors of rounds 1-3.  Negative: query.  Returns the previous
  * mode; the mode is part of the plan key. */
 MVE_API int mve_unet_set_residual_mode(void* handle, int pair);
+/* CFG prefix of the UNet executor (no reference counterpart).  Under classifier-free guidance the batch is [uncond | text]: the reference builds it as
+ * torch.cat([latents] * 2) with one timestep, so both halves enter the network identical and differ in encoder_hidden_states alone.  Every op in front
+ * of the first cross-attention (SD-1.5: down_blocks.0.resnets.0 and the first transformer up to attn2.to_q, one of the five 4096-token self-attentions
+ * among them; conv_in stays at full batch) then produces bit-identical rows for image b and image b + B / 2.  With the switch on (the default) a probe
+ * kernel at the start of each forward compares the two halves of `sample` and of the time-embedding projection rows bit for bit and writes a device flag;
+ * the blocks of those ops that belong to the second half return at once when it is 1, and one copy kernel hands the first half of the tensors that
+ * outlive the prefix to the second.  The launches are the full-batch problem's either way (same tiles, same K slices), so the output is bit-identical
+ * to the switch-off output for ANY input; nothing is decided on the host and a graph replay re-evaluates the flag.  Planned when B is even,
+ * (B / 2) % num_cross_attn_imgs == 0 and reference attention is off; ControlNet handles are not covered.  on < 0: query.  Returns the previous value;
+ * the switch is part of the plan key. */
+MVE_API int mve_unet_tune_cfg_prefix(void* handle, int on);
+/* Diagnostics (tests / tools): synchronises the stream of the last mve_unet_forward that ran a prologue and returns its flag -- 1: the halves were
+ * identical and the prefix ran once, 0: they differed, -1: that plan had no prefix.  Errors are MVE_ERR_HIP, or MVE_ERR_STATE for a null handle (-1 is taken). */
+MVE_API int mve_unet_cfg_prefix_state(void* handle);
 /* SDXL added-condition embedding of a UNet or ControlNet handle (diffusers 0.27.2 UNet2DConditionModel / ControlNetModel with
  * addition_embed_type='text_time'; the reference passes `added_cond_kwargs` to both, lib/pipelines/adapter3d_mixin.py:99-125).  Mirrors
  *   time_embeds = self.add_time_proj(time_ids.flatten())                       # Timesteps(addition_time_embed_dim, True, 0), fp32

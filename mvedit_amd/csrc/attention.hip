@@ -41,6 +41,7 @@ struct AttnParams {
     int B, Lq, Lk, Lk2, heads;
     float scale_log2e;   // softmax scale * log2(e); 1 when the caller folded it into Q (mve_attention_prescaled)
     int prescaled;
+    const int* skip_if;  // second-half predicate (common.h): non-null -> blocks of batch items [B / 2, B) return at once when *skip_if != 0
 };
 
 // chunk permutation of K row `row` (a bijection inside every group of 4 chunks, applied identically by the LDS-DMA source side and the
@@ -123,10 +124,11 @@ __global__ __launch_bounds__(NT, (OCC ? OCC : (D > 80 ? 1 : 2))) void k_attentio
 
     const int q_tiles = (p.Lq + QB - 1) / QB;
     const unsigned nblk = (unsigned)(q_tiles * p.heads * p.B);
-    const unsigned bid = mve_xcd_remap(blockIdx.x, nblk);
+    const unsigned bid = p.skip_if ? mve_xcd_remap_halves(blockIdx.x, nblk, nblk / 2) : mve_xcd_remap(blockIdx.x, nblk);
     const int qt = bid % q_tiles;
     const int h = (bid / q_tiles) % p.heads;
     const int b = bid / (q_tiles * p.heads);
+    if (mve_second_half_skipped(p.skip_if, 2 * b >= p.B)) return;
     const int Ltot = p.Lk + p.Lk2;
 
     const T* Qp = reinterpret_cast<const T*>(p.Q);
@@ -479,10 +481,11 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_attention3(const AttnParams p)
 
     const int q_tiles = (p.Lq + QB - 1) / QB;
     const unsigned nblk = (unsigned)(q_tiles * p.heads * p.B);
-    const unsigned bid = mve_xcd_remap(blockIdx.x, nblk);
+    const unsigned bid = p.skip_if ? mve_xcd_remap_halves(blockIdx.x, nblk, nblk / 2) : mve_xcd_remap(blockIdx.x, nblk);
     const int qt = bid % q_tiles;
     const int h = (bid / q_tiles) % p.heads;
     const int b = bid / (q_tiles * p.heads);
+    if (mve_second_half_skipped(p.skip_if, 2 * b >= p.B)) return;
     const int Ltot = p.Lk + p.Lk2;
 
     const T* kb1 = reinterpret_cast<const T*>(p.K) + (size_t)b * p.Lk * p.ldk + h * D;
@@ -1008,6 +1011,8 @@ static int attention_entry(int dtype, const void* Q, int ldq, const void* K, int
     p.B = B; p.Lq = Lq; p.Lk = Lk; p.Lk2 = Lk2; p.heads = heads;
     p.scale_log2e = prescaled ? 1.0f : scale * 1.4426950408889634f;
     p.prescaled = prescaled;
+    p.skip_if = mve_skip_second_half();
+    MVE_CHECK(!p.skip_if || B % 2 == 0, MVE_ERR_ARG, "attention: the second-half predicate needs an even batch (B=%d)", B);
     if (dtype == MVE_F16) return dispatch_d<F16Tag>(p, head_dim, (hipStream_t)stream);
     if (dtype == MVE_BF16) return dispatch_d<BF16Tag>(p, head_dim, (hipStream_t)stream);
     mve_set_error("attention: unsupported dtype %d", dtype);

@@ -170,6 +170,11 @@ int Builder::build(int B_, int H, int W, int n_img, int has_res, int io_dtype, i
         conv(x_in, 8, Bb, H, W, 1, 0, wt("conv_in.w"), c.ch[0], x, wt("conv_in.b"), Ref(), 0, Ref(), 0, "conv_in");
     }
     rel(x_in);
+    // CFG prefix (executor_builder.h): planned for a UNet batch of two equal halves whose cross-image groups do not straddle the middle.  Reference
+    // attention exempts the CFG-first item (ref_skip), so its halves differ; ControlNet engines are the follow-up.  conv_in stays outside: its output
+    // is a skip the last up-block reads at full batch, and it costs less than broadcasting it would.
+    if (!c.controlnet && pl.ao.cfg_prefix && Bb % 2 == 0 && (Bb / 2) % n_img == 0 && pl.ao.ref_mode == 0)
+        begin_prefix((size_t)(Bb / 2) * c.in_ch * H * W * esz(io_dtype), (size_t)(Bb / 2) * ld_temb * 4);
     skips.push_back({x, c.ch[0], H, W});
     int h = H, w = W, cin = c.ch[0];
     for (int i = 0; i < n; ++i) {
@@ -194,6 +199,7 @@ int Builder::build(int B_, int H, int W, int n_img, int has_res, int io_dtype, i
             skips.push_back({x, cin, h, w});
         }
     }
+    end_prefix();          // (a network without cross-attention in its down path: the prefix does not reach into unet_dec)
     pl.enc_end = pl.ops.size();
     if (c.controlnet) {
         const int C = c.ch[n - 1];
@@ -299,6 +305,7 @@ int Builder::build(int B_, int H, int W, int n_img, int has_res, int io_dtype, i
         op(OC_OTHER, 0, "nhwc->nchw", [=](const Run& r) { return mve_nhwc_to_nchw(io_dtype, MVE_F32, r.p(o8), 8, Bb, oc, H, W, r.p(dst), r.stream); });
     }
     pl.ws_bytes = ar.peak + 256;
+    if (pl.cfg_prefix) { *pfx_flag = ar.peak; pl.cfg_flag_off = ar.peak; }      // the flag lives in the tail pad: the workspace size does not move
     pl.ref_store_bytes = ref_off;
     if (!u.err.empty()) { mve_set_error("unet plan: %s", u.err.c_str()); u.err.clear(); return MVE_ERR_STATE; }
     return MVE_OK;

@@ -44,6 +44,21 @@ void mve_set_error(const char* fmt, ...);
         }                                                              \
     } while (0)
 
+// ---------------------------------------------------------------------------
+// Second-half predicate (the UNet executor's CFG prefix).  While a device flag is installed on the calling thread,
+// every GEMM / conv / GroupNorm / LayerNorm / attention launched through the C ABI hands it to its kernels: a block whose work
+// lies wholly in the second half of the leading (image-major) axis returns at once when *flag != 0.  The launch itself --
+// grid, tile family, K slices -- is the full problem's, so the rows that do run get the bits they always got.
+// ---------------------------------------------------------------------------
+const int* mve_skip_second_half();
+void mve_set_skip_second_half(const int* d_flag);      // nullptr clears
+struct MveSkipScope {
+    explicit MveSkipScope(const int* d_flag) { mve_set_skip_second_half(d_flag); }
+    ~MveSkipScope() { mve_set_skip_second_half(nullptr); }
+    MveSkipScope(const MveSkipScope&) = delete;
+    MveSkipScope& operator=(const MveSkipScope&) = delete;
+};
+
 static inline unsigned mve_cdiv(unsigned long long a, unsigned long long b) {
     return (unsigned)((a + b - 1) / b);
 }
@@ -175,4 +190,16 @@ __device__ __forceinline__ unsigned mve_xcd_remap(unsigned bid, unsigned nblk) {
     const unsigned xcd = bid % nx, k = bid / nx;
     const unsigned base = (xcd < r) ? xcd * (q + 1u) : r * (q + 1u) + (xcd - r) * q;
     return base + k;
+}
+
+// The same remap for a launch under the second-half predicate: logical blocks [0, n1) -- the half that always runs -- are spread over all
+// eight XCDs by the hardware block ids [0, n1), the rest by [n1, nblk).  The one-piece remap would hand the first half to XCDs 0-3 alone.
+__device__ __forceinline__ unsigned mve_xcd_remap_halves(unsigned bid, unsigned nblk, unsigned n1) {
+    return bid < n1 ? mve_xcd_remap(bid, n1) : n1 + mve_xcd_remap(bid - n1, nblk - n1);
+}
+
+// true (wave-uniform): the block may leave -- it lies in the second half and the flag says the halves are identical
+__device__ __forceinline__ bool mve_second_half_skipped(const int* skip_if, bool in_second_half) {
+    if (!skip_if || !__builtin_amdgcn_readfirstlane((int)in_second_half)) return false;
+    return __builtin_amdgcn_readfirstlane(*skip_if) != 0;
 }

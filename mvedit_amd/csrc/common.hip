@@ -10,6 +10,10 @@ void mve_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
+static thread_local const int* g_skip_flag = nullptr;
+const int* mve_skip_second_half() { return g_skip_flag; }
+void mve_set_skip_second_half(const int* d_flag) { g_skip_flag = d_flag; }
+
 extern "C" {
 
 const char* mve_last_error(void) { return g_err; }

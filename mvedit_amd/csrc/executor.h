@@ -198,14 +198,17 @@ struct Op {
 //   cn_cond_repeat: ControlNet plans only (mve_controlnet_set_cond_repeat): the conditioning images are given for B / R items and item b uses image
 //                   b mod (B / R) -- under classifier-free guidance both halves of the batch see the same control images
 //                   (mvedit_3d_pipeline.py:1232: `ctrl_images.split(diff_bs) * 2`), so the conditioning embedding runs once, not R times.
+//   cfg_prefix    : UNet plans only (mve_unet_tune_cfg_prefix, default on): the ops in front of the first cross-attention run for the first half of
+//                   the batch alone whenever a device-side probe finds the two halves of sample and time embedding identical (builder_unet.h).
 struct AttnOpts {
     int ip_tokens = 0; float ip_scale = 1.0f;
     int ref_mode = 0, ref_H = 0, ref_W = 0, ref_skip = 0;
     int residual_pair = 0;
     int cn_cond_repeat = 1;
+    int cfg_prefix = 1;
     bool operator==(const AttnOpts& o) const {
         return ip_tokens == o.ip_tokens && ip_scale == o.ip_scale && ref_mode == o.ref_mode && ref_H == o.ref_H && ref_W == o.ref_W &&
-               ref_skip == o.ref_skip && residual_pair == o.residual_pair && cn_cond_repeat == o.cn_cond_repeat;
+               ref_skip == o.ref_skip && residual_pair == o.residual_pair && cn_cond_repeat == o.cn_cond_repeat && cfg_prefix == o.cfg_prefix;
     }
 };
 
@@ -219,6 +222,8 @@ struct Plan {
     std::vector<Op> ops;
     size_t enc_end = 0;        // ops[0, enc_end) = unet_enc
     size_t ws_bytes = 0;
+    bool cfg_prefix = false;   // the CFG prefix is planned (AttnOpts::cfg_prefix and the conditions in Builder::build)
+    size_t cfg_flag_off = 0;   // its device flag: a word of the workspace's tail pad
     double flops[OC_COUNT] = {0, 0, 0, 0, 0};
 };
 
@@ -293,6 +298,9 @@ struct Unet {
         hipGraphExec_t exec = nullptr;
         unsigned long long last_use = 0;
     };
+    // CFG prefix: the flag of the last forward that ran a prologue (null: that plan had no prefix) and the stream it ran on (mve_unet_cfg_prefix_state)
+    const int* cfg_flag = nullptr;
+    hipStream_t cfg_stream = nullptr;
     bool graph_mode = false;
     std::vector<GraphEntry> graphs;
     unsigned long long plan_counter = 0;

@@ -5,6 +5,48 @@
 namespace {
 
 // ---------------------------------------------------------------------------------------------------
+// CFG prefix kernels (Builder::begin_prefix / end_prefix): the device-side probe and the broadcast of the boundary tensors
+// ---------------------------------------------------------------------------------------------------
+__global__ void k_cfg_probe_init(int* __restrict__ flag) { *flag = 1; }
+
+// true: bytes [0, half) and [half, 2 half) of x differ somewhere in this thread's share
+__device__ __forceinline__ bool cfg_halves_differ(const unsigned char* __restrict__ x, size_t half, size_t t, size_t nt) {
+    const unsigned char* y = x + half;
+    unsigned d = 0;
+    if ((((size_t)x | half) & 15) == 0) {
+        const u32x4* X = reinterpret_cast<const u32x4*>(x);
+        const u32x4* Y = reinterpret_cast<const u32x4*>(y);
+        for (size_t i = t; i < half / 16; i += nt) {
+            const u32x4 a = X[i], b = Y[i];
+            d |= (a[0] ^ b[0]) | (a[1] ^ b[1]) | (a[2] ^ b[2]) | (a[3] ^ b[3]);
+        }
+    } else {
+        for (size_t i = t; i < half; i += nt) d |= (unsigned)(x[i] ^ y[i]);
+    }
+    return d != 0;
+}
+
+// Bitwise comparison of the two halves of `sample` (io dtype) and of the time-embedding projection rows (fp32).  The flag was set to 1 by
+// k_cfg_probe_init; every thread that sees a difference stores 0 (all writers store the same value: no ordering is needed).
+__global__ __launch_bounds__(256) void k_cfg_probe(const unsigned char* __restrict__ sample, size_t sample_half, const unsigned char* __restrict__ tproj,
+                                                   size_t tproj_half, int* __restrict__ flag) {
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x, nt = (size_t)gridDim.x * 256;
+    if (cfg_halves_differ(sample, sample_half, t, nt) || cfg_halves_differ(tproj, tproj_half, t, nt)) *flag = 0;
+}
+
+// Tensor j = blockIdx.y: bytes [0, half) copied onto [half, 2 half) when the flag is 1 (16-byte aligned; half a multiple of 16)
+constexpr int CFG_BCAST_MAX = 8;
+struct CfgBcast { unsigned char* p[CFG_BCAST_MAX]; unsigned long long half[CFG_BCAST_MAX]; };
+
+__global__ __launch_bounds__(256) void k_cfg_broadcast(const CfgBcast c, const int* __restrict__ flag) {
+    if (__builtin_amdgcn_readfirstlane(*flag) == 0) return;
+    const unsigned long long half = c.half[blockIdx.y], n16 = half / 16;
+    const u32x4* __restrict__ src = reinterpret_cast<const u32x4*>(c.p[blockIdx.y]);
+    u32x4* __restrict__ dst = reinterpret_cast<u32x4*>(c.p[blockIdx.y] + half);
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n16; i += (unsigned long long)gridDim.x * 256) dst[i] = src[i];
+}
+
+// ---------------------------------------------------------------------------------------------------
 // plan builder
 // ---------------------------------------------------------------------------------------------------
 struct Builder {
@@ -22,7 +64,11 @@ struct Builder {
 
     Builder(Unet& u_, Plan& p) : u(u_), pl(p), c(u_.cfg) {}
 
-    Ref ws(size_t bytes) { Ref r; r.kind = Ref::WS; r.off = ar.alloc(bytes); return r; }
+    Ref ws(size_t bytes) {
+        Ref r; r.kind = Ref::WS; r.off = ar.alloc(bytes);
+        if (pfx_on) pfx_live[r.off] = bytes;
+        return r;
+    }
     // residual_pair mode (AttnOpts::residual_pair): a tensor of the residual stream gets a companion of half its size for its 8-bit low half.  The
     // companion is found through the high half's workspace offset, so the ops below pick it up by themselves: an output with a companion is
     // written as a pair, a residual / normalised input with a companion is read as one.  Everything else -- every MFMA operand read -- sees the
@@ -41,8 +87,9 @@ struct Builder {
     void rel(const Ref& r) {
         if (r.kind != Ref::WS) return;
         auto it = lo_of.find(r.off);
-        if (it != lo_of.end()) { ar.release(it->second.off); lo_of.erase(it); }
+        if (it != lo_of.end()) { ar.release(it->second.off); pfx_live.erase(it->second.off); lo_of.erase(it); }
         ar.release(r.off);
+        pfx_live.erase(r.off);
     }
     Ref wt(const std::string& n, size_t elem_off = 0) {
         auto it = u.params.find(n);
@@ -63,6 +110,76 @@ struct Builder {
     void op(int cls, double flops, const char* what, std::function<int(const Run&)> fn) {
         pl.ops.push_back({cls, flops, what, std::move(fn)});
         pl.flops[cls] += flops;
+    }
+
+    // ---- CFG prefix -------------------------------------------------------------------------------------
+    // Under classifier-free guidance the batch is [uncond | text]: both halves carry the same latents and timesteps and differ in the text context
+    // alone, so every op in front of the first cross-attention produces bit-identical rows for image b and image b + B / 2.  The ops recorded
+    // between begin_prefix() and end_prefix() stay what they are -- one op-list entry each, the launches of the full-batch problem -- but run under
+    // the second-half predicate (common.h): their blocks for images [B / 2, B) return at once when the plan's device flag is 1.  The first of them
+    // is preceded by the probe that writes the flag (bitwise comparison of the halves of sample and of the time-embedding projection rows, which
+    // covers per-image timesteps and added conditions), the last one is followed by the broadcast of the boundary tensors: every tensor allocated
+    // inside the prefix that is still live at its end (residual stream, prescaled q of the first cross-attention, skips) gets its first half copied
+    // onto its second.  Tensors that die inside the prefix keep a stale second half nobody reads.  Nothing is decided on the host: the flag is
+    // re-evaluated by every forward and every graph replay.
+    bool pfx_on = false;
+    size_t pfx_first = 0;                                       // first op of the prefix
+    std::map<size_t, size_t> pfx_live;                          // workspace offset -> bytes of every tensor allocated inside the prefix and not released yet
+    std::shared_ptr<size_t> pfx_flag;                           // workspace offset of the flag: known when the arena's peak is (build())
+    size_t pfx_sample_half = 0, pfx_tproj_half = 0;
+    void begin_prefix(size_t sample_half_bytes, size_t tproj_half_bytes) {
+        pfx_on = true;
+        pfx_first = pl.ops.size();
+        pfx_live.clear();
+        pfx_flag = std::make_shared<size_t>(0);
+        pfx_sample_half = sample_half_bytes; pfx_tproj_half = tproj_half_bytes;
+    }
+    void end_prefix() {
+        if (!pfx_on) return;
+        pfx_on = false;
+        const size_t first = pfx_first, end = pl.ops.size();
+        if (end == first) return;
+        std::vector<std::pair<Ref, size_t>> bt;                 // boundary tensors: (tensor, bytes of one half)
+        for (auto& kv : pfx_live) {
+            if (kv.second % 32 != 0 && u.err.empty()) u.err = "cfg prefix: a boundary tensor does not split into 16-byte aligned halves";
+            Ref r; r.kind = Ref::WS; r.off = kv.first;
+            bt.push_back({r, kv.second / 2});
+        }
+        pfx_live.clear();
+        pl.cfg_prefix = true;
+        const std::shared_ptr<size_t> fo = pfx_flag;
+        const Ref tp = tproj;
+        const size_t sh = pfx_sample_half, th = pfx_tproj_half;
+        for (size_t i = first; i < end; ++i) {
+            const std::function<int(const Run&)> inner = std::move(pl.ops[i].fn);
+            const bool is_first = i == first, is_last = i + 1 == end;
+            pl.ops[i].fn = [=](const Run& r) -> int {
+                int* flag = reinterpret_cast<int*>(r.ws + *fo);
+                if (is_first) {
+                    const size_t units = (sh > th ? sh : th) / 16 + 1;
+                    k_cfg_probe_init<<<1, 1, 0, r.stream>>>(flag);
+                    k_cfg_probe<<<units > 64 * 256 ? 64u : mve_cdiv(units, 256), 256, 0, r.stream>>>((const unsigned char*)r.sample, sh, (const unsigned char*)r.p(tp), th, flag);
+                    MVE_LAUNCH_CHECK();
+                }
+                int rc;
+                { MveSkipScope scope(flag); rc = inner(r); }
+                if (rc || !is_last) return rc;
+                for (size_t j = 0; j < bt.size(); j += CFG_BCAST_MAX) {
+                    CfgBcast cb;
+                    memset(&cb, 0, sizeof(cb));
+                    const size_t n = bt.size() - j < (size_t)CFG_BCAST_MAX ? bt.size() - j : (size_t)CFG_BCAST_MAX;
+                    size_t most = 0;
+                    for (size_t k = 0; k < n; ++k) {
+                        cb.p[k] = (unsigned char*)r.p(bt[j + k].first); cb.half[k] = bt[j + k].second;
+                        most = bt[j + k].second > most ? bt[j + k].second : most;
+                    }
+                    const unsigned gx = most / 16 > 2048ull * 256 ? 2048u : mve_cdiv(most / 16 + 1, 256);
+                    k_cfg_broadcast<<<dim3(gx, (unsigned)n), 256, 0, r.stream>>>(cb, flag);
+                    MVE_LAUNCH_CHECK();
+                }
+                return (int)MVE_OK;
+            };
+        }
     }
 
     int rows_img = 0;        // rows per image of the level being emitted (split-K granularity); 0: never split
@@ -329,6 +446,7 @@ struct Builder {
             Ref q = ws((size_t)M * C * e);
             gemm(n2, C, wt(b + ".q2.w"), C, q, C, M, C, C, Ref(), Ref(), 0, 0, Ref(), 0, 0, "attn2.to_q");
             rel(n2);
+            end_prefix();          // the first cross-attention: from here on the halves of the batch differ
             Ref a2 = ws((size_t)M * C * e);
             const size_t ko = (size_t)u.kv_off[b] * e;
             attn(prescaled(q, b + ".q2.w", hd), C, at(ctxkv, ko), ld_kv, at(ctxkv, ko + (size_t)C * e), ld_kv, a2, C, nb, L, Lt, heads, hd);

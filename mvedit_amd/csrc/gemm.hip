@@ -86,7 +86,7 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, unsigned char* sm
     const int tiles_m = (p.M + BM - 1) / BM;
     // split-K: the K slices of one output tile are adjacent logical blocks (same XCD, concurrently resident)
     const int S = p.splitk > 1 ? p.splitk : 1;
-    const unsigned lin = mve_xcd_remap(blockIdx.x, (unsigned)(tiles_m * tiles_n * S));
+    const unsigned lin = gemm_block_lin(p, (unsigned)(tiles_m * tiles_n * S), tiles_n, S, BM);
     int kslice, tm, tn;
     if (p.w_major) {          // weight strip major (GemmParams::w_major): the row panels of one (column tile, K slice) strip are consecutive blocks
         tm = (int)(lin % (unsigned)tiles_m);
@@ -99,6 +99,7 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, unsigned char* sm
         tm = tile / tiles_n; tn = tile % tiles_n;
     }
     const int m0 = tm * BM, n0 = tn * BN;
+    if (mve_second_half_skipped(p.skip_if, m0 >= p.skip_from)) return;      // (all K slices of a tile share m0: nobody waits for a block that left)
 
     // ---- per-thread load coordinates ------------------------------------------------------
     const int lr = tid >> 3;           // row within a 32-row pass
@@ -432,6 +433,7 @@ __global__ __launch_bounds__(256) void k_splitk_reduce(const GemmParams p) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (size_t)p.M * chunks_n) return;
     const int m = (int)(i / chunks_n), n = (int)(i - (size_t)m * chunks_n) * 8;
+    if (p.skip_if && m >= p.skip_from && *p.skip_if != 0) return;      // second-half predicate (rows, not tiles: a straddling tile's rows past the middle are not needed either)
     float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int s = 0; s < p.splitk; ++s) {        // fixed order: deterministic
         const float* pp = p.partial + ((size_t)s * p.M + m) * p.N + n;
@@ -1009,6 +1011,10 @@ static int gemm_pair_impl(int dtype, const void* A, int lda, const void* W, int 
     if (rc) return rc;
     MVE_CHECK(A && lda % 8 == 0 && lda >= K, MVE_ERR_ARG, "gemm: bad A/lda (%d)", lda);
     p.w_major = gemm_w_major_on() && M < N;       // fewer activation rows than weight rows: walk the row panels inside a weight strip (GemmParams::w_major)
+    if (const int* skip = mve_skip_second_half()) {
+        MVE_CHECK(M % 2 == 0, MVE_ERR_ARG, "gemm: the second-half predicate needs an even number of rows (M=%d)", M);
+        p.skip_if = skip; p.skip_from = M / 2; p.w_major = 0;
+    }
     p.splitk = 1;
     if (workspace && !(flags & MVE_GEMM_NO_SPLITK)) {
         const int sk = choose_splitk(rows_per_image, N, K);
@@ -1065,6 +1071,10 @@ static int conv3x3_impl(int dtype, const void* x1, int C1, const void* x2, int C
     int rc = check_common(p, "conv3x3");
     if (rc) return rc;
     p.w_major = gemm_w_major_on() && (long long)p.M * (C1 + C2) < (long long)p.N * p.K;      // activation tensor smaller than the weights (GemmParams::w_major)
+    if (const int* skip = mve_skip_second_half()) {
+        MVE_CHECK(B % 2 == 0, MVE_ERR_ARG, "conv3x3: the second-half predicate needs an even batch (B=%d)", B);
+        p.skip_if = skip; p.skip_from = p.M / 2; p.w_major = 0;
+    }
     p.splitk = 1;
     if (workspace && !(flags & MVE_GEMM_NO_SPLITK)) {
         const int sk = choose_splitk(p.g.Ho * p.g.Wo, p.N, p.K);

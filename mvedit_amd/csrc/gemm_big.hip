@@ -43,11 +43,12 @@ __global__ __launch_bounds__(NTH, 2) void k_gemm_big(const GemmParams p) {
     const int tiles_n = (p.N + BN2 - 1) / BN2;
     const int tiles_m = (p.M + BM2 - 1) / BM2;
     const int S = p.splitk > 1 ? p.splitk : 1;
-    const unsigned lin = mve_xcd_remap(blockIdx.x, (unsigned)(tiles_m * tiles_n * S));
+    const unsigned lin = gemm_block_lin(p, (unsigned)(tiles_m * tiles_n * S), tiles_n, S, BM2);
     const int kslice = lin % S;
     const unsigned tile = lin / S;
     const int tm = tile / tiles_n, tn = tile % tiles_n;
     const int m0 = tm * BM2, n0 = tn * BN2;
+    if (mve_second_half_skipped(p.skip_if, m0 >= p.skip_from)) return;
 
     const int lr = tid >> 3;                                   // 0..63
     const int lc = (tid & 7) ^ ((lr >> 1) & 7);                // source chunk: swizzle applied on the global side

@@ -246,7 +246,7 @@ __global__ __launch_bounds__(PNTH, NSL == 3 ? 4 : 2) void k_gemm_pp(const GemmPa
     const int tiles_n = (p.N + BN2 - 1) / BN2;
     const int tiles_m = (p.M + PBM - 1) / PBM;
     const int S = p.splitk > 1 ? p.splitk : 1;
-    const unsigned lin = mve_xcd_remap(blockIdx.x, (unsigned)(tiles_m * tiles_n * S));
+    const unsigned lin = gemm_block_lin(p, (unsigned)(tiles_m * tiles_n * S), tiles_n, S, PBM);
     int kslice, tm, tn;
     if (p.w_major) {          // weight strip major (GemmParams::w_major): the row panels of one (column tile, K slice) strip are consecutive blocks
         tm = __builtin_amdgcn_readfirstlane((int)(lin % (unsigned)tiles_m));
@@ -260,6 +260,7 @@ __global__ __launch_bounds__(PNTH, NSL == 3 ? 4 : 2) void k_gemm_pp(const GemmPa
     }
     const unsigned tile = (unsigned)(tm * tiles_n + tn);
     const int m0 = tm * PBM, n0 = tn * BN2;
+    if (__builtin_expect(mve_second_half_skipped(p.skip_if, m0 >= p.skip_from), 0)) return;      // second-half predicate: before any M0, LDS or loop state exists
 
     const int nk_all = p.K / BK;
     // (the 64-bit divisions are expanded on the VALU: readfirstlane returns the results to SGPRs)

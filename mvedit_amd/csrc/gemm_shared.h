@@ -92,8 +92,20 @@ struct GemmParams {
     const float* ln_beta;
     float ln_eps;
     int ld_ln;
+    // Second-half predicate (common.h; the executor's CFG prefix): non-null -> a block whose rows all lie in [skip_from, M) returns at once when
+    // *skip_if != 0.  skip_from = M / 2, an image boundary.  The launch is the full problem's in every other respect; the entries clear w_major for it
+    // (the row-panel-major order keeps the first half's tiles in one run of block ids, see gemm_block_lin).
+    const int* skip_if;
+    int skip_from;
     ConvGeom g;
 };
+
+// logical block id of a launch of BMT-row tiles: the XCD remap, in two pieces under the second-half predicate
+__device__ __forceinline__ unsigned gemm_block_lin(const GemmParams& p, unsigned nblk, int tiles_n, int S, int BMT) {
+    if (!p.skip_if) return mve_xcd_remap(blockIdx.x, nblk);
+    const unsigned n1 = (unsigned)((p.skip_from + BMT - 1) / BMT) * (unsigned)(tiles_n * S);
+    return mve_xcd_remap_halves(blockIdx.x, nblk, n1 < nblk ? n1 : nblk);
+}
 
 __device__ __forceinline__ int swz(int row, int chunk) { return row * ROW_BYTES + ((chunk ^ ((row >> 1) & 7)) << 4); }
 

@@ -33,6 +33,7 @@ struct GNSrc {
     int C1, C2;       // channels of each source (C2 may be 0)
     int HW, B;
     const void* x1_lo; const void* x2_lo;      // residual_pair mode: 8-bit low halves of the sources (lo8, common.h: the value is hi + lo), or null
+    const int* skip_if;                        // second-half predicate (common.h): non-null -> blocks of images [B / 2, B) return at once when *skip_if != 0
 };
 
 // chunk index (over the concatenated channel axis) -> source pointer for row r of image b
@@ -73,6 +74,7 @@ __global__ __launch_bounds__(GN_THREADS) void k_gn_partial(GNSrc s, int nsplit, 
     const int C = s.C1 + s.C2;
     const int chunk = blockIdx.y * GN_TX + threadIdx.x;
     const int b = blockIdx.z, split = blockIdx.x;
+    if (mve_second_half_skipped(s.skip_if, 2 * b >= s.B)) return;
     const int rows_per = (s.HW + nsplit - 1) / nsplit;
     const int r0 = split * rows_per, r1 = min(s.HW, r0 + rows_per);
     float sum[8], sq[8];
@@ -116,10 +118,11 @@ __global__ __launch_bounds__(GN_THREADS) void k_gn_partial(GNSrc s, int nsplit, 
 }
 
 __global__ void k_gn_finalize(const float* __restrict__ partial, int B, int nsplit, int C, int G, int HW, float eps,
-                              float* __restrict__ stats /* [B][G][2] mean, rstd */) {
+                              float* __restrict__ stats /* [B][G][2] mean, rstd */, const int* __restrict__ skip_if) {
     // one wave per (b, group): lanes stride over the nsplit*cpg partials, fixed-order xor-tree merge in fp64
     const int i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (i >= B * G) return;
+    if (mve_second_half_skipped(skip_if, 2 * (i / G) >= B)) return;
     const int lane = threadIdx.x & 63;
     const int b = i / G, g = i - b * G, cpg = C / G;
     double a = 0.0, q = 0.0;
@@ -153,6 +156,7 @@ __global__ __launch_bounds__(GN_THREADS) void k_gn_apply(GNSrc s, int nsplit, in
     // (round 5) the apply pass walks the tensor in the REVERSE order of the statistics pass: what that pass read last is read first here, while it
     // is still in the Infinity Cache (3-7 % on the level-0 tensors, tools/gn_pair_bench.py; pure index remap: same bits)
     const int b = (int)gridDim.z - 1 - (int)blockIdx.z, split = (int)gridDim.x - 1 - (int)blockIdx.x;
+    if (mve_second_half_skipped(s.skip_if, 2 * b >= s.B)) return;
     const int rows_per = (s.HW + nsplit - 1) / nsplit;
     const int r0 = split * rows_per, r1 = min(s.HW, r0 + rows_per);
     const int cpg = C / G;
@@ -243,6 +247,7 @@ __global__ __launch_bounds__(NT) void k_gn_fused(GNSrc s, int G, int W8, int nch
         b = blockIdx.x / nchunk;
         chunk = blockIdx.x - b * nchunk;
     }
+    if (mve_second_half_skipped(s.skip_if, 2 * b >= s.B)) return;
     const int total = s.HW * W8;
     V8 raw[MAXI];
     // the 8 values of vector `it` (row, c8): the packed 16-bit half, plus its low half when the source is a pair
@@ -372,7 +377,7 @@ int gnf_plan(int HW, int C, int G, int* nt, int* maxi) {
 template <class Tag, int NT, bool PAIR = false>
 int gnf_launch(const GNSrc& s, int G, int W8, int maxi, float eps, const float* gamma, const float* beta, int silu, void* out, hipStream_t st) {
     const int nchunk = (s.C1 + s.C2) / (W8 * 8);
-    const int xcd = (s.B % 8 == 0) ? 1 : 0;
+    const int xcd = (s.B % 8 == 0 && !s.skip_if) ? 1 : 0;      // (the map interleaves the images over the XCDs: under the second-half predicate half of them would idle)
     const unsigned grid = (unsigned)(s.B * nchunk);
     switch (maxi) {
         case 4: k_gn_fused<Tag, NT, 4, PAIR><<<grid, NT, 0, st>>>(s, G, W8, nchunk, xcd, eps, gamma, beta, silu, out); break;
@@ -394,12 +399,13 @@ int gnf_launch(const GNSrc& s, int G, int W8, int maxi, float eps, const float* 
 template <class Tag, int MAXC8, int R>   // MAXC8: chunks per lane
 __global__ __launch_bounds__(256) void k_layernorm(const void* __restrict__ x, int ldx, void* __restrict__ y, int ldy, int M,
                                                    int C, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                   float eps, const void* __restrict__ x_lo) {
+                                                   float eps, const void* __restrict__ x_lo, const int* __restrict__ skip_if) {
     typedef typename Tag::T T;
     typedef typename Tag::V8 V8;
     const int lane = threadIdx.x & 63;
     const int row0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * R;
     if (row0 >= M) return;
+    if (mve_second_half_skipped(skip_if, 2 * row0 >= M)) return;      // second-half predicate (common.h): the wave's rows all lie in [M / 2, M)
     const int nchunk = C / 8;
     V8 raw[R][MAXC8];
     u32x2 rawl[R][MAXC8];                 // residual_pair mode: the 8-bit low halves (lo8, common.h)
@@ -511,7 +517,7 @@ int gn_run(const GNSrc& s, int G, float eps, const float* gamma, const float* be
         else if (tx == 32) k_gn_partial<Tag, 32, true><<<grid, block, 0, st>>>(s, ns, partial);
         else k_gn_partial<Tag, 64, true><<<grid, block, 0, st>>>(s, ns, partial);
         MVE_LAUNCH_CHECK();
-        k_gn_finalize<<<mve_cdiv(s.B * G, 4), 256, 0, st>>>(partial, s.B, ns, C, G, s.HW, eps, stats);
+        k_gn_finalize<<<mve_cdiv(s.B * G, 4), 256, 0, st>>>(partial, s.B, ns, C, G, s.HW, eps, stats, s.skip_if);
         MVE_LAUNCH_CHECK();
         if (tx == 40) k_gn_apply<Tag, 40, true><<<grid, block, 0, st>>>(s, ns, G, stats, gamma, beta, silu, out);
         else if (tx == 16) k_gn_apply<Tag, 16, true><<<grid, block, 0, st>>>(s, ns, G, stats, gamma, beta, silu, out);
@@ -534,7 +540,7 @@ int gn_run(const GNSrc& s, int G, float eps, const float* gamma, const float* be
     else if (tx == 32) k_gn_partial<Tag, 32><<<grid, block, 0, st>>>(s, ns, partial);
     else k_gn_partial<Tag, 64><<<grid, block, 0, st>>>(s, ns, partial);
     MVE_LAUNCH_CHECK();
-    k_gn_finalize<<<mve_cdiv(s.B * G, 4), 256, 0, st>>>(partial, s.B, ns, C, G, s.HW, eps, stats);
+    k_gn_finalize<<<mve_cdiv(s.B * G, 4), 256, 0, st>>>(partial, s.B, ns, C, G, s.HW, eps, stats, s.skip_if);
     MVE_LAUNCH_CHECK();
     if (tx == 40) k_gn_apply<Tag, 40><<<grid, block, 0, st>>>(s, ns, G, stats, gamma, beta, silu, out);
     else if (tx == 16) k_gn_apply<Tag, 16><<<grid, block, 0, st>>>(s, ns, G, stats, gamma, beta, silu, out);
@@ -547,11 +553,13 @@ int gn_run(const GNSrc& s, int G, float eps, const float* gamma, const float* be
 template <class Tag>
 int ln_run(const void* x, int ldx, void* y, int ldy, int M, int C, const float* gamma, const float* beta, float eps,
            hipStream_t st, const void* x_lo) {
+    const int* skip = mve_skip_second_half();
+    MVE_CHECK(!skip || M % 2 == 0, MVE_ERR_ARG, "layernorm: the second-half predicate needs an even number of rows (M=%d)", M);
     const int per_lane = (C / 8 + 63) / 64;
-    if (per_lane <= 1) k_layernorm<Tag, 1, 4><<<mve_cdiv(M, 16), 256, 0, st>>>(x, ldx, y, ldy, M, C, gamma, beta, eps, x_lo);
-    else if (per_lane == 2) k_layernorm<Tag, 2, 2><<<mve_cdiv(M, 8), 256, 0, st>>>(x, ldx, y, ldy, M, C, gamma, beta, eps, x_lo);
-    else if (per_lane == 3) k_layernorm<Tag, 3, 1><<<mve_cdiv(M, 4), 256, 0, st>>>(x, ldx, y, ldy, M, C, gamma, beta, eps, x_lo);
-    else k_layernorm<Tag, 4, 1><<<mve_cdiv(M, 4), 256, 0, st>>>(x, ldx, y, ldy, M, C, gamma, beta, eps, x_lo);
+    if (per_lane <= 1) k_layernorm<Tag, 1, 4><<<mve_cdiv(M, 16), 256, 0, st>>>(x, ldx, y, ldy, M, C, gamma, beta, eps, x_lo, skip);
+    else if (per_lane == 2) k_layernorm<Tag, 2, 2><<<mve_cdiv(M, 8), 256, 0, st>>>(x, ldx, y, ldy, M, C, gamma, beta, eps, x_lo, skip);
+    else if (per_lane == 3) k_layernorm<Tag, 3, 1><<<mve_cdiv(M, 4), 256, 0, st>>>(x, ldx, y, ldy, M, C, gamma, beta, eps, x_lo, skip);
+    else k_layernorm<Tag, 4, 1><<<mve_cdiv(M, 4), 256, 0, st>>>(x, ldx, y, ldy, M, C, gamma, beta, eps, x_lo, skip);
     MVE_LAUNCH_CHECK();
     return MVE_OK;
 }
@@ -590,6 +598,8 @@ int mve_groupnorm_silu_pair(int dtype, const void* x1, int C1, const void* x2, i
     GNSrc s;
     s.x1 = x1; s.x2 = x2; s.C1 = C1; s.C2 = C2; s.HW = HW; s.B = B;
     s.x1_lo = x1_lo; s.x2_lo = C2 ? x2_lo : nullptr;
+    s.skip_if = mve_skip_second_half();
+    MVE_CHECK(!s.skip_if || B % 2 == 0, MVE_ERR_ARG, "groupnorm: the second-half predicate needs an even batch (B=%d)", B);
     if (dtype == MVE_F16) return gn_run<F16Tag>(s, G, eps, gamma, beta, silu, out, (float*)workspace, (hipStream_t)stream);
     if (dtype == MVE_BF16) return gn_run<BF16Tag>(s, G, eps, gamma, beta, silu, out, (float*)workspace, (hipStream_t)stream);
     mve_set_error("groupnorm: unsupported dtype %d", dtype);

@@ -457,6 +457,8 @@ int mve_unet_forward(void* handle, int phase, const void* d_sample, int io_dtype
     if (phase != 2) {      // unet_dec reuses the emb of its unet_enc state
         rc = take_added_cond(*u, B, r, "unet_forward");
         if (rc) return rc;
+        u->cfg_flag = pl.cfg_prefix ? reinterpret_cast<const int*>(r.ws + pl.cfg_flag_off) : nullptr;
+        u->cfg_stream = r.stream;
     }
     const size_t lo = phase == 2 ? pl.enc_end : 0, hi = phase == 1 ? pl.enc_end : pl.ops.size();
     if (u->graph_mode && !op_ms) {
@@ -552,6 +554,25 @@ int mve_unet_set_residual_mode(void* handle, int pair) {
     const int old = u->ao.residual_pair;
     if (pair >= 0) u->ao.residual_pair = pair ? 1 : 0;     // part of the plan key: plans of either mode stay cached side by side
     return old;
+}
+
+int mve_unet_tune_cfg_prefix(void* handle, int on) {
+    MVE_CHECK(handle, MVE_ERR_ARG, "unet_tune_cfg_prefix: null handle");
+    Unet* u = (Unet*)handle;
+    MVE_CHECK(!u->cfg.controlnet && !u->cfg.vae && !u->cfg.sr && !u->cfg.lpips, MVE_ERR_ARG, "unet_tune_cfg_prefix: a UNet handle is needed");
+    const int old = u->ao.cfg_prefix;
+    if (on >= 0) u->ao.cfg_prefix = on ? 1 : 0;            // part of the plan key, like the residual mode
+    return old;
+}
+
+int mve_unet_cfg_prefix_state(void* handle) {
+    MVE_CHECK(handle, MVE_ERR_STATE, "unet_cfg_prefix_state: null handle");      // (-1 means "not planned")
+    Unet* u = (Unet*)handle;
+    if (!u->cfg_flag) return -1;
+    int v = 0;
+    MVE_HIP(hipStreamSynchronize(u->cfg_stream));
+    MVE_HIP(hipMemcpy(&v, u->cfg_flag, sizeof(int), hipMemcpyDeviceToHost));
+    return v != 0 ? 1 : 0;
 }
 
 int mve_unet_set_addition_embed(void* handle, int addition_type, int addition_time_embed_dim, int projection_input_dim) {

@@ -164,6 +164,24 @@ class UNet2DConditionEngine:
     def residual_pair(self):
         return bool(_lib.raw('mve_unet_set_residual_mode')(self._h, -1))
 
+    def set_cfg_prefix(self, flag=True):
+        """Run the ops in front of the first cross-attention once for both halves of a classifier-free-guidance batch whenever a device-side probe
+        finds the halves of `sample` and of the time embedding identical (mve_unet_tune_cfg_prefix; ON by default, bit-identical output either
+        way, part of the plan key).  Returns the previous setting."""
+        return bool(_lib.raw('mve_unet_tune_cfg_prefix')(self._h, int(bool(flag))))
+
+    @property
+    def cfg_prefix(self):
+        return bool(_lib.raw('mve_unet_tune_cfg_prefix')(self._h, -1))
+
+    def cfg_prefix_state(self):
+        """Tests / tools: 1 when the last forward found its halves identical and ran the prefix once, 0 when they differed, -1 when its plan had
+        no prefix (odd batch, reference attention, cross-image groups across the middle).  Synchronises."""
+        rc = int(_lib.raw('mve_unet_cfg_prefix_state')(self._h))
+        if rc < -1:
+            raise RuntimeError('mve_unet_cfg_prefix_state: ' + _lib.last_error())
+        return rc
+
     def enable_graph(self, flag=True):
         """Opt-in hipGraph replay of forwards whose plan and tensors (addresses) repeat -- for launch-bound small batches (mve_unet_graph)."""
         return bool(_lib.raw('mve_unet_graph')(self._h, int(bool(flag))))
