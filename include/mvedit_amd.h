@@ -575,6 +575,14 @@ MVE_API int mve_controlnet_create(void** handle, int dtype, int in_channels, int
  * both.  Bit-identical to passing the images R times.  Part of the plan key; returns the previous value (repeat < 1: query).  Not combined with the
  * residual-pair mode. */
 MVE_API int mve_controlnet_set_cond_repeat(void* handle, int repeat);
+/* Context tail of a UNet / ControlNet handle (CNAttnProcessor / CNAttnProcessor2_0, lib/models/architecture/ip_adapter/attention_processor.py:400-480:
+ * `encoder_hidden_states[:, :end_pos]` with end_pos = L - num_tokens).  Under an IP-Adapter the context is [text rows | image tokens] and the
+ * reference's ControlNets cross-attend to the text rows alone.  With rows = n > 0 every later plan / forward of the handle ignores the last n rows
+ * of every item's d_ctx: the cross-attention K/V GEMM reads the first ctx_len - n rows of each item (one strided device copy inside the plan, no
+ * caller-side copy), bit-identical to passing those rows as a dense [B, ctx_len - n, D] context.  n >= ctx_len is MVE_ERR_ARG at plan time, as is
+ * the combination with ip_tokens > 0 (mve_unet_set_attention).  Part of the plan key, and with it of the hipGraph key.  Returns the previous
+ * value (rows < 0: query). */
+MVE_API int mve_unet_set_context_tail(void* handle, int rows);
 MVE_API int mve_controlnet_forward(void* handle, const void* d_sample, int io_dtype, const float* d_timesteps, const void* d_ctx,
                                    const void* d_cond, int B, int H, int W, int ctx_len, float conditioning_scale, int accumulate,
                                    void* const* d_outputs, void* d_workspace, size_t workspace_bytes,

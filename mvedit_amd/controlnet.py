@@ -15,6 +15,7 @@ import ctypes
 import torch
 
 from . import _lib
+from .attn_processors import controlnet_attn_processor_names
 from .ops import dt as _dt
 from .unet import UNet2DConditionEngine
 
@@ -43,6 +44,17 @@ class ControlNetEngine(UNet2DConditionEngine):
         self._ip = (0, 1.0)
         self._ref_keep = None
 
+    _attn_is_controlnet = True
+
+    def _attn_names(self):
+        return controlnet_attn_processor_names(self.cfg)
+
+    def _bind_context_tail(self):
+        """CNAttnProcessor(num_tokens) of an installed table: the executor ignores that many trailing context rows (mve_unet_set_context_tail,
+        mirroring the number the object carries).  Without a governing table nothing is touched."""
+        if self._attn_governs:
+            _lib.call('mve_unet_set_context_tail', self._h, self._attn_resolve().cn_tokens)
+
     def output_shapes(self, B, H, W):
         ch = self.cfg['block_out_channels']
         shapes = [(ch[0], H, W)]
@@ -64,6 +76,7 @@ class ControlNetEngine(UNet2DConditionEngine):
 
     def run(self, sample, timestep, encoder_hidden_states, cond, scale, down, mid, accumulate, profile=False, added_cond_kwargs=None):
         B, _, H, W = sample.shape
+        self._bind_context_tail()
         self._bind_added_cond(added_cond_kwargs, B)
         io = encoder_hidden_states.dtype
         ctx = encoder_hidden_states.to(self.device).contiguous()
@@ -111,6 +124,28 @@ class MultiControlNetEngine:
 
     def __init__(self, nets):
         self.nets = list(nets)
+
+    # the diffusers module surface the reference touches on `pipe.controlnet` (ip_adapter.py:105-110 takes the single-net branch here, because
+    # its isinstance(..., MultiControlNetModel) is false for this class; lib/apis/adapter3d.py:307-313, :328-330)
+    def set_attn_processor(self, processor):
+        for net in self.nets:
+            net.set_attn_processor(processor)
+
+    def set_use_memory_efficient_attention_xformers(self, valid, attention_op=None):
+        for net in self.nets:
+            net.set_use_memory_efficient_attention_xformers(valid, attention_op)
+
+    def parameters(self):
+        for net in self.nets:
+            yield from net.parameters()
+
+    @property
+    def dtype(self):
+        return self.nets[0].dtype
+
+    @property
+    def device(self):
+        return self.nets[0].device
 
     def __call__(self, sample, timestep, encoder_hidden_states, controlnet_cond, conditioning_scale, guess_mode=False,
                  added_cond_kwargs=None, return_dict=False, **unused):

@@ -96,7 +96,9 @@ int Builder::build(int B_, int H, int W, int n_img, int has_res, int io_dtype, i
         }
     }
     const AttnOpts ao = pl.ao;
-    Lt = Lc - ao.ip_tokens;
+    MVE_CHECK(ao.ctx_tail >= 0 && ao.ctx_tail < Lc, MVE_ERR_ARG, "unet: cannot ignore the last %d rows of a context of %d rows", ao.ctx_tail, Lc);
+    MVE_CHECK(!ao.ctx_tail || !ao.ip_tokens, MVE_ERR_ARG, "unet: an ignored context tail (%d rows) is not combined with ip tokens", ao.ctx_tail);
+    Lt = Lc - ao.ip_tokens - ao.ctx_tail;
     H0 = H;
     ref_off = 0;
     if (ao.ip_tokens > 0) {
@@ -112,6 +114,12 @@ int Builder::build(int B_, int H, int W, int n_img, int has_res, int io_dtype, i
         gemm(ctx_ip, c.ctx_dim, wt("ip_kv.w"), c.ctx_dim, ipkv, ld_kv, ctxB * ao.ip_tokens, ld_kv, c.ctx_dim, Ref(), Ref(), 0, 0, Ref(), 0, 0,
              "ip-adapter K,V (all layers, one GEMM)");
         rel(ctx_ip);
+        ctx_in = ctx_text;
+    } else if (ao.ctx_tail > 0) {
+        // the first Lt rows of every item, densely: the K/V GEMM below then never sees the tail (attention_processor.py:519-520)
+        const size_t rowb = (size_t)c.ctx_dim * e;
+        Ref ctx_text = ws((size_t)ctxB * Lt * rowb);
+        copy2d(ctx_text, Lt * rowb, ctx_in, Lc * rowb, Lt * rowb, ctxB, "ctx rows without the tail");
         ctx_in = ctx_text;
     }
     if (ao.ref_mode) {

@@ -198,6 +198,9 @@ struct Op {
 //   cn_cond_repeat: ControlNet plans only (mve_controlnet_set_cond_repeat): the conditioning images are given for B / R items and item b uses image
 //                   b mod (B / R) -- under classifier-free guidance both halves of the batch see the same control images
 //                   (mvedit_3d_pipeline.py:1232: `ctrl_images.split(diff_bs) * 2`), so the conditioning embedding runs once, not R times.
+//   ctx_tail      : mve_unet_set_context_tail: the last ctx_tail rows of every item's encoder_hidden_states are ignored -- CNAttnProcessor2_0
+//                   (lib/models/architecture/ip_adapter/attention_processor.py:472-480) on a ControlNet under an IP-Adapter, whose context carries
+//                   image tokens the ControlNet must not attend to.  Not combined with ip_tokens.
 //   cfg_prefix    : UNet plans only (mve_unet_tune_cfg_prefix, default on): the ops in front of the first cross-attention run for the first half of
 //                   the batch alone whenever a device-side probe finds the two halves of sample and time embedding identical (builder_unet.h).
 struct AttnOpts {
@@ -206,9 +209,10 @@ struct AttnOpts {
     int residual_pair = 0;
     int cn_cond_repeat = 1;
     int cfg_prefix = 1;
+    int ctx_tail = 0;
     bool operator==(const AttnOpts& o) const {
         return ip_tokens == o.ip_tokens && ip_scale == o.ip_scale && ref_mode == o.ref_mode && ref_H == o.ref_H && ref_W == o.ref_W &&
-               ref_skip == o.ref_skip && residual_pair == o.residual_pair && cn_cond_repeat == o.cn_cond_repeat && cfg_prefix == o.cfg_prefix;
+               ref_skip == o.ref_skip && residual_pair == o.residual_pair && cn_cond_repeat == o.cn_cond_repeat && cfg_prefix == o.cfg_prefix && ctx_tail == o.ctx_tail;
     }
 };
 

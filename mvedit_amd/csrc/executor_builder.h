@@ -58,7 +58,7 @@ struct Builder {
     int ld_temb, ld_kv;
     Ref tproj, ctxkv, ipkv;  // hoisted projections
     int ctx_rows_per_img = 0, ctxB = 0;
-    int Lt = 0;              // text rows of the context (ctx_rows_per_img - ip_tokens)
+    int Lt = 0;              // text rows of the context (ctx_rows_per_img - ip_tokens - ctx_tail)
     int H0 = 0;              // latent height of this pass (reference-store geometry)
     size_t ref_off = 0;      // running offset into the reference K/V store
 

@@ -618,6 +618,15 @@ int mve_controlnet_set_cond_repeat(void* handle, int repeat) {
     return old;
 }
 
+int mve_unet_set_context_tail(void* handle, int rows) {
+    MVE_CHECK(handle, MVE_ERR_ARG, "unet_set_context_tail: null handle");
+    Unet* u = (Unet*)handle;
+    MVE_CHECK(!u->cfg.vae && !u->cfg.sr && !u->cfg.lpips, MVE_ERR_ARG, "unet_set_context_tail: a UNet / ControlNet handle is needed");
+    const int old = u->ao.ctx_tail;
+    if (rows >= 0) u->ao.ctx_tail = rows;                  // part of the plan key (and through the plan's uid of the graph key)
+    return old;
+}
+
 size_t mve_unet_ref_store_bytes(void* handle, int B, int ref_H, int ref_W, int ref_skip) {
     if (!handle || B <= ref_skip) return 0;
     const Config& c = ((Unet*)handle)->cfg;

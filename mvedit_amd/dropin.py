@@ -16,7 +16,15 @@ What `install()` rebinds -- the operator seams of SURVEY.md section 8(b), nothin
      constructor has registered the loaded torch modules (lib/apis/adapter3d.py:971-975), `pipe.unet`, `pipe.controlnet`, `pipe.vae`,
      `pipe.image_enhancer`, `pipe.segmentation` and `pipe.mesh_renderer` are replaced by engines built from those modules' own configs and
      state dicts, and `pipe.nerf.render` by the native renderer.  Engines are cached on the source module (`Adapter3DRunner` builds a pipeline
-     object per request from the same loaded modules), and rebuilt when the module's parameters have been replaced.
+     object per request from the same loaded modules), and rebuilt when the module's parameters have been replaced or moved.  A UNet / ControlNet
+     engine keeps its source module and treats that module's attention-processor table as the single source of truth: `attn_processors` /
+     `set_attn_processor` delegate to the module and every forward translates the module's current table (mvedit_amd/attn_processors.py), so
+     the runner's `unload_ip_adapter` (lib/apis/adapter3d.py:325-336), which talks to the modules and not to `pipe.unet`, reaches the engines.
+     `Zero123PlusPipeline` is the exception: `from_pretrained` constructs it on the CPU and `prepare()` (zero123plus.py:316-319) wraps the UNet
+     only while it still is a `UNet2DConditionModel`, so nothing is swapped at `__init__`; when `prepare()` returns with the parameters on an
+     accelerator, the inner `.unet` of `RefOnlyNoisedUNet` (and the `.controlnet` of a `DepthControlUNet`) and `pipe.vae` are replaced, past
+     `nn.Module.__setattr__` -- the wrappers keep their own `forward`, whose `mode` / `ref_dict` / `is_cfg_guidance` kwargs the engine
+     understands, and the `ReferenceOnlyAttnProc` table `RefOnlyNoisedUNet.__init__` installed on the module is what the engine translates.
   4. `tinycudann` (CUDA-only, imported by lib/models/decoders/ingp_decoder.py:5-8 and triplane_ingp_decoder.py:5-8): seeded in `sys.modules`
      with `Encoding` bound to `mvedit_amd.tinycudann.Encoding`, so the reference's decoders construct and train unchanged.  Decoder
      modules imported before `install()` (their `tcnn` is None after the failed import) get `tcnn` rebound.
@@ -46,7 +54,9 @@ PIPELINE_CLASSES = {'lib.pipelines.mvedit_3d_pipeline': 'MVEdit3DPipeline',
                     'lib.pipelines.zero123plus': 'Zero123PlusPipeline'}
 SWAPPED_ATTRS = ('unet', 'controlnet', 'vae', 'image_enhancer', 'segmentation', 'mesh_renderer')
 
-_state = dict(installed=False, finder=None, undo=[], seeded=[])
+ZERO123_WRAPPERS = ('RefOnlyNoisedUNet', 'DepthControlUNet')          # lib/pipelines/zero123plus.py:80, :178 (recognised by class name)
+
+_state = dict(installed=False, finder=None, undo=[], seeded=[], instances=[])
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -55,13 +65,31 @@ _state = dict(installed=False, finder=None, undo=[], seeded=[])
 def _module_dtype_device(m):
     import torch
     p = next(iter(m.parameters()))
+    if p.device.type == 'cpu':
+        raise RuntimeError(f'{type(m).__name__}: its parameters are on the CPU -- an engine is built from weights that sit on the accelerator '
+                           f'(move the module first; Zero123PlusPipeline is swapped at prepare() for this reason)')
     dtype = p.dtype if p.dtype in (torch.float16, torch.bfloat16) else torch.float16
     return dtype, p.device
 
 
 def _fingerprint(m):
-    """Identity of a module's parameter storage: a reloaded / re-typed module gets a new engine."""
-    return tuple((k, v.data_ptr(), v._version) for k, v in list(m.state_dict().items())[:4])
+    """Identity of a module's parameter storage: a reloaded / re-typed / moved module gets a new engine."""
+    return tuple((k, v.data_ptr(), v._version, str(v.device)) for k, v in list(m.state_dict().items())[:4])
+
+
+def _on_accelerator(m):
+    p = next(iter(m.parameters()), None)
+    return p is not None and p.device.type != 'cpu'
+
+
+def _follow_module_table(eng, module):
+    """The module's attention-processor table becomes the engine's (AttnProcessorTable._attn_source); MultiControlNetModel: net by net."""
+    nets = getattr(eng, 'nets', None)
+    if nets is not None and hasattr(module, 'nets'):
+        for e, n in zip(nets, module.nets):
+            _follow_module_table(e, n)
+    elif hasattr(eng, '_attn_resolve') and hasattr(module, 'attn_processors') and hasattr(module, 'set_attn_processor'):
+        eng._attn_source = module
 
 
 def make_unet(m):
@@ -136,6 +164,8 @@ def engine_for(kind, module):
     if cached is not None and cached[0] == fp:
         return cached[1]
     eng = MAKERS[kind](module)
+    if kind in ('unet', 'controlnet'):
+        _follow_module_table(eng, module)
     try:
         object.__setattr__(eng, '_mve_is_engine', True)
     except (AttributeError, TypeError):
@@ -169,6 +199,32 @@ def swap_engines(pipe):
     if nerf is not None and not getattr(nerf, '_mve_render_bound', False):
         object.__setattr__(nerf, 'render', _native_nerf_render(nerf))
         object.__setattr__(nerf, '_mve_render_bound', True)
+    return pipe
+
+
+def _set_instance(obj, name, value):
+    """Instance attribute past nn.Module.__setattr__ (the torch module stays registered in `_modules`, so `.to()` / `state_dict()` of a wrapper
+    still see it); remembered for uninstall()."""
+    if obj.__dict__.get(name) is value:
+        return
+    _state['instances'].append((obj, name, name in obj.__dict__, obj.__dict__.get(name)))
+    object.__setattr__(obj, name, value)
+
+
+def swap_zero123(pipe):
+    """After `Zero123PlusPipeline.prepare()`: idempotent; members whose parameters are still on the CPU are left for the next call."""
+    vae = getattr(pipe, 'vae', None)
+    if vae is not None and not getattr(vae, '_mve_is_engine', False) and _on_accelerator(vae):
+        _set_instance(pipe, 'vae', engine_for('vae', vae))
+    w = getattr(pipe, 'unet', None)
+    while type(w).__name__ in ZERO123_WRAPPERS:
+        for name, kind in (('controlnet', 'controlnet'), ('unet', 'unet')):
+            inner = w.__dict__.get(name) or w.__dict__.get('_modules', {}).get(name)
+            if inner is None or getattr(inner, '_mve_is_engine', False) or type(inner).__name__ in ZERO123_WRAPPERS:
+                continue
+            if _on_accelerator(inner):
+                _set_instance(w, name, engine_for(kind, inner))
+        w = w.__dict__.get('_modules', {}).get('unet') if type(w).__name__ == 'DepthControlUNet' else None
     return pipe
 
 
@@ -208,12 +264,23 @@ def _patch_pipeline(mod):
     if getattr(orig, '_mve_wrapped', False):
         return
 
+    zero123 = cls.__name__ == 'Zero123PlusPipeline'
+
     def __init__(self, *args, **kwargs):
         orig(self, *args, **kwargs)
-        swap_engines(self)
+        if not zero123:              # from_pretrained builds Zero123++ on the CPU and prepare() must still find a UNet2DConditionModel
+            swap_engines(self)
     __init__._mve_wrapped = True
     __init__.__wrapped__ = orig
     _set(cls, '__init__', __init__)
+    prepare = vars(cls).get('prepare')
+    if zero123 and prepare is not None:
+        def prepare_and_swap(self, *args, **kwargs):
+            out = prepare(self, *args, **kwargs)
+            swap_zero123(self)
+            return out
+        prepare_and_swap.__wrapped__ = prepare
+        _set(cls, 'prepare', prepare_and_swap)
 
 
 def _patch_tcnn_decoder(mod):
@@ -316,9 +383,14 @@ def uninstall():
                 delattr(obj, name)
             except AttributeError:
                 pass
+    for obj, name, had, old in reversed(_state['instances']):
+        if had:
+            object.__setattr__(obj, name, old)
+        else:
+            obj.__dict__.pop(name, None)
     for name, old in reversed(_state['seeded']):
         if old is None:
             sys.modules.pop(name, None)
         else:
             sys.modules[name] = old
-    _state.update(installed=False, finder=None, undo=[], seeded=[])
+    _state.update(installed=False, finder=None, undo=[], seeded=[], instances=[])

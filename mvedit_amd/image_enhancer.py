@@ -8,11 +8,12 @@ import torch
 
 from . import _lib
 from .ops import dt as _dt
+from .module_surface import ModuleSurface
 
 OP_CLASSES = ('conv', 'linear', 'attention', 'norm', 'other')
 
 
-class SRVGGNetCompactEngine:
+class SRVGGNetCompactEngine(ModuleSurface):
     def __init__(self, num_in_ch=3, num_out_ch=3, num_feat=64, num_conv=16, upscale=4, act_type='prelu', dtype=torch.float16, device='cuda'):
         assert act_type == 'prelu', 'the pipelines build the PReLU variant (lib/pipelines/utils.py:213)'
         assert dtype in (torch.float16, torch.bfloat16)

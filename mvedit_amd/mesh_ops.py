@@ -443,11 +443,15 @@ class MeshRenderer:
     # ---------------------------------------------------------------------------------------------------------------
     def bake_xyz_shading_fun(self, meshes, shading_fun, map_size=1024, force_auto_uv=False, dilation_iters=7):
         """base_mesh_renderer.py:397-423: evaluate `shading_fun(world_pos=...)` at the surface point behind every texel of the
-        UV atlas and store the result as the albedo map.  (mesh.auto_uv -- xatlas -- is mesh I/O and out of scope: the mesh must
-        carry vt / ft.)"""
+        UV atlas and store the result as the albedo map.  A mesh without vt (or force_auto_uv) is unwrapped by its OWN `auto_uv()` when it has
+        one, as the reference does at :401-402 (the reference's Mesh runs xatlas on the CPU there); UV unwrapping itself is mesh I/O and not part
+        of this engine, so a mesh object without `auto_uv` must carry vt / ft."""
         assert len(meshes) == 1, 'only support one mesh'
         mesh = meshes[0]
-        assert mesh.vt is not None and not force_auto_uv, 'UV unwrapping (mesh.auto_uv) is not part of this engine'
+        if (mesh.vt is None or force_auto_uv) and hasattr(mesh, 'auto_uv'):
+            mesh.auto_uv()
+        else:
+            assert mesh.vt is not None and not force_auto_uv, 'UV unwrapping (mesh.auto_uv) is not part of this engine'
         assert len(mesh.ft) == len(mesh.f)
         vt = mesh.vt.float().contiguous()
         vt_clip = torch.cat([vt * 2 - 1, vt.new_tensor([[0., 1.]]).expand(vt.size(0), -1)], dim=-1)

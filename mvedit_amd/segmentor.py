@@ -14,6 +14,7 @@ import torch
 
 from . import _lib
 from .ops import dt as _dt
+from .module_surface import ModuleSurface
 
 ACT_NONE, ACT_SWISH, ACT_SELU, ACT_RELU, ACT_SIGMOID = 0, 1, 2, 3, 4
 SELU_SCALE = 1.0507009873554805
@@ -61,7 +62,7 @@ class PadHW:
         self.t, self.b, self.l, self.r = t, b, l, r
 
 
-class TracerUniversalB7Engine:
+class TracerUniversalB7Engine(ModuleSurface):
     def __init__(self, input_image_size=640, batch_size=8, torch_dtype='bfloat16', erosion=1, device='cuda', min_chunk=32, pretrained=None,
                  freeze=True):
         # pretrained / freeze: the reference's constructor arguments (tracer_b7.py:16-30; a config built for the reference constructs this class

@@ -17,6 +17,8 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib
+from .attn_processors import AttnProcessorTable, attn_processor_names
+from .module_surface import ModuleSurface
 from .ops import dt as _dt
 
 SD15_CONFIG = dict(
@@ -77,7 +79,7 @@ def config_from_diffusers(cfg):
                 norm_eps=g('norm_eps'), transformer_layers=tl, use_linear_projection=bool(g('use_linear_projection', False)), **extra)
 
 
-class UNet2DConditionEngine:
+class UNet2DConditionEngine(AttnProcessorTable, ModuleSurface):
     def __init__(self, config=None, dtype=torch.float16, device='cuda'):
         self.cfg = dict(config or SD15_CONFIG)
         assert dtype in (torch.float16, torch.bfloat16)
@@ -221,11 +223,36 @@ class UNet2DConditionEngine:
         through load_state_dict under their diffusers names `<block>.attn2.processor.to_{k,v}_ip.weight`."""
         self._ip = (int(num_tokens), float(scale))
 
-    def _set_attention(self, cak, B, H, W):
+    # the diffusers processor table (attn_processors / set_attn_processor: mvedit_amd/attn_processors.py) ------------------------
+    def _attn_names(self):
+        return attn_processor_names(self.cfg)
+
+    def _attn_push(self, name, tensor):
+        """One to_k_ip / to_v_ip weight of an installed IPAttnProcessor into the executor (stream-ordered: no synchronisation)."""
+        t = tensor.detach()
+        if t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            t = t.float()
+        t = t.to(self.device).contiguous()
+        shape = (ctypes.c_longlong * t.dim())(*t.shape)
+        with torch.cuda.device(self.device):
+            _lib.call('mve_unet_load_param', self._h, name.encode(), _lib.ptr(t), _dt(t), t.dim(), shape, _lib.stream_ptr(self.device))
+
+    def _set_attention(self, cak, B, H, W, ctx_len=None):
         """Translate the reference's cross_attention_kwargs (mode / ref_dict / is_cfg_guidance) into engine state.  The
-        reference fills ref_dict with one tensor per attention layer; here ref_dict receives ONE entry, the K/V store."""
+        reference fills ref_dict with one tensor per attention layer; here ref_dict receives ONE entry, the K/V store.
+        Once a processor table governs (set_attn_processor was called, or the engine follows a source module) the IP branch and the
+        right to use reference attention come from the table, resolved here at every forward."""
         cak = cak or {}
         mode, ref_dict = cak.get('mode'), cak.get('ref_dict')
+        ip = self._ip
+        if self._attn_governs:
+            tr = self._attn_resolve()
+            ip = (tr.ip_tokens, tr.ip_scale)
+            if (mode is not None or ref_dict is not None) and not tr.reference:
+                raise ValueError(f'cross_attention_kwargs mode={mode!r} / ref_dict given, but the installed attention processors hold no '
+                                 f'enabled ReferenceOnlyAttnProc / ReferenceAttnProc')
+            if ip[0] and ctx_len is not None and ctx_len <= ip[0]:
+                raise ValueError(f'the installed IP-Adapter processors take the last {ip[0]} rows of encoder_hidden_states, which has {ctx_len}')
         skip = 1 if cak.get('is_cfg_guidance') else 0
         store, ref_mode, rH, rW = None, 0, 0, 0
         if mode is not None and ref_dict is not None:
@@ -241,7 +268,7 @@ class UNet2DConditionEngine:
             else:
                 raise AssertionError(mode)
         self._ref_keep = store
-        _lib.call('mve_unet_set_attention', self._h, self._ip[0], self._ip[1], ref_mode, rH, rW, skip, _lib.ptr(store),
+        _lib.call('mve_unet_set_attention', self._h, ip[0], ip[1], ref_mode, rH, rW, skip, _lib.ptr(store),
                   store.numel() if store is not None else 0)
 
     @property
@@ -324,7 +351,7 @@ class UNet2DConditionEngine:
         """diffusers UNet2DConditionModel.forward signature subset used by the reference."""
         self._bind_added_cond(added_cond_kwargs, sample.shape[0])
         n_img = int((cross_attention_kwargs or {}).get('num_cross_attn_imgs', 1))
-        self._set_attention(cross_attention_kwargs, sample.shape[0], sample.shape[2], sample.shape[3])
+        self._set_attention(cross_attention_kwargs, sample.shape[0], sample.shape[2], sample.shape[3], encoder_hidden_states.shape[1])
         res = self._run(0, sample, timestep, encoder_hidden_states, n_img, down_block_additional_residuals,
                         mid_block_additional_residual, out)
         if return_dict:
@@ -336,7 +363,7 @@ class UNet2DConditionEngine:
     def profile(self, sample, timestep, encoder_hidden_states, num_cross_attn_imgs=1, added_cond_kwargs=None):
         """-> (out, [(class, label, flops, ms)]) with HIP-event timing around every launch."""
         self._bind_added_cond(added_cond_kwargs, sample.shape[0])
-        self._set_attention(None, *[sample.shape[i] for i in (0, 2, 3)])
+        self._set_attention(None, *[sample.shape[i] for i in (0, 2, 3)], encoder_hidden_states.shape[1])
         out, ms = self._run(0, sample, timestep, encoder_hidden_states, num_cross_attn_imgs, None, None, None, profile=True)
         return out, [(c, lab, fl, m) for (ph, c, fl, lab), m in zip(self.op_table(), ms)]
 
@@ -347,7 +374,7 @@ class UNet2DConditionEngine:
         self._bind_added_cond(added_cond_kwargs, sample.shape[0])
         n_img = int((cross_attention_kwargs or {}).get('num_cross_attn_imgs', 1))
         B, _, H, W = sample.shape
-        self._set_attention(cross_attention_kwargs, B, H, W)
+        self._set_attention(cross_attention_kwargs, B, H, W, encoder_hidden_states.shape[1])
         # residual-carrying decode needs the same plan: decided at dec() time, so enc always plans with residual slots
         info = self.plan(B, H, W, encoder_hidden_states.shape[1], n_img, True, encoder_hidden_states.dtype)
         ws = workspace if workspace is not None else torch.empty(info['workspace_bytes'], dtype=torch.uint8, device=self.device)
@@ -357,7 +384,7 @@ class UNet2DConditionEngine:
 
     def dec(self, state, encoder_hidden_states, down_block_additional_residuals=None, mid_block_additional_residual=None,
             cross_attention_kwargs=None):
-        self._set_attention(cross_attention_kwargs, state.shape[0], state.shape[2], state.shape[3])
+        self._set_attention(cross_attention_kwargs, state.shape[0], state.shape[2], state.shape[3], encoder_hidden_states.shape[1])
         return self._enc_dec(2, state, None, encoder_hidden_states, down_block_additional_residuals,
                              mid_block_additional_residual)
 

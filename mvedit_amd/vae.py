@@ -15,6 +15,7 @@ import torch
 
 from . import _lib
 from .ops import dt as _dt
+from .module_surface import ModuleSurface
 
 SD_VAE_CONFIG = dict(in_channels=3, out_channels=3, latent_channels=4, block_out_channels=(128, 256, 512, 512), layers_per_block=2,
                      norm_num_groups=32, scaling_factor=0.18215)
@@ -132,7 +133,7 @@ class _Half:
         return (out, prof) if profile else out
 
 
-class AutoencoderKLEngine:
+class AutoencoderKLEngine(ModuleSurface):
     """`vae` of the reference's pipelines: `.config.scaling_factor`, `.decode(z, return_dict=False)[0]`,
     `.encode(x).latent_dist` / `.encode(x, return_dict=False)[0]`."""
 
