@@ -313,6 +313,38 @@ MVE_API int mve_layernorm_pair(int dtype, const void* d_x, int ldx, void* d_y, i
  * are lo8 bytes; an all-zero addend leaves the pair untouched bit for bit */
 MVE_API int mve_axpy_pair(int dtype, const void* d_a, const void* d_a_lo, const void* d_b, float alpha, void* d_y, void* d_y_lo, size_t n, void* stream);
 
+/* ---- 2b. MXFP8 block-scaled linear (csrc/mxfp8.hip; mvedit_amd/mxfp8.py) ---------------------------------------------------------------------------
+ * An 8-bit matrix path on gfx950's block-scaled MFMA (v_mfma_scale_f32_16x16x128_f8f6f4), the only instruction that reaches the fp8 rate.  A
+ * primitive: no engine uses it yet.  (No reference counterpart: the reference has no fp8)
+ *
+ * Packed format (OCP MX): a [R][K] matrix, K % 32 == 0, is two byte tensors
+ *   q : uint8 [R][Kp], row-major, Kp = 128 * ceil(K / 128) = mve_mxfp8_packed_k(K): OCP e4m3fn bytes (what torch.float8_e4m3fn holds);
+ *   e : uint8 [R][Kp / 32], row-major: E8M0 bytes, byte b = 2^(b - 127);
+ *   element (r, k) = e4m3(q[r][k]) * 2^(e[r][k / 32] - 127).  Columns K .. Kp-1 are padding: q = 0x00, e = 127 (mve_mxfp8_quantize writes it).
+ * Scale rule, per block of 32 consecutive k, on exponents only:
+ *   amax = max |x| over the block in fp32; s = the smallest integer with amax * 2^-s <= 448 (amax = m * 2^ex, 0.5 <= m < 1: s = ex - 9 if
+ *   m <= 0.875, else ex - 8), clamped to [-127, 127]; amax == 0 gives s = 0; e = s + 127;
+ *   q = RNE_e4m3(clamp(x * 2^-s, -448, 448)), the scaling exact (an exponent change).
+ *   This is the CLIPPING-FREE variant of the MX rule: the OCP text takes s = floor(log2 amax) - 8 and saturates the elements that then exceed 448;
+ *   here the block maximum always fits, at the cost of one bit less for blocks with m > 0.875.  Away from the exponent clamp
+ *   |dequantised - x| <= max(2^-4 |x|, 2^-10 * 2^s).
+ * Non-finite inputs are outside the contract.  What the kernel does: NaN -> 0 (as the lo8 packer); +-Inf sets its block's scale to s = 120, its
+ * own element to +-448, and the block's finite elements are scaled by 2^-120.
+ * Host converters with the same bits: mvedit_amd.mxfp8.quantize_host / dequantize_host. */
+MVE_API int mve_mxfp8_packed_k(int K);      /* host only: Kp, or -1 when K is not a positive multiple of 32 */
+/* d_x: [R][ldx] of `dtype` in {MVE_F32, MVE_F16, MVE_BF16} (ldx >= K in elements: row-strided views), d_q: [R][Kp] 16-byte aligned, d_e: [R][Kp/32]
+ * 4-byte aligned.  One pass; 16-byte loads when d_x and its rows are 16-byte aligned, element loads otherwise (same bytes out). */
+MVE_API int mve_mxfp8_quantize(int dtype, const void* d_x, int ldx, int R, int K, uint8_t* d_q, uint8_t* d_e, void* stream);
+/* out[m][n] = round_once( sum_k A[m][k] * W[n][k] + bias[n] + residual[m][n] ): packed A [M][Kp] / W [N][Kp] (torch Linear layout), fp32
+ * accumulation, then (acc + bias) + residual in fp32, one rounding to out_dtype in {MVE_F32, MVE_F16, MVE_BF16}.  d_out: [M][ldc];
+ * d_bias: [N] f32 (16-byte aligned) or NULL; d_residual: [M][ldr] of out_dtype or NULL.
+ * Constraints: K % 32 == 0, N % 8 == 0, M >= 1, ldc >= N, ldr >= N, d_aq / d_wq 16-byte and d_ae / d_we 4-byte aligned; anything else returns
+ * MVE_ERR_ARG with a message that names the argument, before the device is touched.
+ * Every output element is ONE fp32 accumulation chain over the 128-wide K steps in ascending order (no K split, no atomics), whatever M and N:
+ * two runs give the same bits, and a row's result does not depend on the rows around it. */
+MVE_API int mve_mxfp8_gemm(const uint8_t* d_aq, const uint8_t* d_ae, const uint8_t* d_wq, const uint8_t* d_we, int M, int N, int K, int out_dtype,
+                           void* d_out, int ldc, const float* d_bias, const void* d_residual, int ldr, void* stream);
+
 /* Scaled-dot-product attention over packed projections (no head permutes):
  *   Q row (b,i) at d_Q + (b*Lq+i)*ldq, head h at column h*head_dim; same for K/V with Lk, O with Lq.
  *   Optional second KV segment (K2,V2,Lk2) is logically concatenated after the first along the key
