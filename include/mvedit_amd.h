@@ -378,6 +378,36 @@ MVE_API int mve_attention_prescaled(int dtype, const void* d_Q, int ldq, const v
                                     const void* d_K2, int ldk2, const void* d_V2, int ldv2, void* d_O, int ldo,
                                     int B, int Lq, int Lk, int Lk2, int heads, int head_dim, void* stream);
 
+/* ---- 2c. CLIP text tower primitives (csrc/clip_text.hip): the arithmetic of transformers' CLIPTextModel / CLIPTextModelWithProjection
+ * (models/clip/modeling_clip.py) that the reference's pipelines run as `self.text_encoder` through diffusers' `_encode_prompt`
+ * (lib/pipelines/mvedit_3d_pipeline.py:368; the SDXL towers are built at lib/pipelines/utils.py:244-283).  Every argument error returns
+ * MVE_ERR_ARG with a message that names the argument, before the device is touched. */
+
+/* Causal scaled-dot-product SELF-attention over packed projections, as mve_attention lays them out (row (b,i) at d_X + (b*L+i)*ldx, head h at
+ * column h*64): key j is visible to query i only when j <= i -- the `is_causal=True` attention of CLIPAttention under CLIPTextModel
+ * (create_causal_mask + eager / sdpa attention, modeling_clip.py:298-335, :543-556).  head_dim == 64 (ViT-L, OpenCLIP-H and bigG text towers),
+ * 1 <= L <= 128 (CLIP: 77); ldq / ldk / ldv multiples of 8 and the three pointers 16-byte aligned.  Logits, mask, maximum, exp and sum in fp32;
+ * the causal triangle and the padded tail of the last tile are masked by a select (a masked key takes no part in the maximum and has probability
+ * exactly 0; no infinity is formed); fp32 accumulation, one rounding of the output.  One block per (batch item, head): two runs give the same
+ * bits, an item's output does not depend on B, and rows <= p do not depend on K / V rows > p. */
+MVE_API int mve_attention_causal(int dtype, const void* d_Q, int ldq, const void* d_K, int ldk, const void* d_V, int ldv, void* d_O, int ldo,
+                                 int B, int L, int heads, int head_dim, float scale, void* stream);
+/* CLIPTextEmbeddings (modeling_clip.py:221-277) with the default position ids: out[b,i,:] = round_once(float(tok[ids[b,i]]) + float(pos[i])).
+ * d_ids int32 [B,L]; d_tok [vocab,C], d_pos [max_pos,C] and d_out [B,L,C] in `dtype`, 16-byte aligned; C % 8 == 0; L <= max_pos.  The caller
+ * validates the ids; the kernel clamps one outside [0, vocab) so that it cannot read outside the table. */
+MVE_API int mve_clip_embed(int dtype, const int32_t* d_ids, const void* d_tok, const void* d_pos, void* d_out, int B, int L, int C, int vocab,
+                           int max_pos, void* stream);
+/* Elementwise activation in fp32, in or out of place (d_y may equal d_x): CLIPMLP.activation_fn (modeling_clip.py:338-350).
+ * MVE_ACT_QUICK_GELU: x * sigmoid(1.702 x) (transformers QuickGELUActivation, `hidden_act='quick_gelu'`); MVE_ACT_GELU: the erf form
+ * 0.5 x (1 + erf(x / sqrt 2)) (`hidden_act='gelu'`, nn.GELU()). */
+#define MVE_ACT_QUICK_GELU 0
+#define MVE_ACT_GELU 1
+MVE_API int mve_act(int dtype, int kind, const void* d_x, void* d_y, size_t n, void* stream);
+/* The pooled output of CLIPTextModel (modeling_clip.py:561-581): out[b,:] = x[b, pos(b), :] with pos chosen on the device from d_ids int32 [B,L]:
+ * eos_token_id == 2 (configs from before transformers PR #24773): the first position of the maximum id; otherwise the first position whose id
+ * equals eos_token_id, position 0 when there is none.  d_x [B,L,C], d_out [B,C] in `dtype`. */
+MVE_API int mve_clip_pool(int dtype, const void* d_x, const int32_t* d_ids, void* d_out, int B, int L, int C, int eos_token_id, void* stream);
+
 /* GroupNorm over NHWC input (optionally the channel-concat of two tensors) with optional fused SiLU:
  *   out[B*HW][C1+C2] = act( (x - mean_g) * rstd_g * gamma + beta ), torch.nn.GroupNorm semantics.
  * gamma/beta: [C1+C2] f32.  d_workspace: >= mve_groupnorm_workspace_bytes(B,HW,C,G) bytes.
@@ -648,6 +678,25 @@ MVE_API int mve_srvgg_create(void** handle, int dtype, int num_in_ch, int num_ou
 MVE_API int mve_srvgg_plan(void* handle, int B, int H, int W, int io_dtype, size_t* workspace_bytes, int* n_ops, double* flops);
 MVE_API int mve_srvgg_forward(void* handle, const void* d_in, int io_dtype, int B, int H, int W, void* d_out, void* d_workspace,
                               size_t workspace_bytes, float* op_ms, void* stream);
+/* CLIP text tower (`text_encoder` / `text_encoder_2` of the pipelines: transformers CLIPTextModel and CLIPTextModelWithProjection,
+ * models/clip/modeling_clip.py:494-586, :835-895; built at lib/pipelines/utils.py:244-283 and called through diffusers' `_encode_prompt`,
+ * lib/pipelines/mvedit_3d_pipeline.py:368).  An executor handle: parameters through mve_unet_load_param under transformers' own state-dict
+ * names (`text_model.embeddings.{token,position}_embedding.weight`, `text_model.encoder.layers.N.{layer_norm1,layer_norm2}.{weight,bias}`,
+ * `...self_attn.{q,k,v,out}_proj.{weight,bias}`, `...mlp.{fc1,fc2}.{weight,bias}`, `text_model.final_layer_norm.{weight,bias}`,
+ * `text_projection.weight` when projection_dim > 0); mve_unet_missing_params / mve_unet_op_info / mve_unet_destroy apply.
+ * Per layer: LayerNorm, one q|k|v GEMM over the packed [3C, C] weight, mve_attention_causal (scale = 64^-1/2), out_proj GEMM + residual,
+ * LayerNorm, fc1 GEMM, mve_act, fc2 GEMM + residual; then final LayerNorm, mve_clip_pool, and the bias-free text_projection GEMM.
+ * hidden == heads * 64, hidden <= 2048 (mve_layernorm), intermediate % 8 == 0, projection_dim % 8 == 0 (0 = no projection), act in
+ * {MVE_ACT_QUICK_GELU, MVE_ACT_GELU}; the forward's eos_token_id selects the pooling rule of mve_clip_pool.  d_ids int32 [B,L], 1 <= L <= min(max_pos, 128),
+ * validated by the caller.  Outputs in the handle's dtype: d_last_hidden_state [B,L,C], d_pooler_output [B,C], d_text_embeds [B,P] (required
+ * when the handle has a projection, NULL otherwise); d_hidden_states: NULL, or layers + 1 pointers to [B,L,C] tensors that receive the embedding
+ * output and every layer's output (before the final norm), transformers' `output_hidden_states=True`. */
+MVE_API int mve_clip_text_create(void** handle, int dtype, int vocab_size, int max_position_embeddings, int hidden_size, int num_layers,
+                                 int num_heads, int intermediate_size, int act, float layer_norm_eps, int projection_dim);
+MVE_API int mve_clip_text_plan(void* handle, int B, int L, size_t* workspace_bytes, int* n_ops, double* flops);
+MVE_API int mve_clip_text_forward(void* handle, const int32_t* d_ids, int B, int L, int eos_token_id, void* d_last_hidden_state,
+                                  void* d_pooler_output, void* d_text_embeds, void* const* d_hidden_states, void* d_workspace, size_t workspace_bytes, float* op_ms,
+                                  void* stream);
 /* LPIPS(net='vgg') perceptual loss, forward and backward w.r.t. the prediction: the `patch_loss` of the reference's reconstruct step
  * (lib/models/losses/lpips_loss.py:8-42 -> lpips==0.1.4 `LPIPS.forward`; lib/models/autoencoders/base_nerf.py:337-344, 8 patches of
  * 128 x 128 per optimisation iteration).  An executor handle: parameters through mve_unet_load_param under lpips' own state-dict

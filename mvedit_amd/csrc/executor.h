@@ -54,6 +54,10 @@ int mve_relu_backward(int, void*, const void*, size_t, void*);
 size_t mve_lpips_layer_scratch_bytes(int, int);
 int mve_lpips_layer(int, const void*, const float*, int, int, int, int, float*, void*, void*);
 int mve_lpips_layer_backward(int, const void*, const float*, const float*, int, int, int, void*, void*);
+int mve_attention_causal(int, const void*, int, const void*, int, const void*, int, void*, int, int, int, int, int, float, void*);
+int mve_clip_embed(int, const int32_t*, const void*, const void*, void*, int, int, int, int, int, void*);
+int mve_act(int, int, const void*, void*, size_t, void*);
+int mve_clip_pool(int, const void*, const int32_t*, void*, int, int, int, int, void*);
 }
 
 namespace {
@@ -124,6 +128,9 @@ struct Config {
     int sr = 0, sr_scale = 4;          // SRVGGNetCompact (lib/models/decoders/image_space_ss.py): ch[0] = num_feat, layers_per_block = num_conv
     int vae = 0;                       // AutoencoderKL half: 1 = post_quant_conv + Decoder, 2 = Encoder + quant_conv (no time embedding,
                                        // no transformers; in_ch / out_ch are the half's own input / output channels, both <= 8)
+    // CLIPTextModel(WithProjection) (transformers models/clip/modeling_clip.py): ch[0] = hidden_size, heads[0] = num_attention_heads,
+    // layers_per_block = num_hidden_layers, eps = layer_norm_eps; clip_proj = projection_dim (0: no text_projection)
+    int clip = 0, clip_vocab = 0, clip_max_pos = 0, clip_inter = 0, clip_act = 0, clip_proj = 0;
     int dtype, in_ch, out_ch, n_levels, layers_per_block, ctx_dim, groups, linear_proj;
     // UNet2DConditionModel / ControlNetModel addition_embed_type (mve_unet_set_addition_embed): 0 none, 1 'text_time' (SDXL);
     // add_time_dim = addition_time_embed_dim, add_P = projection_class_embeddings_input_dim (in_features of add_embedding.linear_1)
@@ -160,6 +167,7 @@ struct Run {
     const void* add_text = nullptr;           // 'text_time': text_embeds [B, add_text_dim] (add_text_dtype), time_ids f32 [B, add_n_ids]
     const float* add_ids = nullptr;           //              (mve_unet_bind_added_cond)
     int add_text_dtype = 0, add_text_dim = 0, add_n_ids = 0;
+    int clip_eos = 0;                         // CLIP text tower: eos_token_id of this forward (pooling rule of mve_clip_pool)
     hipStream_t stream;
     void* p(const Ref& r) const {
         switch (r.kind) {
@@ -326,7 +334,7 @@ struct XfDesc { std::string name; int c, heads, layers; };
 
 void enumerate(const Config& c, std::vector<ResnetDesc>& rs, std::vector<XfDesc>& xs) {
     const int n = c.n_levels, L = c.layers_per_block;
-    if (c.sr || c.lpips) return;     // plain conv stacks
+    if (c.sr || c.lpips || c.clip) return;     // plain conv stacks / the text tower (builder_clip.h)
     if (c.vae) {      // diffusers Encoder / Decoder (autoencoders/vae.py): resnets only, one attention in the mid block
         const int Cm = c.ch[n - 1];
         if (c.vae == 2) {

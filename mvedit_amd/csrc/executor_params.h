@@ -46,6 +46,36 @@ void layout_params(Unet& u) {
         u.slab_bytes = sb.top;
         return;
     }
+    if (c.clip) {
+        // transformers' names; q_proj / k_proj / v_proj share one [3C, C] matrix and one [3C] bias (one GEMM per layer)
+        const size_t C = c.ch[0], I = c.clip_inter;
+        const std::string em = "text_model.embeddings.";
+        sb.add(em + "token_embedding.w", (size_t)c.clip_vocab * C, false); need(em + "token_embedding.weight");
+        sb.add(em + "position_embedding.w", (size_t)c.clip_max_pos * C, false); need(em + "position_embedding.weight");
+        auto norm = [&](const std::string& n) {
+            sb.add(n + ".g", C, true); need(n + ".weight");
+            sb.add(n + ".b", C, true); need(n + ".bias");
+        };
+        auto linear = [&](const std::string& n, size_t rows, size_t cols) {
+            sb.add(n + ".w", rows * cols, false); need(n + ".weight");
+            sb.add(n + ".b", rows, true); need(n + ".bias");
+        };
+        for (int k = 0; k < c.layers_per_block; ++k) {
+            const std::string b = "text_model.encoder.layers." + std::to_string(k);
+            norm(b + ".layer_norm1");
+            sb.add(b + ".self_attn.qkv.w", 3 * C * C, false);
+            sb.add(b + ".self_attn.qkv.b", 3 * C, true);
+            for (const char* pj : {"q_proj", "k_proj", "v_proj"}) { need(b + ".self_attn." + pj + ".weight"); need(b + ".self_attn." + pj + ".bias"); }
+            linear(b + ".self_attn.out_proj", C, C);
+            norm(b + ".layer_norm2");
+            linear(b + ".mlp.fc1", I, C);
+            linear(b + ".mlp.fc2", C, I);
+        }
+        norm("text_model.final_layer_norm");
+        if (c.clip_proj) { sb.add("text_projection.w", (size_t)c.clip_proj * C, false); need("text_projection.weight"); }
+        u.slab_bytes = sb.top;
+        return;
+    }
     if (c.sr) {
         // body.0: conv in_ch -> F; body.(2k), k = 1..num_conv: conv F -> F; body.(2k+1): PReLU slopes; last: conv F -> out_ch * r * r
         const size_t F = c.ch[0];
@@ -293,7 +323,30 @@ int load_param(Unet& u, const std::string& name, const void* src, int src_dtype,
     const int Cm_ = c.ch[c.n_levels - 1];
     const int vin = c.vae == 1 ? Cm_ : c.ch[0], vout = c.vae == 1 ? c.ch[0] : Cm_;     // widths after conv_in / before conv_out
     const std::string va = "mid_block.attentions.0";
-    if (c.lpips) {
+    if (c.clip) {
+        const long long C = c.ch[0], I = c.clip_inter;
+        const std::string em = "text_model.embeddings.";
+        int which = -1;
+        for (int k = 0; k < 3; ++k)
+            if (ends_with(name, std::string(".self_attn.") + "qkv"[k] + "_proj.weight") || ends_with(name, std::string(".self_attn.") + "qkv"[k] + "_proj.bias")) which = k;
+        if (name == em + "token_embedding.weight") rc = mat(P(em + "token_embedding.w"), 0, c.clip_vocab, C, C);
+        else if (name == em + "position_embedding.weight") rc = mat(P(em + "position_embedding.w"), 0, c.clip_max_pos, C, C);
+        else if (which >= 0 && ends_with(name, ".weight"))
+            rc = mat(P(name.substr(0, name.size() - std::string("q_proj.weight").size()) + "qkv.w"), (size_t)which * C * C, C, C, C);
+        else if (which >= 0) rc = vec(P(name.substr(0, name.size() - std::string("q_proj.bias").size()) + "qkv.b"), (size_t)which * C, C, 1);
+        else if (ends_with(name, ".self_attn.out_proj.weight")) rc = mat(P(strip(name, ".weight") + ".w"), 0, C, C, C);
+        else if (ends_with(name, ".mlp.fc1.weight")) rc = mat(P(strip(name, ".weight") + ".w"), 0, I, C, C);
+        else if (ends_with(name, ".mlp.fc2.weight")) rc = mat(P(strip(name, ".weight") + ".w"), 0, C, I, I);
+        else if (ends_with(name, ".mlp.fc1.bias")) rc = vec(P(strip(name, ".bias") + ".b"), 0, I, 1);
+        else if (ends_with(name, ".self_attn.out_proj.bias") || ends_with(name, ".mlp.fc2.bias")) rc = vec(P(strip(name, ".bias") + ".b"), 0, C, 1);
+        else if (c.clip_proj && name == "text_projection.weight") rc = mat(P("text_projection.w"), 0, c.clip_proj, C, C);
+        else if (ends_with(name, ".weight") && P(strip(name, ".weight") + ".g")) rc = vec(P(strip(name, ".weight") + ".g"), 0, C, 1);   // the LayerNorms
+        else if (ends_with(name, ".bias") && P(strip(name, ".bias") + ".b") && P(strip(name, ".bias") + ".g")) rc = vec(P(strip(name, ".bias") + ".b"), 0, C, 1);
+        else {
+            mve_set_error("load_param: %s is not a parameter of this CLIP text model", name.c_str());
+            return MVE_ERR_ARG;
+        }
+    } else if (c.lpips) {
         int li = -1;
         for (int i = 0; i < 13; ++i) if (name.compare(0, vgg_name(i).size() + 1, vgg_name(i) + ".") == 0) li = i;
         if (li >= 0 && ends_with(name, ".weight")) {

@@ -33,6 +33,9 @@ What `install()` rebinds -- the operator seams of SURVEY.md section 8(b), nothin
      `mvedit_amd.nvdiffrast.torch` (parent first), so `import nvdiffrast.torch as dr` resolves and `dr.*` computes on the native kernels.  A
      base_mesh_renderer imported before `install()` gets `dr` rebound.
 
+Not part of `install()`: `swap_text_encoder(pipe)` puts native CLIP text towers (mvedit_amd/text_encoder.py) behind `pipe.text_encoder` /
+`pipe.text_encoder_2` of ONE pipeline object, on request.
+
 Nothing here computes: every replacement is one of the engines / mirrors INTEGRATION.md documents seam by seam, and a conversion that fails
 raises -- there is no fallback to the torch module.  `uninstall()` restores everything (tests).
 """
@@ -149,6 +152,34 @@ def decoder_params(decoder):
     return INGPDecoderParams(table, l1.weight.detach(), l1.bias.detach(), l2.weight.detach(), l2.bias.detach(), n_levels=decoder.n_levels,
                              max_resolution=decoder.max_resolution, bound=getattr(decoder, 'bound', 1.0), blob_density=decoder.blob_density,
                              blob_radius=decoder.blob_radius, sigmoid_saturation=decoder.sigmoid_saturation, device=table.device)
+
+
+def make_text_encoder(m):
+    """transformers CLIPTextModel / CLIPTextModelWithProjection (`text_encoder`, `text_encoder_2`; lib/pipelines/utils.py:244-283)."""
+    from .text_encoder import CLIPTextEngine
+    dtype, device = _module_dtype_device(m)
+    return CLIPTextEngine.from_module(m, dtype=dtype, device=device)
+
+
+TEXT_ENCODER_ATTRS = ('text_encoder', 'text_encoder_2')
+
+
+def swap_text_encoder(pipe):
+    """Opt-in (install() / swap_engines leave the text towers alone): replaces `pipe.text_encoder` and, when present, `pipe.text_encoder_2` by
+    native engines built from those modules.  Idempotent; the engine is cached on the source module like the other seams'."""
+    for name in TEXT_ENCODER_ATTRS:
+        m = getattr(pipe, name, None)
+        if m is None or getattr(m, '_mve_is_engine', False) or not hasattr(m, 'state_dict'):
+            continue
+        fp = _fingerprint(m)
+        cached = getattr(m, '_mve_engine', None)
+        if cached is None or cached[0] != fp:
+            eng = make_text_encoder(m)
+            object.__setattr__(eng, '_mve_is_engine', True)
+            cached = (fp, eng)
+            object.__setattr__(m, '_mve_engine', cached)
+        object.__setattr__(pipe, name, cached[1])
+    return pipe
 
 
 MAKERS = dict(unet=make_unet, controlnet=make_controlnet, vae=make_vae, image_enhancer=make_image_enhancer, segmentation=make_segmentation,
