@@ -205,6 +205,26 @@ MVE_API int mve_gemm_deep_tune(int max_blocks);
  * of rows per image, N, K only), 1 where the un-split launch fills the chip (or the rule's count again in the strict mode, which emulates the slices
  * inside one block), or the smallest count that fills the chip where the rule would over-fill it.  Host logic only. */
 MVE_API int mve_gemm_effective_splitk(int M, int N, int K, int rows_per_image);
+/* Diagnostics: the dispatch plan of a launch under the current switches (csrc/gemm_dispatch.h: gemm_plan -- the function the entry points launch
+ * from).  Host logic only: no GPU is touched, no buffer is needed.  The parameters are filled by the code the entry points use:
+ *   kind 0: mve_gemm / mve_gemm_pair / mve_gemm_pair_ln of M x N x K with dense leading dimensions (conv_geom may be null);
+ *   kind 1: mve_conv3x3* with conv_geom = {C1, C2, C3, C4, B, Hs, Ws, stride, upsample} and N = Cout (C3 > 0: the shortcut forms); M, K ignored;
+ *   kind 2: one launch of mve_upsample_conv_phases with conv_geom = {C, 0, 0, 0, B, Hs, Ws} and N = Cout; M, K ignored.
+ * `flags`: the MVE_GEMM_* / MVE_CONV_* flags of the call.  `features`: which optional operands the call has (MVE_PLAN_*).  With MVE_GEMM_RED on,
+ * the slice-fold counters are taken to be available.  out[MVE_PLAN_DESCRIBE_INTS] = {family (0: 128-row kernel, 1: 256-row two-stage loop,
+ * 2: ping-pong loop, 3: ping-pong three-slot 256 x 160 tile), tile width, tile rows, ring (0: two-stage, 1: four-stage, 2: ping-pong), epilogue
+ * (0: plain, 1: residual pair, 2: in-launch slice fold, 3: fused LayerNorm, 4: in-block slice emulation), splitk, splitk_seq, 1 if a split-K
+ * reducer launch follows, w_major, grid (blocks), number of such launches the entry point makes (4 for unfused phases), M of the launch}. */
+#define MVE_PLAN_RESIDUAL 1
+#define MVE_PLAN_RESIDUAL_LO 2
+#define MVE_PLAN_OUT_LO 4
+#define MVE_PLAN_ROWVEC 8
+#define MVE_PLAN_LN 16          /* mve_gemm_pair_ln */
+#define MVE_PLAN_BIAS 32
+#define MVE_PLAN_WORKSPACE 64   /* a split-K workspace of sufficient size */
+#define MVE_PLAN_SCALED 128     /* out_scale != 1 */
+#define MVE_PLAN_DESCRIBE_INTS 12
+MVE_API int mve_gemm_plan_describe(int kind, int M, int N, int K, int rows_per_image, int flags, int features, const int* conv_geom, int* out);
 
 /* Development aid for csrc/gemm_pp.hip: with `d_buf` (device, 64 uint64 per launched block) set, fp16 320-wide launches of the
  * ping-pong kernel run an instrumented copy and every wave writes its shader-clock sums {L-section work, wait at the L barrier,

@@ -63,6 +63,22 @@ static inline unsigned mve_cdiv(unsigned long long a, unsigned long long b) {
     return (unsigned)((a + b - 1) / b);
 }
 
+// Launch a kernel that needs more dynamic LDS than the 64 KiB a kernel gets without asking: hipFuncAttributeMaxDynamicSharedMemorySize is set
+// once per kernel instantiation and device (the attribute is per device; one process may drive several), then the kernel is launched.
+template <auto Kernel, class... Args>
+int mve_launch_dyn_lds(dim3 grid, dim3 block, int lds_bytes, hipStream_t s, const Args&... args) {
+    static bool configured[64] = {};
+    int dev = 0;
+    MVE_HIP(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64 || !configured[dev]) {
+        MVE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+        if (dev >= 0 && dev < 64) configured[dev] = true;
+    }
+    Kernel<<<grid, block, lds_bytes, s>>>(args...);
+    MVE_LAUNCH_CHECK();
+    return MVE_OK;
+}
+
 // ---------------------------------------------------------------------------
 // 16-bit storage types.  Kernels are templated on a tag so fp16 and bf16 share
 // one source; accumulation is always fp32.

@@ -37,6 +37,7 @@
 #include <mutex>
 #include <utility>
 
+#include "gemm_dispatch.h"
 #include "gemm_shared.h"
 
 namespace {
@@ -44,13 +45,6 @@ namespace {
 constexpr int BM = 128;
 
 }  // namespace
-// defined in gemm_big.hip (256 x 320 tiles, bit-identical results)
-long long mve_gemm_big_blocks(int M, int N, int splitk);
-int mve_gemm_big_launch(int dtype, int mode, const void* params, void* stream);
-int mve_gemm_pp_launch(int dtype, int mode, const void* params, void* stream);      // gemm_pp.hip; 1 = not eligible
-void mve_gemm_pp_old_swizzle(int on);
-bool mve_gemm_pp_ln_fused();
-int mve_gemm_pp_ln_fuse_tune(int on);
 extern "C" int mve_layernorm_pair(int, const void*, int, void*, int, int, int, const float*, const float*, float, const void*, void*);
 namespace {
 
@@ -60,7 +54,7 @@ namespace {
 // ~0.3 us of MFMA work: time_embedding.linear_2, 20 tiles, 26.6 us; the 8 x 8 conv at 8 images, 22 tiles per slice, 40 us).  The ring keeps THREE tiles in
 // flight and never drains: LDS-DMA pieces issued from inline asm (M0 owned by the loop), one `s_waitcnt vmcnt(2 x pieces)` + `s_barrier` per tile.
 // Same tile, MFMA order and epilogue: bit-identical results.
-// BM (round 6): rows of the tile, 128 or 64.  64 x 64 tiles serve launches so small that even 128 x 64 tiles leave CUs with a single block (launch_v):
+// BM (round 6): rows of the tile, 128 or 64.  64 x 64 tiles serve launches so small that even 128 x 64 tiles leave CUs with a single block (gemm_dispatch.h: plan_v128):
 // the waves stay 2 x 2, a wave owns 32 rows, the epilogue is ONE 64-row pass written by both wave rows.  Same K order and epilogue arithmetic: same bits.
 template <class Tag, int BN, int MODE, int NST, int BM = 128>   // MODE 0: dense A, 1: conv3x3 gather
 __device__ __forceinline__ void gemm_body(const GemmParams& p, unsigned char* smem) {
@@ -444,245 +438,13 @@ __global__ __launch_bounds__(256) void k_splitk_reduce(const GemmParams p) {
     gemm_epilogue_store<Tag>(p, m, n, v);
 }
 
-// Split K at the deep UNet levels, where one image contributes only a few output tiles (8x8 / 16x16 latents) but K is
-// 9*1280..9*2560.  The RULE below is a function of (rows per image, N, K) only -- never of the batch.  What a launch actually runs with is the
-// rule's count only while the launch is small: launch_gemm (below) runs ONE accumulation chain where the un-split launch fills the chip and
-// `ceil(256 / tiles)` slices where the rule would over-fill it, so the effective count falls with the rows of the launch
-// (mve_gemm_effective_splitk; 16 x 16 level: 4 slices up to 16 images, 2 at 32, 1 from 64; 8 x 8 level: 8 / 4 / 2 / 1 slices at <= 32 / 64 / 128 /
-// 256 images).  A view therefore gets bit-identical results alone, in a chunk or on another rank AS LONG AS those launches take the same decision
-// (all small batches do); MVE_GEMM_STRICT_SPLITK=1 / mve_gemm_tune bit 30 / mvedit_amd.parallel.set_partition_invariant() make every launch
-// round as the rule's slices, at any batch (tests/test_abi.py::test_effective_splitk_by_batch).
-template <class Tag>
-int splitk_reduce_launch(const GemmParams& p, hipStream_t s) {
-    if (p.splitk > 1 && !p.sk_sync) {
-        k_splitk_reduce<Tag><<<mve_cdiv((size_t)p.M * (p.N / 8), 256), 256, 0, s>>>(p);
-        MVE_LAUNCH_CHECK();
-    }
-    return MVE_OK;
+// ---- host side: compute the plan (gemm_dispatch.h: gemm_plan is the one place that decides), build the parameter copy it implies, launch -------------
+
+GemmSwitches& gemm_switches() {
+    static GemmSwitches sw = GemmSwitches::from_env();      // on first use of any GEMM entry point or tune call, not at library load
+    return sw;
 }
 
-int g_splitk_policy = -1;      // MVE_GEMM_SPLITK: 1 (default) = the rule below; 0 = never split (A/B: what the slices cost at a given batch)
-int choose_splitk(int rows_per_image, int N, int K) {
-    if (g_splitk_policy < 0) {
-        const char* e = getenv("MVE_GEMM_SPLITK");
-        g_splitk_policy = e ? atoi(e) : 1;
-    }
-    if (rows_per_image <= 0 || g_splitk_policy == 0) return 1;
-    const int bn = (N % 160 == 0) ? 160 : (N % 128 == 0 ? 128 : (N <= 64 ? 64 : 128));
-    const long long t1 = (long long)mve_cdiv(rows_per_image, BM) * mve_cdiv(N, bn);      // tiles of ONE image
-    const int nk = (K + BK - 1) / BK;
-    // ceil (round 6): an image of 40 tiles (the 30 x 20 level of Zero123++'s 120 x 80 latent: 80 blocks for a CFG pair, each walking K = 11 520 alone --
-    // 271 us per conv, profiles/r06_trace_zero123pp.txt) gets 2 slices instead of 1.  Power-of-two tile counts (every level of a 64 x 64 latent: 64 / 32 /
-    // 16 / 8 tiles) divide 64: their slice counts, and with them every bit of those results, are unchanged.
-    long long s = (64 + t1 - 1) / t1;
-    if (s > nk / 8) s = nk / 8;        // at least 8 K tiles (512 k) per slice
-    if (s > 16) s = 16;
-    return s < 2 ? 1 : (int)s;
-}
-
-int gemm_red_mode();
-int* gemm_sk_sync(hipStream_t s);
-constexpr int SK_SYNC_TILES = 8192;
-
-// Weight-strip-major block order for launches whose activations are the smaller operand (GemmParams::w_major).  MVE_GEMM_WMAJOR=0 / mve_gemm_deep_tune bit 30 off.
-int g_w_major = -1;
-bool gemm_w_major_on() {
-    if (g_w_major < 0) {
-        const char* e = getenv("MVE_GEMM_WMAJOR");
-        g_w_major = e ? atoi(e) : 1;
-    }
-    return g_w_major != 0;
-}
-
-// Narrower tile for launches of at most gemm_small_bn_max_blocks() 128 x 160 blocks (see launch_v).  MVE_GEMM_SMALL_BN = 0 | 64 | 128, MVE_GEMM_SMALL_BN_MAX.
-int g_small_bn = -1, g_small_bn_max = -1;
-int gemm_small_bn() {
-    if (g_small_bn < 0) {
-        const char* e = getenv("MVE_GEMM_SMALL_BN");
-        g_small_bn = e ? atoi(e) : 64;      // same-box sweep, profiles/r06_ab_small_bn.log: Zero123++ 21.55 -> 20.4 ms, 8-image forward -1 %; 128 is neutral
-        if (g_small_bn != 64 && g_small_bn != 128) g_small_bn = 0;
-    }
-    return g_small_bn;
-}
-int gemm_small_bn_max_blocks() {
-    if (g_small_bn_max < 0) {
-        const char* e = getenv("MVE_GEMM_SMALL_BN_MAX");
-        g_small_bn_max = e ? atoi(e) : 384;
-    }
-    return g_small_bn_max;
-}
-
-int g_small_bm = -1, g_small_bm_max = -1;
-int gemm_small_bm() {
-    if (g_small_bm < 0) {
-        const char* e = getenv("MVE_GEMM_SMALL_BM");
-        g_small_bm = e ? atoi(e) : 0;
-        if (g_small_bm != 64) g_small_bm = 0;
-    }
-    return g_small_bm;
-}
-int gemm_small_bm_max_blocks() {
-    if (g_small_bm_max < 0) {
-        const char* e = getenv("MVE_GEMM_SMALL_BM_MAX");
-        g_small_bm_max = e ? atoi(e) : 512;
-    }
-    return g_small_bm_max;
-}
-
-// K columns per block from which a launch that fills neither 256-row rule takes the ping-pong 256 x 160 tile anyway; 0 = never.  MVE_GEMM_PP160_MINK.
-int g_pp160_min_k = -1;
-int gemm_pp160_min_k() {
-    if (g_pp160_min_k < 0) {
-        const char* e = getenv("MVE_GEMM_PP160_MINK");
-        g_pp160_min_k = e ? atoi(e) : 1440;      // same-box sweep, profiles/r06_ab_pp160_min_k.log: Zero123++ 22.9 -> 21.4 ms, 8-image forward 12.44 -> 12.18 ms; 640 and below lose again
-    }
-    return g_pp160_min_k;
-}
-
-// The four-stage ring of the 128-row kernel (k_gemm_deep) for launches of at most this many blocks; 0 turns it off.  MVE_GEMM_DEEP / mve_gemm_deep_tune.
-int g_gemm_deep = -1;
-int gemm_deep_max_blocks() {
-    if (g_gemm_deep < 0) {
-        const char* e = getenv("MVE_GEMM_DEEP");
-        g_gemm_deep = e ? atoi(e) : 0;
-    }
-    return g_gemm_deep;
-}
-
-template <class Tag>
-int splitk_reduce_launch(const GemmParams& p, hipStream_t s);
-
-template <class Tag, int BN, int MODE>
-int launch_deep(const GemmParams& p, unsigned grid, hipStream_t s) {
-    constexpr int SM = gemm_smem_bytes<BN, DEEP_NST>();
-    static bool configured[64] = {};
-    int dev = 0;
-    MVE_HIP(hipGetDevice(&dev));
-    if (dev >= 0 && dev < 64 && !configured[dev]) {
-        MVE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_deep<Tag, BN, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, SM));
-        configured[dev] = true;
-    }
-    k_gemm_deep<Tag, BN, MODE><<<grid, NT, SM, s>>>(p);
-    MVE_LAUNCH_CHECK();
-    return splitk_reduce_launch<Tag>(p, s);
-}
-
-template <class Tag, int MODE>
-int launch_v(const GemmParams& p, hipStream_t s) {
-    MVE_CHECK(p.g.kw != 2, MVE_ERR_STATE, "gemm: 2 x 2 conv windows run on the ping-pong kernel only");
-    // tile width: prefer the widest tile that divides N (no dead columns), else 128
-    int bn = 128;
-    if (p.N % 160 == 0) bn = 160;
-    else if (p.N % 128 == 0) bn = 128;
-    else if (p.N <= 64) bn = 64;
-    // (round 6) a launch of at most one 128 x 160 block per CU runs its phases back to back (one wave per SIMD: LDS-DMA, fragment reads + MFMAs and
-    // the epilogue add up, profiles/r06_gemm_lab_ablation.txt); narrower tiles put two or more blocks on a CU, whose phases overlap.  gemm_small_bn():
-    // the tile width such launches take when it divides N (0 = keep 160).  Bit-identical like every tile choice.
-    if (bn == 160 && gemm_small_bn() > 0 && p.N % gemm_small_bn() == 0 &&
-        mve_cdiv(p.M, BM) * mve_cdiv(p.N, 160) * (p.splitk > 1 ? p.splitk : 1) <= (unsigned)gemm_small_bn_max_blocks())
-        bn = gemm_small_bn();
-    const unsigned tiles_m = mve_cdiv(p.M, BM), tiles_n = mve_cdiv(p.N, bn);
-    const unsigned grid = tiles_m * tiles_n * (p.splitk > 1 ? p.splitk : 1);
-#ifdef MVE_GEMM_LAB
-    { const char* e = getenv("MVE_GEMM_LAB_BITS"); const_cast<GemmParams&>(p).dbg = e ? atoi(e) : 0; }
-#endif
-    // K slices folded inside the launch (gemm_reduce_slices) where every block of the grid is resident at once -- two 72 KiB blocks per CU -- so that a
-    // block waiting for its siblings never holds the slot one of them needs: no k_splitk_reduce launch behind such a launch
-    GemmParams pf;
-    if (p.splitk > 1 && !p.sk_sync && (gemm_red_mode() & 1) && grid <= 512 && tiles_m * tiles_n <= (unsigned)SK_SYNC_TILES &&
-        (unsigned long long)p.splitk * p.M * p.N * 4ull < 0xF0000000ull) {
-        if (int* sync = gemm_sk_sync(s)) {
-            pf = p;
-            pf.sk_sync = sync;
-            return launch_v<Tag, MODE>(pf, s);
-        }
-    }
-    // launches of at most gemm_deep_max_blocks() blocks (a block or two per CU) and more than two K tiles per block: the four-stage ring (k_gemm_deep)
-    const int nk_slice = ((p.K + BK - 1) / BK) / (p.splitk > 1 ? p.splitk : 1);
-    if ((int)grid <= gemm_deep_max_blocks() && nk_slice > 2 && bn >= 128) {
-        if (bn == 160) return launch_deep<Tag, 160, MODE>(p, grid, s);
-        return launch_deep<Tag, 128, MODE>(p, grid, s);
-    }
-    // ... and 64 x 64 tiles where even the 128 x 64 tiling is at most gemm_small_bm_max_blocks() blocks (MVE_GEMM_SMALL_BM = 64 | 0)
-    if (bn == 64 && gemm_small_bm() == 64 && p.N % 64 == 0 && p.M > 64 && (int)grid <= gemm_small_bm_max_blocks()) {
-        const unsigned grid64 = mve_cdiv(p.M, 64) * tiles_n * (p.splitk > 1 ? p.splitk : 1);
-        k_gemm64<Tag, 64, MODE><<<grid64, NT, 0, s>>>(p);
-        MVE_LAUNCH_CHECK();
-        return splitk_reduce_launch<Tag>(p, s);
-    }
-    if (bn == 160) k_gemm<Tag, 160, MODE><<<grid, NT, 0, s>>>(p);
-    else if (bn == 128) k_gemm<Tag, 128, MODE><<<grid, NT, 0, s>>>(p);
-    else k_gemm<Tag, 64, MODE><<<grid, NT, 0, s>>>(p);
-    MVE_LAUNCH_CHECK();
-    return splitk_reduce_launch<Tag>(p, s);
-}
-
-// What a launch does when the slice rule (choose_splitk) asks for S > 1 slices but the un-split launch already fills the chip (>= one 256 x 320
-// tile per CU: 64 images on one GPU at the 32 x 32 and 16 x 16 levels).
-//   0 (default, round 4): one block per tile walks all of K in ONE accumulation chain.  The result differs from the sliced sum (what the same
-//     image gets in a small batch, where the slices run as separate blocks + reducer) by fp32 summation order only -- well inside the 16-bit output
-//     rounding, see tests/test_unet_ops.py::test_unsplit_chain_vs_sliced_sum -- so bitwise batch invariance holds among launches that take the
-//     same decision (all small batches; all chip-filling batches), not across the two.
-//   1 (MVE_GEMM_STRICT_SPLITK=1 / mve_gemm_tune bit 30): the block emulates the slices (GemmParams::splitk_seq: accumulators folded into an fp32
-//     running total at every slice boundary), bitwise equal to split-K + reducer at any batch.  Measured cost at 64 images: the fold drains
-//     the DMA ring and moves 160 fp32 registers per lane through HBM per slice: level-1 / level-2 convs 1 080 -> 1 310-1 400 TFLOP/s without it,
-//     the N = K GEMMs of level 2 550 -> 900, ff.out 750 -> 1 240; 3.8 ms of a 68 ms step (profiles/r04_oplist_*.log).
-int g_strict_splitk = -1;
-int gemm_strict_splitk() {
-    if (g_strict_splitk < 0) {
-        const char* e = getenv("MVE_GEMM_STRICT_SPLITK");
-        g_strict_splitk = e ? (atoi(e) != 0) : 0;
-    }
-    return g_strict_splitk;
-}
-
-// minimum number of 256 x 320 blocks for which the big-tile kernel is used (0 disables it); MVE_GEMM_BIG overrides
-int g_big_min_blocks = -1;
-int g_seq_splitk = 1;         // mve_gemm_tune bit 29 clears it (A/B: real split-K + reducer)
-int gemm_big_min_blocks() {
-    if (g_big_min_blocks < 0) {
-        const char* e = getenv("MVE_GEMM_BIG");
-        g_big_min_blocks = e ? atoi(e) : 256;     // one block per CU: measured break-even on MI355X (profiles/r01_ab_gemm_big*.log)
-    }
-    return g_big_min_blocks;
-}
-
-// The 256-row tile has two main loops with bit-identical results: the ping-pong schedule (gemm_pp.hip) wherever it is eligible,
-// else the two-stage loop (gemm_big.hip).  mve_gemm_tune bit 27 / MVE_GEMM_PP=0 turn the former off (A/B).
-int g_gemm_pp = -1;
-bool gemm_pp_on() {
-    if (g_gemm_pp < 0) {
-        const char* e = getenv("MVE_GEMM_PP");
-        g_gemm_pp = e ? atoi(e) : 1;
-    }
-    return g_gemm_pp != 0;
-}
-// The two-blocks-per-CU 256 x 160 tile (gemm_pp.hip, NSL = 3) for dense GEMMs, bit-identical results.  2 (default): taken where the dispatcher
-// asks for the narrow tile because 320-wide tiles would leave CUs idle (small batches: the per-wave epilogue and the second resident block are
-// what those short launches lack); 1: wherever it is eligible (A/B: slower at 64 images); 0: never.  MVE_GEMM_PP2 / mve_gemm_tune.
-int g_gemm_pp2 = -1;
-int g_old_swizzle = 0;
-
-int gemm_pp2_mode() {
-    if (g_gemm_pp2 < 0) {
-        const char* e = getenv("MVE_GEMM_PP2");
-        g_gemm_pp2 = e ? atoi(e) : 2;
-        if (g_gemm_pp2 < 0 || g_gemm_pp2 > 2) g_gemm_pp2 = 2;
-    }
-    return g_gemm_pp2;
-}
-// In-kernel slice reduction (round 6; gemm_pp.hip: pp_reduce_slices).  A K-sliced launch that the ping-pong tile can take (320-wide where that fills
-// the chip, 160-wide otherwise) folds its slices inside the launch: no k_splitk_reduce launch behind it, and -- for the small launches of a rank
-// that holds few images, which used to run on the 128-row two-stage kernel -- the deep LDS-DMA ring of the ping-pong loop.  Bit-identical to
-// partials + reducer (same slices, same fold order, same epilogue function).  MVE_GEMM_RED=0 / mve_gemm_red_tune(0) restore the reducer launches.
-int g_gemm_red = -1;      // bit 0: the 128-row kernel folds its slices (launch_v);  bit 1: small K-sliced launches go to the ping-pong tile and fold there (launch_red)
-int gemm_red_mode() {
-    if (g_gemm_red < 0) {
-        const char* e = getenv("MVE_GEMM_RED");
-        g_gemm_red = e ? atoi(e) : 0;      // off: measured slower than partials + reducer on every K-sliced launch of an 8-image forward but the longest (profiles/r06_fold_modes_8images.log)
-    }
-    return g_gemm_red;
-}
 // one zeroed counter array per (device, stream): launches of a stream are ordered, and every launch leaves its counters at zero
 int* gemm_sk_sync(hipStream_t s) {
     static std::mutex mu;
@@ -700,128 +462,65 @@ int* gemm_sk_sync(hipStream_t s) {
     bufs[{dev, s}] = b;
     return b;
 }
-// -> MVE_OK: launched, result complete;  1: not taken (the caller runs its ordinary path);  < 0: error
-int launch_red(int dtype, int mode, const GemmParams& p, hipStream_t s) {
-    if (!(gemm_red_mode() & 2) || !gemm_pp_on() || p.splitk <= 1 || p.splitk > 64 || p.M < 64) return 1;
-    GemmParams q = p;
-    const long long tm = mve_cdiv(p.M, 256);
-    if (p.N % 320 == 0 && tm * (p.N / 320) * p.splitk >= 256) q.tile_n = 0;
-    else if (p.N % 160 == 0) q.tile_n = 160;
-    else return 1;
-    const long long tiles = tm * (p.N / (q.tile_n == 160 ? 160 : 320));
-    if (tiles > SK_SYNC_TILES || tiles * p.splitk > 256) return 1;      // every block of the grid resident at once (one 104-144 KiB block per CU): a block waiting for its siblings never holds the slot one of them needs
-    if ((unsigned long long)p.splitk * p.M * p.N * 4ull >= 0xF0000000ull) return 1;      // the partial tiles are addressed through 32-bit buffer offsets
-    q.sk_sync = gemm_sk_sync(s);
-    if (!q.sk_sync) return 1;
-    return mve_gemm_pp_launch(dtype, mode, &q, s);
-}
 
-// MVE_OK after a launch, 1 when neither loop takes the problem (the caller falls back to the 128-row kernel), < 0 on error
-int launch_tile256(int dtype, int mode, const GemmParams* q, hipStream_t s) {
-    const int pp2 = gemm_pp2_mode();
-    // (round 6) in the default mode also the chip-filling launches WITHOUT a GEGLU epilogue: attn1.qkv / attn2.to_q at every level run 8-16 % faster on
-    // two 256 x 160 blocks per CU than on one 256 x 320 block (the epilogue of one block under the K loop of the other; K = C is 10-40 steps), the
-    // GEGLU launches 6-7 % slower at the 32 x 32 level (profiles/r06_oplist64_pp2_ab.txt) -- residual / pair launches are not eligible for this tile
-    if (gemm_pp_on() && mode == 0 && q->splitk <= 1 && q->splitk_seq <= 1 &&
-        ((pp2 == 1 && q->tile_n == 0) || (pp2 == 2 && (q->tile_n == 160 || (q->tile_n == 0 && !q->geglu))))) {
-        GemmParams r = *q;
-        r.tile_n = 161;
-        const int rc = mve_gemm_pp_launch(dtype, mode, &r, s);
-        if (rc <= 0) return rc;
-    }
-    if (gemm_pp_on()) {
-        const int rc = mve_gemm_pp_launch(dtype, mode, q, s);
-        if (rc <= 0) return rc;
-    }
-    if (q->tile_n == 160 || mve_gemm_big_blocks(q->M, q->N, q->splitk) <= 0) return 1;
-    if (q->residual_lo || q->out_lo) return 1;        // residual_pair mode: only the ping-pong 320-wide tile and the 128-row kernel carry the pair
-    return mve_gemm_big_launch(dtype, mode, q, s);
-}
-
-// Width of the 256-row tile for N columns (0: none fits): 320 (every UNet width), 256 (the VAE's 256 / 512-channel convs; no
-// split-K variants), 128 (the VAE's 128-channel convs at image resolution; ping-pong loop only, no split-K).  Any other N -- 8 for
-// conv_out -- would leave most of a tile dead and takes the 128 x {64,128,160} kernel, whose results are bit-identical.
-int tile256_bn(int N, int splitk) {
-    if (N % 320 == 0) return 320;
-    if (splitk > 1) return 0;
-    if (N % 256 == 0) return 256;
-    if (N % 128 == 0 && gemm_pp_on()) return 128;
-    return 0;
-}
-long long tile256_blocks(int M, int N, int splitk) {
-    const int bn = tile256_bn(N, splitk);
-    if (bn == 0 || M < 64) return 0;
-    return (long long)mve_cdiv(M, 256) * (N / bn) * (splitk > 1 ? splitk : 1);
+// the 128-row kernel the plan names
+template <class Tag, int MODE>
+int launch_v128(const GemmPlan& pl, GemmParams p, hipStream_t s) {
+#ifdef MVE_GEMM_LAB
+    { const char* e = getenv("MVE_GEMM_LAB_BITS"); p.dbg = e ? atoi(e) : 0; }
+#endif
+    const int bn = pl.tile_n;
+    const bool deep = pl.ring == GEMM_RING_DEEP && pl.tile_m == 128, two = pl.ring == GEMM_RING_TWO_STAGE && pl.tile_m == 128;
+    if (deep && bn == 160) return mve_launch_dyn_lds<&k_gemm_deep<Tag, 160, MODE>>(pl.grid, NT, gemm_smem_bytes<160, DEEP_NST>(), s, p);
+    if (deep && bn == 128) return mve_launch_dyn_lds<&k_gemm_deep<Tag, 128, MODE>>(pl.grid, NT, gemm_smem_bytes<128, DEEP_NST>(), s, p);
+    if (pl.ring == GEMM_RING_TWO_STAGE && pl.tile_m == 64 && bn == 64) k_gemm64<Tag, 64, MODE><<<pl.grid, NT, 0, s>>>(p);
+    else if (two && bn == 160) k_gemm<Tag, 160, MODE><<<pl.grid, NT, 0, s>>>(p);
+    else if (two && bn == 128) k_gemm<Tag, 128, MODE><<<pl.grid, NT, 0, s>>>(p);
+    else if (two && bn == 64) k_gemm<Tag, 64, MODE><<<pl.grid, NT, 0, s>>>(p);
+    else MVE_CHECK(false, MVE_ERR_STATE, "gemm: no 128-row kernel for the plan (ring %d, tile %d x %d)", pl.ring, pl.tile_m, bn);
+    MVE_LAUNCH_CHECK();
+    return MVE_OK;
 }
 
 template <class Tag, int MODE>
-int launch_gemm_split(const GemmParams& p, hipStream_t s);
-
-template <class Tag, int MODE>
-int launch_gemm(const GemmParams& p, hipStream_t s) {
-    if (tile256_bn(p.N, p.splitk) == 0) return launch_v<Tag, MODE>(p, s);
-    // enough 256 x 320 tiles to fill the chip WITHOUT cutting K: one block per tile walks the slices one after the other and
-    // reproduces the split-K rounding exactly (GemmParams::splitk_seq) -- no partial tiles, no reducer launch
-    if (gemm_big_min_blocks() > 0 && p.splitk > 1 && p.N % 320 == 0 && g_seq_splitk && tile256_blocks(p.M, p.N, 1) >= gemm_big_min_blocks() &&
-        (size_t)tile256_blocks(p.M, p.N, 1) * 256 * 320 <= (size_t)p.splitk * p.M * p.N) {
-        GemmParams q = p;
-        q.splitk_seq = gemm_strict_splitk() ? p.splitk : 0;      // default: ONE accumulation chain over all of K (see gemm_strict_splitk)
-        q.splitk = 1;
-        const int rc = launch_tile256(Tag::dtype, MODE, &q, s);
-        if (rc != 1) return rc;                            // 1: no 256-row loop takes it in this form (e.g. strict slices + residual pair): split K for real below
+int launch_plan(const GemmPlan& pl, const GemmParams& q, hipStream_t s) {
+    int rc = MVE_OK;
+    switch (pl.family) {
+        case GEMM_V128: rc = launch_v128<Tag, MODE>(pl, q, s); break;
+        case GEMM_BIG: rc = mve_gemm_big_launch(Tag::dtype, MODE, &pl, &q, s); break;
+        default: rc = mve_gemm_pp_launch(Tag::dtype, MODE, &pl, &q, s); break;
     }
-    // The slice rule asks for more slices than this launch needs to fill the chip (64 images at the 8 x 8 level: 64 tiles x 8 slices): cut K into
-    // just enough slices for one block per CU -- every slice fewer is 2 x M x N x 4 bytes of fp32 partials less through HBM and a longer K loop
-    // per prologue / epilogue.  Like the single chain above this changes the fp32 summation order with the batch, not the value; the strict mode
-    // keeps the rule's slice count.
-    GemmParams pfew;
-    const GemmParams* pp = &p;
-    if (!gemm_strict_splitk() && gemm_big_min_blocks() > 0 && p.splitk > 2 && p.N % 320 == 0) {
-        const long long t1 = tile256_blocks(p.M, p.N, 1);
-        if (t1 > 0 && t1 * p.splitk >= 2 * gemm_big_min_blocks()) {
-            int few = (int)((gemm_big_min_blocks() + t1 - 1) / t1);
-            few = few < 2 ? 2 : few;
-            if (few < p.splitk) { pfew = p; pfew.splitk = few; pp = &pfew; }
-        }
+    if (rc != MVE_OK) return rc;
+    if (pl.reducer) {
+        k_splitk_reduce<Tag><<<mve_cdiv((size_t)q.M * (q.N / 8), 256), 256, 0, s>>>(q);
+        MVE_LAUNCH_CHECK();
     }
-    if (pp != &p) return launch_gemm_split<Tag, MODE>(*pp, s);
-    return launch_gemm_split<Tag, MODE>(p, s);
+    return MVE_OK;
 }
 
-template <class Tag, int MODE>
-int launch_gemm_split(const GemmParams& p, hipStream_t s) {
-    if (p.splitk > 1) {
-        const int rc = launch_red(Tag::dtype, MODE, p, s);
-        if (rc != 1) return rc;
-    }
-    // small batches: 256 x 320 tiles would leave CUs without a block, 256 x 160 tiles (ping-pong loop only) still cover them
-    const bool narrow = gemm_big_min_blocks() > 0 && gemm_pp_on() && p.splitk <= 1 && p.N % 320 == 0 && p.M >= 64 &&
-                        tile256_blocks(p.M, p.N, 1) < gemm_big_min_blocks() && 2 * tile256_blocks(p.M, p.N, 1) >= gemm_big_min_blocks();
-    if (narrow || (gemm_big_min_blocks() > 0 && tile256_blocks(p.M, p.N, p.splitk) >= gemm_big_min_blocks())) {
-        GemmParams q = p;
-        q.tile_n = narrow ? 160 : 0;
-        const int rc = launch_tile256(Tag::dtype, MODE, &q, s);
-        if (rc < 0) return rc;
-        if (rc == 0) {
-            if (p.splitk > 1) {
-                k_splitk_reduce<Tag><<<mve_cdiv((size_t)p.M * (p.N / 8), 256), 256, 0, s>>>(p);
-                MVE_LAUNCH_CHECK();
-            }
-            return MVE_OK;
-        }
-    }
-    // (round 6) launches too small for either rule above but with a LONG K loop per block: the ping-pong 256 x 160 tile with half the blocks of the
-    // 128-row kernel still wins -- its K step costs ~0.45 us per 32 columns against ~1.6 us per 64 for a 128-row block that runs alone on its CU
-    // (profiles/r06_gemm_lab_ablation.txt), and the fixed costs of a launch stop mattering.  Zero123++'s CFG pair on a 120 x 80 latent lives here
-    // (75-300 blocks of 128 x 160 per conv, K = 2 880 .. 11 520 unsplit or in 2 slices).  Bit-identical like every tile choice.
-    if (gemm_pp_on() && gemm_pp160_min_k() > 0 && p.N % 160 == 0 && p.M >= 128 && p.K / (p.splitk > 1 ? p.splitk : 1) >= gemm_pp160_min_k()) {
-        GemmParams q = p;
-        q.tile_n = 160;
-        const int rc = mve_gemm_pp_launch(Tag::dtype, MODE, &q, s);
-        if (rc < 0) return rc;
-        if (rc == 0) return splitk_reduce_launch<Tag>(p, s);
-    }
-    return launch_v<Tag, MODE>(p, s);
+// The plan of a launch under the process's switches, or the error it stands for.  `s` null: no GPU is touched and the fold counters are taken to be
+// available; else they are obtained where sw.red asks for a fold (their allocation can fail under stream capture: the plan keeps the reducer launch).
+int plan_for(int mode, const GemmParams& p, bool pp_only, const char* who, const hipStream_t* s, GemmPlan* pl, int** sync = nullptr) {
+    const GemmSwitches& sw = gemm_switches();
+    const bool wants_fold = (sw.red & 3) && p.splitk > 1;
+    int* counters = wants_fold && s ? gemm_sk_sync(*s) : nullptr;
+    if (sync) *sync = counters;
+    *pl = gemm_plan(mode, p, sw, s ? counters != nullptr : wants_fold, pp_only);
+    MVE_CHECK(pl->error != GEMM_PLAN_ERR_WINDOW, MVE_ERR_STATE, "%s: 2 x 2 conv windows run on the ping-pong kernel only", who);
+    MVE_CHECK(pl->error != GEMM_PLAN_ERR_PP_ONLY, MVE_ERR_ARG, "%s: the ping-pong kernel does not take M=%d N=%d K=%d (mve_upsample_conv_phases_supported)", who, p.M, p.N, p.K);
+    return MVE_OK;
+}
+
+// mode 0: dense A, 1: conv gather.  plan_out: what was launched (mve_gemm_pair_ln asks whether the LayerNorm went into the launch).
+int run_gemm(int dtype, int mode, const GemmParams& p, bool pp_only, const char* who, void* stream, GemmPlan* plan_out = nullptr) {
+    MVE_CHECK(dtype == MVE_F16 || dtype == MVE_BF16, MVE_ERR_ARG, "%s: unsupported dtype %d", who, dtype);
+    hipStream_t s = (hipStream_t)stream;
+    int* sync = nullptr;
+    GemmPlan local, &pl = plan_out ? *plan_out : local;
+    if (const int rc = plan_for(mode, p, pp_only, who, &s, &pl, &sync)) return rc;
+    const GemmParams q = gemm_plan_params(p, pl, gemm_switches(), sync);
+    if (dtype == MVE_F16) return mode == 0 ? launch_plan<F16Tag, 0>(pl, q, s) : launch_plan<F16Tag, 1>(pl, q, s);
+    return mode == 0 ? launch_plan<BF16Tag, 0>(pl, q, s) : launch_plan<BF16Tag, 1>(pl, q, s);
 }
 
 int check_common(const GemmParams& p, const char* who) {
@@ -840,35 +539,56 @@ int check_common(const GemmParams& p, const char* who) {
     return MVE_OK;
 }
 
-// one K-sliced launch of a phase of mve_upsample_conv_phases: launch_gemm's slice policy on the ping-pong kernel alone
-template <class Tag>
-int launch_phase(GemmParams q, hipStream_t s) {
-    const int minb = gemm_big_min_blocks() > 0 ? gemm_big_min_blocks() : 256;
-    if (q.splitk > 1 && q.N % 320 != 0) q.splitk = 1;         // (only the 320-wide tile cuts K)
-    // (strict mode, MVE_GEMM_STRICT_SPLITK: the rule's slices run as real slices + reducer at any batch -- the path small batches take anyway; the
-    // in-block slice emulation of the 3 x 3 convs is not instantiated for this form)
-    if (q.splitk > 1 && !gemm_strict_splitk()) {
-        const long long t1 = tile256_blocks(q.M, q.N, 1);
-        if (t1 >= minb) q.splitk = 1;                         // the un-split launch fills the chip: one accumulation chain
-        else if (q.splitk > 2 && t1 > 0 && t1 * q.splitk >= 2 * minb) {
-            const int few = (int)((minb + t1 - 1) / t1);
-            q.splitk = few < 2 ? 2 : (few < q.splitk ? few : q.splitk);
-        }
+// K slices of a launch: the rule's count where the caller's workspace holds its partial tiles
+void set_splitk(GemmParams& p, int rows_per_image, int flags, void* workspace, size_t workspace_bytes) {
+    p.splitk = 1;
+    if (workspace && !(flags & MVE_GEMM_NO_SPLITK)) {
+        const int sk = choose_splitk(rows_per_image, p.N, p.K, gemm_switches());
+        if (sk > 1 && workspace_bytes >= (size_t)sk * p.M * p.N * sizeof(float)) { p.splitk = sk; p.partial = (float*)workspace; }
     }
-    if (q.splitk > 1) {
-        const int rr = launch_red(Tag::dtype, 1, q, s);
-        if (rr != 1) return rr;
-    }
-    const int rc = mve_gemm_pp_launch(Tag::dtype, 1, &q, s);
-    if (rc == 1) {
-        mve_set_error("upsample_conv_phases: the ping-pong kernel does not take M=%d N=%d K=%d (mve_upsample_conv_phases_supported)", q.M, q.N, q.K);
-        return MVE_ERR_ARG;
-    }
-    if (rc != MVE_OK) return rc;
-    if (q.splitk > 1) {
-        k_splitk_reduce<Tag><<<mve_cdiv((size_t)q.M * (q.N / 8), 256), 256, 0, s>>>(q);
-        MVE_LAUNCH_CHECK();
-    }
+}
+
+// The parameter fillers of the entry points, shared with mve_gemm_plan_describe.  PARAMS_EMPTY: nothing to launch (the entry returns MVE_OK).
+constexpr int PARAMS_EMPTY = 1;
+
+// All four phases of mve_upsample_conv_phases in ONE launch when the rows of a phase fill whole 256-row tiles (ConvGeom::phase_rows): the phases then
+// share the chip like the tiles of any conv (64 images at the 8 x 8 level: 4 x 64 tiles = one block per CU in a single accumulation chain, instead of
+// four launches of 64 tiles x 4 K slices and four reducers; 8 images per rank: 2 launches instead of 8).  Same arithmetic per output element either
+// way up to the K-slice policy.  MVE_PHASES_ONE_LAUNCH=0: always four launches (A/B).
+bool phases_fused(int B, int Hs, int Ws) { return gemm_switches().phases_one_launch && (B * Hs * Ws) % 256 == 0; }
+
+// launch `ph` of mve_upsample_conv_phases (the only one when fused)
+int phase_params(GemmParams& p, int ph, bool fused, const void* x, int C, int B, int Hs, int Ws, const void* W4, int Cout, void* out, const float* bias,
+                 int flags, void* workspace, size_t workspace_bytes, void* out_lo) {
+    int lw = 0;
+    while ((1 << lw) < Ws) ++lw;
+    const int py = ph >> 1, px = ph & 1;
+    memset(&p, 0, sizeof(p));
+    p.g.Hs = p.g.Hv = p.g.Ho = Hs;
+    p.g.Ws = p.g.Wv = p.g.Wo = Ws;
+    p.g.stride = 1;
+    p.g.kw = 2;
+    p.g.pad = 1 - py; p.g.pad_x = 1 - px;
+    p.g.C1 = C;
+    p.g.chunk64 = 1;
+    p.M = B * Hs * Ws; p.N = Cout; p.K = 4 * C;
+    if (fused) { p.g.phase_rows = p.M; p.M *= 4; }
+    p.A = x;
+    p.W = (const char*)W4 + (size_t)ph * Cout * p.K * 2;
+    const size_t o0 = ((size_t)py * 2 * Ws + px) * Cout * 2;       // bytes: pixel (py, px) of image 0
+    p.out = (char*)out + o0;
+    p.out_lo = out_lo ? (char*)out_lo + o0 / 2 : nullptr;         // (lo8: one byte per element)
+    p.bias = bias;
+    p.ldc = 2 * Cout; p.ldw = p.K;
+    p.orow_shift = lw; p.orow_extra = 2 * Ws * Cout;
+    p.rows_per_vec = Hs * Ws;
+    p.out_scale = 1.0f;
+    int rc = check_common(p, "upsample_conv_phases");
+    if (rc) return rc;
+    // The slice rule sees an image as the 4 Hs Ws rows its four phases put into a launch (whether or not they share one): K = 4 C is short
+    // and the launch is four times an ordinary conv's rows, so the rule stops slicing from the 16 x 16 level up -- and a view gets the same
+    // slices alone or in a batch until the batch fills the chip (tests/test_unet.py::test_engine_sd15_full_size_properties).
+    set_splitk(p, 4 * Hs * Ws, flags, workspace, workspace_bytes);
     return MVE_OK;
 }
 
@@ -894,59 +614,49 @@ __global__ __launch_bounds__(256) void k_pack_phase_weights(const SrcT* __restri
         for (int xx = x0; xx <= x1; ++xx) acc += (float)src[yy * 3 + xx];
     w4[i] = Tag::from_f32(acc);
 }
+// The tune entry points: the whole previous word comes back (threshold + option bits), so that old = tune(x); ...; tune(old) restores every
+// switch; a negative argument only queries.  Bit layouts: GemmSwitches (gemm_dispatch.h).
+template <class Get, class Set>
+int swap_word(int w, Get get, Set set) {
+    GemmSwitches& sw = gemm_switches();
+    const int old = get(sw);
+    if (w >= 0) set(sw, w);
+    return old;
+}
 }  // namespace
 
 extern "C" {
 
-int mve_gemm_tune(int big_min_blocks) {
-    // the whole previous word comes back (threshold + option bits), so that old = tune(x); ...; tune(old) restores every switch
-    const int old = gemm_big_min_blocks() | (g_seq_splitk ? 0 : (1 << 29)) | (gemm_pp_on() ? 0 : (1 << 27)) | (gemm_pp2_mode() == 1 ? (1 << 26) : 0) | (gemm_pp2_mode() == 0 ? (1 << 28) : 0) |
-                    (g_old_swizzle ? (1 << 25) : 0) | (gemm_strict_splitk() ? (1 << 30) : 0);
-    if (big_min_blocks >= 0) {
-        g_strict_splitk = (big_min_blocks >> 30) & 1;
-        g_seq_splitk = (big_min_blocks & (1 << 29)) ? 0 : 1;
-        g_gemm_pp = (big_min_blocks & (1 << 27)) ? 0 : 1;
-        g_gemm_pp2 = (big_min_blocks & (1 << 26)) ? 1 : ((big_min_blocks & (1 << 28)) ? 0 : 2);
-        g_old_swizzle = (big_min_blocks >> 25) & 1;
-        mve_gemm_pp_old_swizzle(g_old_swizzle);
-        g_big_min_blocks = big_min_blocks & ~((7 << 28) | (1 << 27) | (1 << 26) | (1 << 25));       // (7 << 28): bits 28, 29 and 30
-    }
-    return old;
+int mve_gemm_tune(int big_min_blocks) { return swap_word(big_min_blocks, [](GemmSwitches& s) { return s.tune_word(); }, [](GemmSwitches& s, int w) { s.set_tune_word(w); }); }
+int mve_gemm_deep_tune(int max_blocks) { return swap_word(max_blocks, [](GemmSwitches& s) { return s.deep_tune_word(); }, [](GemmSwitches& s, int w) { s.set_deep_tune_word(w); }); }
+int mve_gemm_red_tune(int on) { return swap_word(on, [](GemmSwitches& s) { return s.red; }, [](GemmSwitches& s, int w) { s.red = w & GemmSwitches::RED_TUNE_MASK; }); }
+// -> previous setting (the environment default resolved)
+int mve_gemm_ln_fuse_tune(int on) { return swap_word(on, [](GemmSwitches& s) { return (int)(s.ln_fuse != 0); }, [](GemmSwitches& s, int w) { s.ln_fuse = w ? 1 : 0; }); }
+/* 1 (default; MVE_PHASES_ONE_LAUNCH): the four phases run as one launch where a phase fills whole tiles; 0: always four launches.  Negative: query.
+ * Returns the previous value. */
+int mve_upsample_conv_phases_tune(int one_launch) {
+    return swap_word(one_launch, [](GemmSwitches& s) { return s.phases_one_launch; }, [](GemmSwitches& s, int w) { s.phases_one_launch = w ? 1 : 0; });
 }
 
-int mve_gemm_deep_tune(int max_blocks) {
-    const int old = gemm_deep_max_blocks() | (gemm_w_major_on() ? 0 : (1 << 30));
-    if (max_blocks >= 0) { g_gemm_deep = max_blocks & ~(1 << 30); g_w_major = (max_blocks & (1 << 30)) ? 0 : 1; }
-    return old;
-}
-
-int mve_gemm_red_tune(int on) {
-    const int old = gemm_red_mode();
-    if (on >= 0) g_gemm_red = on & 3;
-    return old;
-}
-
-/* The number of K slices a launch of this shape actually runs with under the current switches (diagnostics / tests; no GPU touched): the slice
- * rule's count (choose_splitk: a function of rows per image, N, K only), 1 where the un-split launch fills the chip (one accumulation chain;
- * the strict mode emulates the rule's slices inside one block instead: reported as the rule's count), or the smallest count that fills the
- * chip where the rule would over-fill it. */
+/* The number of K slices a launch of this shape actually runs with under the current switches (diagnostics / tests; no GPU touched): the plan of a
+ * dense launch of this shape with a workspace -- the slice rule's count (choose_splitk: a function of rows per image, N, K only), 1 where the
+ * un-split launch fills the chip (one accumulation chain; the strict mode emulates the rule's slices inside one block instead: reported as the
+ * rule's count), or the smallest count that fills the chip where the rule would over-fill it. */
 int mve_gemm_effective_splitk(int M, int N, int K, int rows_per_image) {
     if (M <= 0 || N <= 0 || K <= 0) return 1;
-    const int sk = choose_splitk(rows_per_image, N, K);
-    if (sk <= 1 || tile256_bn(N, sk) == 0 || gemm_big_min_blocks() <= 0 || N % 320 != 0) return sk < 1 ? 1 : sk;
-    const long long t1 = tile256_blocks(M, N, 1);
-    if (g_seq_splitk && t1 >= gemm_big_min_blocks() && (size_t)t1 * 256 * 320 <= (size_t)sk * M * N) return gemm_strict_splitk() ? sk : 1;
-    if (!gemm_strict_splitk() && sk > 2 && t1 > 0 && t1 * sk >= 2 * gemm_big_min_blocks()) {
-        int few = (int)((gemm_big_min_blocks() + t1 - 1) / t1);
-        few = few < 2 ? 2 : few;
-        return few < sk ? few : sk;
-    }
-    return sk;
+    GemmParams p;
+    memset(&p, 0, sizeof(p));
+    p.M = M; p.N = N; p.K = K; p.lda = p.ldw = K; p.ldc = N;
+    p.out_scale = 1.0f;
+    p.splitk = choose_splitk(rows_per_image, N, K, gemm_switches());
+    GemmPlan pl;
+    if (plan_for(0, p, false, "gemm_effective_splitk", nullptr, &pl)) return p.splitk;
+    return pl.splitk_seq > 1 ? pl.splitk_seq : pl.splitk;
 }
 
 size_t mve_gemm_workspace_bytes(int M, int N, int K, int rows_per_image) {
     if (M <= 0 || N <= 0 || K <= 0) return 0;
-    const int sk = choose_splitk(rows_per_image, N, K);
+    const int sk = choose_splitk(rows_per_image, N, K, gemm_switches());
     return sk > 1 ? (size_t)sk * M * N * sizeof(float) : 0;
 }
 
@@ -957,45 +667,47 @@ int mve_gemm(int dtype, const void* A, int lda, const void* W, int ldw, void* ou
                          workspace_bytes, rows_per_image, nullptr, nullptr, stream);
 }
 
-static int gemm_pair_impl(int dtype, const void* A, int lda, const void* W, int ldw, void* out, int ldc, int M, int N, int K,
-                          const float* bias, const float* rowvec, int ldrv, int rows_per_vec, const void* residual, int ldr, int flags,
-                          float out_scale, void* workspace, size_t workspace_bytes, int rows_per_image, const void* residual_lo, void* out_lo,
-                          void* stream, void* ln_out, int ld_ln, const float* ln_gamma, const float* ln_beta, float ln_eps);
+static int dense_params(GemmParams& p, const void* A, int lda, const void* W, int ldw, void* out, int ldc, int M, int N, int K, const float* bias,
+                 const float* rowvec, int ldrv, int rows_per_vec, const void* residual, int ldr, int flags, float out_scale, void* workspace,
+                 size_t workspace_bytes, int rows_per_image, const void* residual_lo, void* out_lo, void* ln_out, int ld_ln, const float* ln_gamma,
+                 const float* ln_beta, float ln_eps);
 
 int mve_gemm_pair(int dtype, const void* A, int lda, const void* W, int ldw, void* out, int ldc, int M, int N, int K,
                   const float* bias, const float* rowvec, int ldrv, int rows_per_vec, const void* residual, int ldr, int flags,
                   float out_scale, void* workspace, size_t workspace_bytes, int rows_per_image, const void* residual_lo, void* out_lo,
                   void* stream) {
-    return gemm_pair_impl(dtype, A, lda, W, ldw, out, ldc, M, N, K, bias, rowvec, ldrv, rows_per_vec, residual, ldr, flags, out_scale, workspace,
-                          workspace_bytes, rows_per_image, residual_lo, out_lo, stream, nullptr, 0, nullptr, nullptr, 0.f);
+    GemmParams p;
+    const int rc = dense_params(p, A, lda, W, ldw, out, ldc, M, N, K, bias, rowvec, ldrv, rows_per_vec, residual, ldr, flags, out_scale, workspace,
+                                workspace_bytes, rows_per_image, residual_lo, out_lo, nullptr, 0, nullptr, nullptr, 0.f);
+    if (rc) return rc == PARAMS_EMPTY ? MVE_OK : rc;
+    return run_gemm(dtype, 0, p, false, "gemm", stream);
 }
 
 /* mve_gemm_pair followed by LayerNorm of the output rows: d_ln_out[m] = LayerNorm(out[m]) * gamma + beta over the N columns, where out[m] is the row
  * as a consumer reads it back (hi + lo8 when d_out_lo is given, the 16-bit row otherwise).  Where the launch runs on the 320-wide pair tile
  * (N = 320, whole 256-row tiles, bias, no K slices: the residual-stream GEMMs of the 64 x 64 level from 16 images up) the tile that produces a row
- * normalises it in its epilogue -- the row never comes back from HBM for its LayerNorm; every other launch is followed by the LayerNorm kernel.
- * Same row arithmetic either way (csrc/ln_core.h): bit-identical.  (BasicTransformerBlock: norm1 / norm2 / norm3 behind proj_in / attn1.to_out /
- * attn2.to_out, diffusers 0.27.2 as driven from lib/models/architecture/diffusers.py:69-97.) */
+ * normalises it in its epilogue (plan epilogue LNF) -- the row never comes back from HBM for its LayerNorm; every other launch is followed by the
+ * LayerNorm kernel.  Same row arithmetic either way (csrc/ln_core.h): bit-identical.  (BasicTransformerBlock: norm1 / norm2 / norm3 behind proj_in /
+ * attn1.to_out / attn2.to_out, diffusers 0.27.2 as driven from lib/models/architecture/diffusers.py:69-97.) */
 int mve_gemm_pair_ln(int dtype, const void* A, int lda, const void* W, int ldw, void* out, int ldc, int M, int N, int K,
                      const float* bias, const void* residual, int ldr, void* workspace, size_t workspace_bytes, int rows_per_image,
                      const void* residual_lo, void* out_lo, void* ln_out, int ld_ln, const float* ln_gamma, const float* ln_beta, float ln_eps,
                      void* stream) {
     MVE_CHECK(ln_out && ln_gamma && ln_beta && ld_ln >= N && ld_ln % 8 == 0, MVE_ERR_ARG, "gemm_pair_ln: LayerNorm output / parameters missing or ld_ln (%d) bad", ld_ln);
-    (void)mve_gemm_pp_ln_fused();                 // clear a stale flag
-    const int rc = gemm_pair_impl(dtype, A, lda, W, ldw, out, ldc, M, N, K, bias, nullptr, 0, 0, residual, ldr, 0, 1.0f, workspace, workspace_bytes,
-                                  rows_per_image, residual_lo, out_lo, stream, ln_out, ld_ln, ln_gamma, ln_beta, ln_eps);
-    if (rc != MVE_OK || M == 0) return rc;
-    if (mve_gemm_pp_ln_fused()) return MVE_OK;
+    GemmParams p;
+    int rc = dense_params(p, A, lda, W, ldw, out, ldc, M, N, K, bias, nullptr, 0, 0, residual, ldr, 0, 1.0f, workspace, workspace_bytes, rows_per_image,
+                          residual_lo, out_lo, ln_out, ld_ln, ln_gamma, ln_beta, ln_eps);
+    if (rc) return rc == PARAMS_EMPTY ? MVE_OK : rc;
+    GemmPlan pl;
+    rc = run_gemm(dtype, 0, p, false, "gemm", stream, &pl);
+    if (rc != MVE_OK || pl.epilogue == GEMM_EPI_LNF) return rc;
     return mve_layernorm_pair(dtype, out, ldc, ln_out, ld_ln, M, N, ln_gamma, ln_beta, ln_eps, out_lo, stream);
 }
 
-int mve_gemm_ln_fuse_tune(int on) { return mve_gemm_pp_ln_fuse_tune(on); }
-
-static int gemm_pair_impl(int dtype, const void* A, int lda, const void* W, int ldw, void* out, int ldc, int M, int N, int K,
-                          const float* bias, const float* rowvec, int ldrv, int rows_per_vec, const void* residual, int ldr, int flags,
-                          float out_scale, void* workspace, size_t workspace_bytes, int rows_per_image, const void* residual_lo, void* out_lo,
-                          void* stream, void* ln_out, int ld_ln, const float* ln_gamma, const float* ln_beta, float ln_eps) {
-    GemmParams p;
+static int dense_params(GemmParams& p, const void* A, int lda, const void* W, int ldw, void* out, int ldc, int M, int N, int K, const float* bias,
+                 const float* rowvec, int ldrv, int rows_per_vec, const void* residual, int ldr, int flags, float out_scale, void* workspace,
+                 size_t workspace_bytes, int rows_per_image, const void* residual_lo, void* out_lo, void* ln_out, int ld_ln, const float* ln_gamma,
+                 const float* ln_beta, float ln_eps) {
     memset(&p, 0, sizeof(p));
     p.ln_out = ln_out; p.ld_ln = ld_ln; p.ln_gamma = ln_gamma; p.ln_beta = ln_beta; p.ln_eps = ln_eps;
     p.A = A; p.W = W; p.out = out; p.bias = bias; p.rowvec = rowvec; p.residual = residual;
@@ -1006,38 +718,30 @@ static int gemm_pair_impl(int dtype, const void* A, int lda, const void* W, int 
     p.out_f32 = (flags & MVE_GEMM_OUT_F32) ? 1 : 0;
     p.out_scale = out_scale;
     p.res_after_scale = (flags & MVE_GEMM_RES_AFTER_SCALE) ? 1 : 0;
-    if (M == 0) return MVE_OK;
+    if (M == 0) return PARAMS_EMPTY;
     int rc = check_common(p, "gemm");
     if (rc) return rc;
     MVE_CHECK(A && lda % 8 == 0 && lda >= K, MVE_ERR_ARG, "gemm: bad A/lda (%d)", lda);
-    p.w_major = gemm_w_major_on() && M < N;       // fewer activation rows than weight rows: walk the row panels inside a weight strip (GemmParams::w_major)
+    p.w_major = gemm_switches().w_major && M < N;       // fewer activation rows than weight rows: walk the row panels inside a weight strip (GemmParams::w_major)
     if (const int* skip = mve_skip_second_half()) {
         MVE_CHECK(M % 2 == 0, MVE_ERR_ARG, "gemm: the second-half predicate needs an even number of rows (M=%d)", M);
         p.skip_if = skip; p.skip_from = M / 2; p.w_major = 0;
     }
-    p.splitk = 1;
-    if (workspace && !(flags & MVE_GEMM_NO_SPLITK)) {
-        const int sk = choose_splitk(rows_per_image, N, K);
-        if (sk > 1 && workspace_bytes >= (size_t)sk * M * N * sizeof(float)) { p.splitk = sk; p.partial = (float*)workspace; }
-    }
-    if (dtype == MVE_F16) return launch_gemm<F16Tag, 0>(p, (hipStream_t)stream);
-    if (dtype == MVE_BF16) return launch_gemm<BF16Tag, 0>(p, (hipStream_t)stream);
-    mve_set_error("gemm: unsupported dtype %d", dtype);
-    return MVE_ERR_ARG;
+    set_splitk(p, rows_per_image, flags, workspace, workspace_bytes);
+    return MVE_OK;
 }
 
-static int conv3x3_impl(int dtype, const void* x1, int C1, const void* x2, int C2, const void* x3, int C3, const void* x4, int C4, int B,
-                        int Hs, int Ws, int stride, int upsample, const void* W, int Cout, void* out, int ldc, const float* bias,
-                        const float* rowvec, int ldrv, const void* residual, int ldr, int flags, float out_scale, void* workspace,
-                        size_t workspace_bytes, void* stream, const void* residual_lo = nullptr, void* out_lo = nullptr) {
-    GemmParams p;
+static int conv3x3_params(GemmParams& p, const void* x1, int C1, const void* x2, int C2, const void* x3, int C3, const void* x4, int C4, int B,
+                   int Hs, int Ws, int stride, int upsample, const void* W, int Cout, void* out, int ldc, const float* bias,
+                   const float* rowvec, int ldrv, const void* residual, int ldr, int flags, float out_scale, void* workspace,
+                   size_t workspace_bytes, const void* residual_lo, void* out_lo) {
     memset(&p, 0, sizeof(p));
     MVE_CHECK(stride == 1 || stride == 2, MVE_ERR_ARG, "conv3x3: stride must be 1 or 2");
     MVE_CHECK(!(upsample && stride != 1), MVE_ERR_ARG, "conv3x3: upsample requires stride 1");
     MVE_CHECK(C1 > 0 && C1 % 8 == 0 && C2 >= 0 && C2 % 8 == 0, MVE_ERR_ARG,
               "conv3x3: channel counts must be multiples of 8 (C1=%d C2=%d)", C1, C2);
     MVE_CHECK(x1 && (C2 == 0 || x2), MVE_ERR_ARG, "conv3x3: null input");
-    if (B == 0) return MVE_OK;
+    if (B == 0) return PARAMS_EMPTY;
     p.g.Hs = Hs; p.g.Ws = Ws;
     p.g.ups = upsample ? 1 : 0;
     p.g.Hv = Hs << p.g.ups; p.g.Wv = Ws << p.g.ups;
@@ -1070,20 +774,24 @@ static int conv3x3_impl(int dtype, const void* x1, int C1, const void* x2, int C
     p.res_after_scale = (flags & MVE_GEMM_RES_AFTER_SCALE) ? 1 : 0;
     int rc = check_common(p, "conv3x3");
     if (rc) return rc;
-    p.w_major = gemm_w_major_on() && (long long)p.M * (C1 + C2) < (long long)p.N * p.K;      // activation tensor smaller than the weights (GemmParams::w_major)
+    p.w_major = gemm_switches().w_major && (long long)p.M * (C1 + C2) < (long long)p.N * p.K;      // activation tensor smaller than the weights (GemmParams::w_major)
     if (const int* skip = mve_skip_second_half()) {
         MVE_CHECK(B % 2 == 0, MVE_ERR_ARG, "conv3x3: the second-half predicate needs an even batch (B=%d)", B);
         p.skip_if = skip; p.skip_from = p.M / 2; p.w_major = 0;
     }
-    p.splitk = 1;
-    if (workspace && !(flags & MVE_GEMM_NO_SPLITK)) {
-        const int sk = choose_splitk(p.g.Ho * p.g.Wo, p.N, p.K);
-        if (sk > 1 && workspace_bytes >= (size_t)sk * p.M * p.N * sizeof(float)) { p.splitk = sk; p.partial = (float*)workspace; }
-    }
-    if (dtype == MVE_F16) return launch_gemm<F16Tag, 1>(p, (hipStream_t)stream);
-    if (dtype == MVE_BF16) return launch_gemm<BF16Tag, 1>(p, (hipStream_t)stream);
-    mve_set_error("conv3x3: unsupported dtype %d", dtype);
-    return MVE_ERR_ARG;
+    set_splitk(p, p.g.Ho * p.g.Wo, flags, workspace, workspace_bytes);
+    return MVE_OK;
+}
+
+static int conv3x3_impl(int dtype, const void* x1, int C1, const void* x2, int C2, const void* x3, int C3, const void* x4, int C4, int B,
+                        int Hs, int Ws, int stride, int upsample, const void* W, int Cout, void* out, int ldc, const float* bias,
+                        const float* rowvec, int ldrv, const void* residual, int ldr, int flags, float out_scale, void* workspace,
+                        size_t workspace_bytes, void* stream, const void* residual_lo = nullptr, void* out_lo = nullptr) {
+    GemmParams p;
+    const int rc = conv3x3_params(p, x1, C1, x2, C2, x3, C3, x4, C4, B, Hs, Ws, stride, upsample, W, Cout, out, ldc, bias, rowvec, ldrv, residual, ldr,
+                                  flags, out_scale, workspace, workspace_bytes, residual_lo, out_lo);
+    if (rc) return rc == PARAMS_EMPTY ? MVE_OK : rc;
+    return run_gemm(dtype, 1, p, false, "conv3x3", stream);
 }
 
 int mve_conv3x3(int dtype, const void* x1, int C1, const void* x2, int C2, int B, int Hs, int Ws, int stride,
@@ -1109,7 +817,7 @@ int mve_conv3x3_pair(int dtype, const void* x1, int C1, const void* x2, int C2, 
  * rounding to the storage type -- a rounding the 3 x 3 form does not have: the two forms agree to the storage precision of the weights, not bit
  * for bit).  A phase is a launch of the ping-pong kernel with a 2 x 2 window (ConvGeom::kw) that writes its quarter of the [B][2H][2W][Cout]
  * output through the grouped output rows of GemmParams::orow_*; where a phase fills whole 256-row tiles the four phases are ONE launch
- * (ConvGeom::phase_rows).  K slices: launch_gemm's policy with the image's 4 Hs Ws rows as the rule's rows per image. */
+ * (ConvGeom::phase_rows).  K slices: gemm_plan's policy (gemm_dispatch.h) with the image's 4 Hs Ws rows as the rule's rows per image. */
 
 int mve_pack_upsample_phase_weights(int src_dtype, int dst_dtype, const void* w_oihw, int Cout, int C, void* W4, void* stream) {
     MVE_CHECK(w_oihw && W4 && Cout > 0 && C > 0 && C % 64 == 0, MVE_ERR_ARG, "pack_upsample_phase_weights: needs C %% 64 == 0 (Cout=%d C=%d)", Cout, C);
@@ -1132,23 +840,13 @@ int mve_pack_upsample_phase_weights(int src_dtype, int dst_dtype, const void* w_
 int mve_upsample_conv_phases_supported(int C, int Cout, int B, int Hs, int Ws) {
     if (C <= 0 || C % 64 != 0 || Cout <= 0 || B <= 0 || Hs <= 0 || Ws <= 0 || (Ws & (Ws - 1)) != 0) return 0;
     if (Cout % 320 != 0 && Cout % 256 != 0 && Cout % 128 != 0) return 0;
-    if (!gemm_pp_on() || (long long)B * Hs * Ws < 64 || (long long)B * Hs * Ws > 0x7fffffffll / 4) return 0;
+    if (!gemm_switches().pp || (long long)B * Hs * Ws < 64 || (long long)B * Hs * Ws > 0x7fffffffll / 4) return 0;
     // the ping-pong kernel addresses its source and its weights through 32-bit buffer offsets (gemm_pp.hip: pp_fits / pp_eligible): a larger
     // launch (a VAE decode of >= 128 images at the 256-channel upsampler) keeps the 3 x 3 form, which falls back to the other 256-row loops
     const unsigned long long lim = 0xFFFFFF00ull - 65536ull;
     if (((unsigned long long)B * Hs * Ws + 2ull * Ws + 4) * (unsigned long long)C * 2 >= lim) return 0;
     if ((unsigned long long)Cout * 4 * C * 2 >= lim) return 0;
     return 1;
-}
-
-/* 1 (default; MVE_PHASES_ONE_LAUNCH): the four phases run as one launch where a phase fills whole tiles; 0: always four launches.  Negative: query.
- * Returns the previous value. */
-int mve_upsample_conv_phases_tune(int one_launch) {
-    static int cur = -1;
-    if (cur < 0) { const char* e = getenv("MVE_PHASES_ONE_LAUNCH"); cur = e ? (atoi(e) != 0) : 1; }
-    const int old = cur;
-    if (one_launch >= 0) cur = one_launch ? 1 : 0;
-    return old;
 }
 
 size_t mve_upsample_conv_phases_workspace_bytes(int C, int Cout, int B, int Hs, int Ws) {
@@ -1163,47 +861,12 @@ int mve_upsample_conv_phases(int dtype, const void* x, int C, int B, int Hs, int
               C, Cout, B, Hs, Ws);
     MVE_CHECK(x && W4 && out, MVE_ERR_ARG, "upsample_conv_phases: null pointer");
     MVE_CHECK(dtype == MVE_F16 || dtype == MVE_BF16, MVE_ERR_ARG, "upsample_conv_phases: unsupported dtype %d", dtype);
-    int lw = 0;
-    while ((1 << lw) < Ws) ++lw;
-    // All four phases in ONE launch when the rows of a phase fill whole 256-row tiles (ConvGeom::phase_rows): the phases then share the chip
-    // like the tiles of any conv (64 images at the 8 x 8 level: 4 x 64 tiles = one block per CU in a single accumulation chain, instead of four
-    // launches of 64 tiles x 4 K slices and four reducers; 8 images per rank: 2 launches instead of 8).  Same arithmetic per output element either
-    // way up to the K-slice policy.  MVE_PHASES_ONE_LAUNCH=0: always four launches (A/B).
-    const bool fused = mve_upsample_conv_phases_tune(-1) && (B * Hs * Ws) % 256 == 0;
+    const bool fused = phases_fused(B, Hs, Ws);
     for (int ph = 0; ph < (fused ? 1 : 4); ++ph) {
-        const int py = ph >> 1, px = ph & 1;
         GemmParams p;
-        memset(&p, 0, sizeof(p));
-        p.g.Hs = p.g.Hv = p.g.Ho = Hs;
-        p.g.Ws = p.g.Wv = p.g.Wo = Ws;
-        p.g.stride = 1;
-        p.g.kw = 2;
-        p.g.pad = 1 - py; p.g.pad_x = 1 - px;
-        p.g.C1 = C;
-        p.g.chunk64 = 1;
-        p.M = B * Hs * Ws; p.N = Cout; p.K = 4 * C;
-        if (fused) { p.g.phase_rows = p.M; p.M *= 4; }
-        p.A = x;
-        p.W = (const char*)W4 + (size_t)ph * Cout * p.K * 2;
-        const size_t o0 = ((size_t)py * 2 * Ws + px) * Cout * 2;       // bytes: pixel (py, px) of image 0
-        p.out = (char*)out + o0;
-        p.out_lo = out_lo ? (char*)out_lo + o0 / 2 : nullptr;         // (lo8: one byte per element)
-        p.bias = bias;
-        p.ldc = 2 * Cout; p.ldw = p.K;
-        p.orow_shift = lw; p.orow_extra = 2 * Ws * Cout;
-        p.rows_per_vec = Hs * Ws;
-        p.out_scale = 1.0f;
-        int rc = check_common(p, "upsample_conv_phases");
+        int rc = phase_params(p, ph, fused, x, C, B, Hs, Ws, W4, Cout, out, bias, flags, workspace, workspace_bytes, out_lo);
         if (rc) return rc;
-        p.splitk = 1;
-        if (workspace && !(flags & MVE_GEMM_NO_SPLITK)) {
-            // The slice rule sees an image as the 4 Hs Ws rows its four phases put into a launch (whether or not they share one): K = 4 C is short
-            // and the launch is four times an ordinary conv's rows, so the rule stops slicing from the 16 x 16 level up -- and a view gets the same
-            // slices alone or in a batch until the batch fills the chip (tests/test_unet.py::test_engine_sd15_full_size_properties).
-            const int sk = choose_splitk(4 * Hs * Ws, p.N, p.K);
-            if (sk > 1 && workspace_bytes >= (size_t)sk * p.M * p.N * sizeof(float)) { p.splitk = sk; p.partial = (float*)workspace; }
-        }
-        rc = dtype == MVE_F16 ? launch_phase<F16Tag>(p, (hipStream_t)stream) : launch_phase<BF16Tag>(p, (hipStream_t)stream);
+        rc = run_gemm(dtype, 1, p, true, "upsample_conv_phases", stream);      // pp_only: a 2 x 2 window exists on the ping-pong kernel alone
         if (rc) return rc;
     }
     return MVE_OK;
@@ -1224,6 +887,40 @@ int mve_conv3x3_shortcut(int dtype, const void* x1, int C1, const void* x3, int 
     // bias2 (the shortcut's bias) rides in the per-image row-vector slot with a zero stride: every row adds the same vector
     return conv3x3_impl(dtype, x1, C1, nullptr, 0, x3, C3, x4, C4, B, Hs, Ws, 1, 0, W, Cout, out, ldc, bias, bias2, 0, residual, ldr,
                         flags | MVE_CONV_W_CHUNK64, out_scale, workspace, workspace_bytes, stream);
+}
+
+int mve_gemm_plan_describe(int kind, int M, int N, int K, int rows_per_image, int flags, int features, const int* conv_geom, int* out) {
+    MVE_CHECK(out && kind >= 0 && kind <= 2 && (kind == 0 || conv_geom), MVE_ERR_ARG, "gemm_plan_describe: kind 0 | 1 | 2, conv_geom for kinds 1 and 2, out required");
+    // stand-ins for the buffers: the plan reads which pointers are present, never what they point to
+    static float buf[4];
+    auto have = [&](int bit) -> float* { return (features & bit) ? buf : nullptr; };
+    float *const bias = have(MVE_PLAN_BIAS), *const rowvec = have(MVE_PLAN_ROWVEC), *const residual = have(MVE_PLAN_RESIDUAL), *const residual_lo = have(MVE_PLAN_RESIDUAL_LO);
+    float *const out_lo = have(MVE_PLAN_OUT_LO), *const ln = have(MVE_PLAN_LN), *const ws = have(MVE_PLAN_WORKSPACE);
+    const float scale = (features & MVE_PLAN_SCALED) ? 0.5f : 1.0f;
+    GemmParams p;
+    int rc, launches = 1;
+    if (kind == 0) {
+        rc = dense_params(p, buf, K, buf, K, buf, (flags & MVE_GEMM_GEGLU) ? N / 2 : N, M, N, K, bias, rowvec, rowvec ? N : 0, rowvec ? (rows_per_image > 0 ? rows_per_image : M) : 0,
+                          residual, N, flags, scale, ws, (size_t)-1, rows_per_image, residual_lo, out_lo, ln, N, ln, ln, 1e-5f);
+    } else if (kind == 1) {
+        const int* g = conv_geom;      // {C1, C2, C3, C4, B, Hs, Ws, stride, upsample}
+        rc = conv3x3_params(p, buf, g[0], g[1] > 0 ? buf : nullptr, g[1], g[2] > 0 ? buf : nullptr, g[2], g[3] > 0 ? buf : nullptr, g[3], g[4], g[5], g[6], g[7], g[8],
+                            buf, N, buf, N, bias, rowvec, (g[2] > 0 || !rowvec) ? 0 : N, residual, N, flags | (g[2] > 0 ? MVE_CONV_W_CHUNK64 : 0), scale, ws, (size_t)-1,
+                            residual_lo, out_lo);
+    } else {
+        const int* g = conv_geom;      // {C, 0, 0, 0, B, Hs, Ws}
+        MVE_CHECK(mve_upsample_conv_phases_supported(g[0], N, g[4], g[5], g[6]), MVE_ERR_ARG, "gemm_plan_describe: shape not supported by mve_upsample_conv_phases");
+        const bool fused = phases_fused(g[4], g[5], g[6]);
+        launches = fused ? 1 : 4;
+        rc = phase_params(p, 0, fused, buf, g[0], g[4], g[5], g[6], buf, N, buf, bias, flags, ws, (size_t)-1, out_lo);
+    }
+    MVE_CHECK(rc != PARAMS_EMPTY, MVE_ERR_ARG, "gemm_plan_describe: empty problem");
+    if (rc) return rc;
+    GemmPlan pl;
+    if ((rc = plan_for(kind == 0 ? 0 : 1, p, kind == 2, "gemm_plan_describe", nullptr, &pl))) return rc;
+    const int v[MVE_PLAN_DESCRIBE_INTS] = {pl.family, pl.tile_n, pl.tile_m, pl.ring, pl.epilogue, pl.splitk, pl.splitk_seq, pl.reducer, pl.w_major, (int)pl.grid, launches, p.M};
+    memcpy(out, v, sizeof(v));
+    return MVE_OK;
 }
 
 }  // extern "C"

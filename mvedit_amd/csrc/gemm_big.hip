@@ -11,6 +11,7 @@
 // kernels produce bit-identical results and the dispatcher may pick either by problem size without breaking batch invariance.
 #include "common.h"
 
+#include "gemm_dispatch.h"
 #include "gemm_shared.h"
 #include "gemm_big_epilogue.h"
 
@@ -230,54 +231,31 @@ __global__ __launch_bounds__(NTH, 2) void k_gemm_big(const GemmParams p) {
     big_tile_epilogue<Tag, BN2>(p, acc, smem, m0, n0, kslice, tid, lane, wm, wn);
 }
 
-int big_bn(int N) { return N % 320 == 0 ? 320 : (N % 256 == 0 ? 256 : 0); }
-
-template <class Tag, int MODE, bool SEQ, bool FAST, int BN2>
-int launch_big3(const GemmParams& p, hipStream_t s) {
-    static bool configured[64] = {};             // the attribute is per device; one process may drive several
-    int dev = 0;
-    MVE_HIP(hipGetDevice(&dev));
-    if (dev >= 0 && dev < 64 && !configured[dev]) {
-        MVE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_big<Tag, MODE, SEQ, FAST, BN2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    smem_big(BN2)));
-        configured[dev] = true;
-    }
-    const unsigned grid = (unsigned)mve_cdiv(p.M, BM2) * (unsigned)mve_cdiv(p.N, BN2) * (unsigned)(p.splitk > 1 ? p.splitk : 1);
-    k_gemm_big<Tag, MODE, SEQ, FAST, BN2><<<grid, NTH, smem_big(BN2), s>>>(p);
-    MVE_LAUNCH_CHECK();
-    return MVE_OK;
-}
 template <class Tag, int MODE, bool SEQ, int BN2>
-int launch_big2(const GemmParams& p, hipStream_t s) {
-    if constexpr (MODE == 1) {
-        if (p.g.chunk64) return launch_big3<Tag, MODE, SEQ, true, BN2>(p, s);
+int launch_big2(const GemmPlan& pl, const GemmParams& p, hipStream_t s) {
+    if constexpr (MODE == 1) {      // FAST: slab-major K order
+        if (p.g.chunk64) return mve_launch_dyn_lds<&k_gemm_big<Tag, MODE, SEQ, true, BN2>>(pl.grid, NTH, smem_big(BN2), s, p);
     }
-    return launch_big3<Tag, MODE, SEQ, false, BN2>(p, s);
+    return mve_launch_dyn_lds<&k_gemm_big<Tag, MODE, SEQ, false, BN2>>(pl.grid, NTH, smem_big(BN2), s, p);
 }
 template <class Tag, int MODE>
-int launch_big(const GemmParams& p, hipStream_t s) {
-    if (big_bn(p.N) == 256) {      // no split-K variants of the 256-wide tile (mve_gemm_big_blocks reports such shapes as not eligible)
-        MVE_CHECK(p.splitk <= 1 && p.splitk_seq <= 1, MVE_ERR_ARG, "gemm_big: the 256-wide tile does not split K");
-        return launch_big2<Tag, MODE, false, 256>(p, s);
-    }
-    return p.splitk_seq > 1 ? launch_big2<Tag, MODE, true, 320>(p, s) : launch_big2<Tag, MODE, false, 320>(p, s);
+int launch_big(const GemmPlan& pl, const GemmParams& p, hipStream_t s) {
+    const bool seq = pl.epilogue == GEMM_EPI_SEQ;
+    MVE_CHECK(pl.family == GEMM_BIG && pl.tile_m == BM2 && (seq || pl.epilogue == GEMM_EPI_PLAIN) && (pl.tile_n == 320 || (pl.tile_n == 256 && !seq && pl.splitk <= 1)),
+              MVE_ERR_STATE, "gemm_big: no kernel for the plan (family %d, tile %d x %d, epilogue %d, splitk %d)", pl.family, pl.tile_m, pl.tile_n, pl.epilogue, pl.splitk);      // (no split-K variants of the 256-wide tile)
+    if (pl.tile_n == 256) return launch_big2<Tag, MODE, false, 256>(pl, p, s);
+    return seq ? launch_big2<Tag, MODE, true, 320>(pl, p, s) : launch_big2<Tag, MODE, false, 320>(pl, p, s);
 }
 
 }  // namespace
 
-// number of blocks the 256 x 320 kernel would launch (0: shape not eligible)
-long long mve_gemm_big_blocks(int M, int N, int splitk) {
-    const int bn = big_bn(N);
-    if (bn == 0 || M < 64 || (bn == 256 && splitk > 1)) return 0;
-    return (long long)mve_cdiv(M, BM2) * (N / bn) * (splitk > 1 ? splitk : 1);
-}
-
 // main loop + epilogue (or split-K partials; the caller runs the reducer)
-int mve_gemm_big_launch(int dtype, int mode, const void* params, void* stream) {
+int mve_gemm_big_launch(int dtype, int mode, const void* plan, const void* params, void* stream) {
+    const GemmPlan& pl = *reinterpret_cast<const GemmPlan*>(plan);
     const GemmParams& p = *reinterpret_cast<const GemmParams*>(params);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == MVE_F16) return mode == 0 ? launch_big<F16Tag, 0>(p, s) : launch_big<F16Tag, 1>(p, s);
-    if (dtype == MVE_BF16) return mode == 0 ? launch_big<BF16Tag, 0>(p, s) : launch_big<BF16Tag, 1>(p, s);
+    if (dtype == MVE_F16) return mode == 0 ? launch_big<F16Tag, 0>(pl, p, s) : launch_big<F16Tag, 1>(pl, p, s);
+    if (dtype == MVE_BF16) return mode == 0 ? launch_big<BF16Tag, 0>(pl, p, s) : launch_big<BF16Tag, 1>(pl, p, s);
     mve_set_error("gemm_big: unsupported dtype %d", dtype);
     return MVE_ERR_ARG;
 }

@@ -39,6 +39,7 @@
 
 #include <type_traits>
 
+#include "gemm_dispatch.h"
 #include "gemm_shared.h"
 #include "gemm_big_epilogue.h"
 
@@ -51,6 +52,7 @@ constexpr int PROWB = 64;                               // bytes per row and K s
 constexpr int PNSLOT = 4;
 constexpr int P_A_SLOT = PBM * PROWB;                   // 16 KiB
 constexpr unsigned P_NUMREC = 0xFFFFFF00u;              // resource size: every valid offset is below it, the all-ones halo offset above
+static_assert(P_NUMREC == PP_NUMREC, "pp_fits (gemm_dispatch.h) guards the offsets of this resource size");
 constexpr int pp_slot_bytes(int bn) { return P_A_SLOT + bn * PROWB; }
 constexpr int pp_smem(int bn, int nsl = PNSLOT) { return nsl * pp_slot_bytes(bn) + (bn == 160 ? 1024 : 0); }      // 160: + a 1 KiB dump for the filler piece
 static_assert(2 * pp_smem(160, 3) <= 160 * 1024, "two blocks of the three-slot 256 x 160 tile per CU");
@@ -594,162 +596,65 @@ __global__ __launch_bounds__(PNTH, NSL == 3 ? 4 : 2) void k_gemm_pp(const GemmPa
     }
 }
 
-// every per-lane byte offset must stay below the resource size (and the out-of-range marker above it)
-bool pp_fits(unsigned long long bytes) { return bytes + 65536ull < (unsigned long long)P_NUMREC; }
-
-int pp_bn(int N) { return N % 320 == 0 ? 320 : (N % 256 == 0 ? 256 : (N % 128 == 0 ? 128 : 0)); }
-int pp_bn(const GemmParams& p) { return (p.tile_n == 160 && p.N % 160 == 0) ? 160 : pp_bn(p.N); }
-
 unsigned long long* g_pp_prof_host = nullptr;
 
-// set by a launch that normalised its output rows itself (GemmParams::ln_out); read and cleared by mve_gemm_pp_ln_fused()
-thread_local bool g_pp_ln_fused = false;
-int g_pp_ln_fuse = -1;      // MVE_GEMM_LN_FUSE (default 1); 0: never (A/B, tests)
-bool pp_ln_fusable(const GemmParams& p) {
-    if (g_pp_ln_fuse < 0) { const char* e = getenv("MVE_GEMM_LN_FUSE"); g_pp_ln_fuse = e ? atoi(e) : 1; }
-    return g_pp_ln_fuse != 0 && p.N == 320 && p.M % PBM == 0 && p.out_lo && p.bias && p.out_scale == 1.0f && !p.res_after_scale && !p.out_f32 && !p.geglu &&
-           !p.rowvec && p.splitk <= 1 && p.splitk_seq <= 1 && p.orow_extra == 0 && p.tile_n == 0 && !(p.dbg & 2) && p.ln_gamma && p.ln_beta && p.ld_ln % 8 == 0;
+int pp_no_kernel(const GemmPlan& pl) {
+    mve_set_error("gemm_pp: no kernel for the plan (family %d, tile %d x %d, epilogue %d, splitk %d)", pl.family, pl.tile_m, pl.tile_n, pl.epilogue, pl.splitk);
+    return MVE_ERR_STATE;
 }
 
+// the four-slot kernel with the epilogue instantiation the plan names
 template <class Tag, int MODE, bool SEQ, int BN2>
-int launch_pp3(const GemmParams& p, hipStream_t s) {
-    if (p.sk_sync && p.splitk > 1) {          // K slices folded inside the launch (the partial tiles leave raw: the plain instantiation's generic epilogue path)
-        if constexpr (!SEQ && (BN2 == 320 || BN2 == 160)) {
-            static bool configured_red[64] = {};
-            int dev = 0;
-            MVE_HIP(hipGetDevice(&dev));
-            if (dev >= 0 && dev < 64 && !configured_red[dev]) {
-                MVE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_pp<Tag, MODE, SEQ, BN2, false, PNSLOT, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, pp_smem(BN2)));
-                configured_red[dev] = true;
-            }
-            const unsigned grid = (unsigned)mve_cdiv(p.M, PBM) * (unsigned)mve_cdiv(p.N, BN2) * (unsigned)p.splitk;
-            k_gemm_pp<Tag, MODE, SEQ, BN2, false, PNSLOT, false, true><<<grid, PNTH, pp_smem(BN2), s>>>(p);
-            MVE_LAUNCH_CHECK();
-            return MVE_OK;
-        } else {
-            return 1;
+int launch_pp3(const GemmPlan& pl, const GemmParams& p, hipStream_t s) {
+    constexpr int LDS = pp_smem(BN2);
+    constexpr bool WIDE = !SEQ && (BN2 == 320 || BN2 == 160);      // the tiles that have the slice fold and the residual pair
+    if (pl.epilogue == GEMM_EPI_RED) {            // K slices folded inside the launch (the partial tiles leave raw: the plain instantiation's generic epilogue path)
+        if constexpr (WIDE) return mve_launch_dyn_lds<&k_gemm_pp<Tag, MODE, SEQ, BN2, false, PNSLOT, false, true>>(pl.grid, PNTH, LDS, s, p);
+    } else if (pl.epilogue == GEMM_EPI_LNF) {     // LayerNorm of the output rows inside the launch
+        if constexpr (!SEQ && BN2 == 320 && MODE == 0) return mve_launch_dyn_lds<&k_gemm_pp<Tag, 0, false, 320, false, PNSLOT, true, false, true>>(pl.grid, PNTH, LDS, s, p);
+    } else if (pl.epilogue == GEMM_EPI_PAIR) {    // residual_pair mode: the 320-wide and (round 5: small batches) 160-wide tiles without the slice fold
+        if constexpr (WIDE) return mve_launch_dyn_lds<&k_gemm_pp<Tag, MODE, SEQ, BN2, false, PNSLOT, true>>(pl.grid, PNTH, LDS, s, p);
+    } else if (pl.epilogue == (SEQ ? GEMM_EPI_SEQ : GEMM_EPI_PLAIN)) {
+        if constexpr (std::is_same<Tag, F16Tag>::value && !SEQ && BN2 == 320) {
+            if (g_pp_prof_host) return mve_launch_dyn_lds<&k_gemm_pp<Tag, MODE, SEQ, BN2, true>>(pl.grid, PNTH, LDS, s, p);      // mve_gemm_pp_profile
         }
+        return mve_launch_dyn_lds<&k_gemm_pp<Tag, MODE, SEQ, BN2>>(pl.grid, PNTH, LDS, s, p);
     }
-    if constexpr (!SEQ && BN2 == 320 && MODE == 0) {
-        // LayerNorm of the output rows inside the launch: exactly the configuration big_tile_epilogue's pair fast path takes on EVERY tile of the launch
-        if (p.ln_out && pp_ln_fusable(p)) {
-            static bool configured_ln[64] = {};
-            int dev = 0;
-            MVE_HIP(hipGetDevice(&dev));
-            if (dev >= 0 && dev < 64 && !configured_ln[dev]) {
-                MVE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_pp<Tag, 0, false, 320, false, PNSLOT, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, pp_smem(320)));
-                configured_ln[dev] = true;
-            }
-            const unsigned grid = (unsigned)(p.M / PBM);
-            k_gemm_pp<Tag, 0, false, 320, false, PNSLOT, true, false, true><<<grid, PNTH, pp_smem(320), s>>>(p);
-            MVE_LAUNCH_CHECK();
-            g_pp_ln_fused = true;
-            return MVE_OK;
-        }
-    }
-    if (p.residual_lo || p.out_lo) {          // residual_pair mode: the 320-wide and (round 5: small batches) 160-wide tiles without the slice fold
-        if constexpr (!SEQ && (BN2 == 320 || BN2 == 160)) {
-            static bool configured_pair[64] = {};
-            int dev = 0;
-            MVE_HIP(hipGetDevice(&dev));
-            if (dev >= 0 && dev < 64 && !configured_pair[dev]) {
-                MVE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_pp<Tag, MODE, SEQ, BN2, false, PNSLOT, true>), hipFuncAttributeMaxDynamicSharedMemorySize, pp_smem(BN2)));
-                configured_pair[dev] = true;
-            }
-            const unsigned grid = (unsigned)mve_cdiv(p.M, PBM) * (unsigned)mve_cdiv(p.N, BN2) * (unsigned)(p.splitk > 1 ? p.splitk : 1);
-            k_gemm_pp<Tag, MODE, SEQ, BN2, false, PNSLOT, true><<<grid, PNTH, pp_smem(BN2), s>>>(p);
-            MVE_LAUNCH_CHECK();
-            return MVE_OK;
-        } else {
-            return 1;                         // not eligible: the caller falls back (128-row kernel: gemm_epilogue_tail carries the pair)
-        }
-    }
-    if constexpr (std::is_same<Tag, F16Tag>::value && !SEQ && BN2 == 320) {
-        if (g_pp_prof_host) {
-            MVE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_pp<Tag, MODE, SEQ, BN2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, pp_smem(BN2)));
-            const unsigned grid = (unsigned)mve_cdiv(p.M, PBM) * (unsigned)mve_cdiv(p.N, BN2) * (unsigned)(p.splitk > 1 ? p.splitk : 1);
-            k_gemm_pp<Tag, MODE, SEQ, BN2, true><<<grid, PNTH, pp_smem(BN2), s>>>(p);
-            MVE_LAUNCH_CHECK();
-            return MVE_OK;
-        }
-    }
-    static bool configured[64] = {};
-    int dev = 0;
-    MVE_HIP(hipGetDevice(&dev));
-    if (dev >= 0 && dev < 64 && !configured[dev]) {
-        MVE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_pp<Tag, MODE, SEQ, BN2>), hipFuncAttributeMaxDynamicSharedMemorySize, pp_smem(BN2)));
-        configured[dev] = true;
-    }
-    const unsigned grid = (unsigned)mve_cdiv(p.M, PBM) * (unsigned)mve_cdiv(p.N, BN2) * (unsigned)(p.splitk > 1 ? p.splitk : 1);
-    k_gemm_pp<Tag, MODE, SEQ, BN2><<<grid, PNTH, pp_smem(BN2), s>>>(p);
-    MVE_LAUNCH_CHECK();
-    return MVE_OK;
+    return pp_no_kernel(pl);
 }
 
-// The two-blocks-per-CU tile: dense GEMM, whole 256 x 160 tiles, the epilogue configuration pp2_epilogue implements
-bool pp2_eligible(int mode, const GemmParams& p) {
-    if (mode != 0 || p.N % 160 != 0 || p.M % PBM != 0 || p.K % BK != 0) return false;
-    if (p.splitk > 1 || p.splitk_seq > 1 || p.rowvec || p.out_f32 || p.out_scale != 1.0f || (p.residual && p.res_after_scale)) return false;
-    if (p.residual_lo || p.out_lo) return false;          // the pair epilogue lives in big_tile_epilogue / gemm_epilogue_tail only
-    if (p.geglu && (p.ldc % 8 != 0)) return false;
-    if (!p.geglu && p.ldc % 8 != 0) return false;
-    return pp_fits((unsigned long long)p.N * p.ldw * 2) && pp_fits((unsigned long long)p.M * p.lda * 2);
-}
-
+// the two-blocks-per-CU tile (three slots)
 template <class Tag>
-int launch_pp2(const GemmParams& p, hipStream_t s) {
-    static bool configured[64] = {};
-    int dev = 0;
-    MVE_HIP(hipGetDevice(&dev));
-    if (dev >= 0 && dev < 64 && !configured[dev]) {
-        MVE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_pp<Tag, 0, false, 160, false, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, pp_smem(160, 3)));
-        configured[dev] = true;
+int launch_pp2(const GemmPlan& pl, const GemmParams& p, hipStream_t s) {
+    constexpr int LDS = pp_smem(160, 3);
+    static const bool said = [] {
         if (getenv("MVE_DEBUG")) {
             int nb = -1;
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&k_gemm_pp<Tag, 0, false, 160, false, 3>), PNTH, pp_smem(160, 3));
-            fprintf(stderr, "[mve] k_gemm_pp<160, 3 slots>: %d blocks per CU by the occupancy API (LDS %d B per block)\n", nb, pp_smem(160, 3));
+            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&k_gemm_pp<Tag, 0, false, 160, false, 3>), PNTH, LDS);
+            fprintf(stderr, "[mve] k_gemm_pp<160, 3 slots>: %d blocks per CU by the occupancy API (LDS %d B per block)\n", nb, LDS);
         }
-    }
-    const unsigned grid = (unsigned)(p.M / PBM) * (unsigned)(p.N / 160);
+        return true;
+    }();
+    (void)said;
     if constexpr (std::is_same<Tag, F16Tag>::value) {
-        if (g_pp_prof_host) {
-            MVE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_pp<Tag, 0, false, 160, true, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, pp_smem(160, 3)));
-            k_gemm_pp<Tag, 0, false, 160, true, 3><<<grid, PNTH, pp_smem(160, 3), s>>>(p);
-            MVE_LAUNCH_CHECK();
-            return MVE_OK;
-        }
+        if (g_pp_prof_host) return mve_launch_dyn_lds<&k_gemm_pp<Tag, 0, false, 160, true, 3>>(pl.grid, PNTH, LDS, s, p);
     }
-    k_gemm_pp<Tag, 0, false, 160, false, 3><<<grid, PNTH, pp_smem(160, 3), s>>>(p);
-    MVE_LAUNCH_CHECK();
-    return MVE_OK;
+    return mve_launch_dyn_lds<&k_gemm_pp<Tag, 0, false, 160, false, 3>>(pl.grid, PNTH, LDS, s, p);
 }
 
 template <class Tag, int MODE>
-int launch_pp(const GemmParams& p, hipStream_t s) {
-    if (pp_bn(p) == 256) return launch_pp3<Tag, MODE, false, 256>(p, s);
-    if (pp_bn(p) == 128) return launch_pp3<Tag, MODE, false, 128>(p, s);
-    if (pp_bn(p) == 160) return launch_pp3<Tag, MODE, false, 160>(p, s);
-    return p.splitk_seq > 1 ? launch_pp3<Tag, MODE, true, 320>(p, s) : launch_pp3<Tag, MODE, false, 320>(p, s);
-}
-
-int g_pp_old_swizzle = 0;
-
-bool pp_eligible(int mode, const GemmParams& p) {
-    const int bn = pp_bn(p);
-    if (bn == 0 || p.M < 64 || p.K % BK != 0) return false;
-    if (bn != 320 && bn != 160 && p.splitk > 1) return false;
-    if (bn != 320 && p.splitk_seq > 1) return false;
-    if (!pp_fits((unsigned long long)p.N * p.ldw * 2)) return false;
-    if (mode == 0) return pp_fits((unsigned long long)p.M * p.lda * 2);
-    if (!p.g.chunk64) return false;
-    const int hw = p.g.Ho * p.g.Wo;
-    if (p.g.phase_rows > 0 && (p.g.kw != 2 || p.g.phase_rows % PBM != 0 || p.M != 4 * p.g.phase_rows)) return false;
-    const int m_img = p.g.phase_rows > 0 ? p.g.phase_rows : p.M;      // rows that address distinct source pixels
-    const unsigned long long px = (unsigned long long)((m_img + hw - 1) / hw) * p.g.Hs * p.g.Ws + 2ull * p.g.Ws + 4;
-    int cmax = p.g.C1 > p.g.C2 ? p.g.C1 : p.g.C2;
-    cmax = cmax > p.g.C3 ? cmax : p.g.C3;
-    cmax = cmax > p.g.C4 ? cmax : p.g.C4;
-    return pp_fits(px * cmax * 2);
+int launch_pp(const GemmPlan& pl, const GemmParams& p, hipStream_t s) {
+    if (pl.tile_m != PBM) return pp_no_kernel(pl);
+    if (pl.family == GEMM_PP2) {
+        if constexpr (MODE == 0) { if (pl.tile_n == 160 && pl.epilogue == GEMM_EPI_PLAIN) return launch_pp2<Tag>(pl, p, s); }
+        return pp_no_kernel(pl);
+    }
+    if (pl.family != GEMM_PP) return pp_no_kernel(pl);
+    if (pl.tile_n == 256) return launch_pp3<Tag, MODE, false, 256>(pl, p, s);
+    if (pl.tile_n == 128) return launch_pp3<Tag, MODE, false, 128>(pl, p, s);
+    if (pl.tile_n == 160) return launch_pp3<Tag, MODE, false, 160>(pl, p, s);
+    if (pl.tile_n != 320) return pp_no_kernel(pl);
+    return pl.epilogue == GEMM_EPI_SEQ ? launch_pp3<Tag, MODE, true, 320>(pl, p, s) : launch_pp3<Tag, MODE, false, 320>(pl, p, s);
 }
 
 }  // namespace
@@ -762,39 +667,13 @@ extern "C" MVE_API int mve_gemm_pp_profile(void* buf) {
     return MVE_OK;
 }
 
-// did the last launch of this thread normalise its output rows itself?  (read once: the flag is cleared)
-bool mve_gemm_pp_ln_fused() {
-    const bool f = g_pp_ln_fused;
-    g_pp_ln_fused = false;
-    return f;
-}
-int mve_gemm_pp_ln_fuse_tune(int on) {       // -> previous setting (the environment default resolved); negative only queries
-    if (g_pp_ln_fuse < 0) { const char* e = getenv("MVE_GEMM_LN_FUSE"); g_pp_ln_fuse = e ? atoi(e) : 1; }
-    const int old = g_pp_ln_fuse != 0;
-    if (on >= 0) g_pp_ln_fuse = on ? 1 : 0;
-    return old;
-}
-
-// A/B aid: 1 = the ring swizzle of round 2 ((row >> 2) & 3: every fragment read 2-way bank conflicted); results are identical either way
-void mve_gemm_pp_old_swizzle(int on) { g_pp_old_swizzle = on ? 1 : 0; }
-
-// ping-pong main loop + epilogue (or split-K partials; the caller runs the reducer).  Returns 1 when the problem is not eligible
-// (the caller falls back to the two-stage kernel), MVE_OK after a launch, < 0 on error.
-int mve_gemm_pp_launch(int dtype, int mode, const void* params, void* stream) {
-    GemmParams p = *reinterpret_cast<const GemmParams*>(params);
-    p.old_swizzle = g_pp_old_swizzle;
-    { static int dbg = -1; if (dbg < 0) { const char* e = getenv("MVE_PP_DBG"); dbg = e ? atoi(e) : 0; } p.dbg = dbg; }
+// ping-pong main loop + epilogue (or split-K partials; the caller runs the reducer)
+int mve_gemm_pp_launch(int dtype, int mode, const void* plan, const void* params, void* stream) {
+    const GemmPlan& pl = *reinterpret_cast<const GemmPlan*>(plan);
+    const GemmParams& p = *reinterpret_cast<const GemmParams*>(params);
     hipStream_t s = (hipStream_t)stream;
-    if (p.tile_n == 161) {               // the caller asks for the two-blocks-per-CU tile
-        if (!pp2_eligible(mode, p)) return 1;
-        if (dtype == MVE_F16) return launch_pp2<F16Tag>(p, s);
-        if (dtype == MVE_BF16) return launch_pp2<BF16Tag>(p, s);
-        mve_set_error("gemm_pp: unsupported dtype %d", dtype);
-        return MVE_ERR_ARG;
-    }
-    if (!pp_eligible(mode, p)) return 1;
-    if (dtype == MVE_F16) return mode == 0 ? launch_pp<F16Tag, 0>(p, s) : launch_pp<F16Tag, 1>(p, s);
-    if (dtype == MVE_BF16) return mode == 0 ? launch_pp<BF16Tag, 0>(p, s) : launch_pp<BF16Tag, 1>(p, s);
+    if (dtype == MVE_F16) return mode == 0 ? launch_pp<F16Tag, 0>(pl, p, s) : launch_pp<F16Tag, 1>(pl, p, s);
+    if (dtype == MVE_BF16) return mode == 0 ? launch_pp<BF16Tag, 0>(pl, p, s) : launch_pp<BF16Tag, 1>(pl, p, s);
     mve_set_error("gemm_pp: unsupported dtype %d", dtype);
     return MVE_ERR_ARG;
 }

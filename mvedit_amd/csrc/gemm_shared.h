@@ -1,6 +1,9 @@
 // Definitions shared by the GEMM / implicit-GEMM conv kernels (gemm.hip: 128 x 160 tiles; gemm_big.hip: 256 x 320 tiles).  Everything is in an anonymous namespace: each translation unit gets its own copy.
+// A plain host compiler (no __HIPCC__: gemm_dispatch.h on its own) sees the constants and the parameter structs only.
 #pragma once
+#ifdef __HIPCC__
 #include "common.h"
+#endif
 
 namespace {
 
@@ -8,10 +11,12 @@ constexpr int BK = 64;           // elements
 constexpr int NT = 256;
 constexpr int ROW_BYTES = BK * 2;  // 128 B per tile row
 
+#ifdef __HIPCC__
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
 
 __device__ __attribute__((aligned(16))) unsigned int g_zero_page[4] = {0u, 0u, 0u, 0u};
+#endif
 
 struct ConvGeom {
     // virtual input (after optional upsample) Hv x Wv, source tensors Hs x Ws
@@ -34,8 +39,10 @@ struct ConvGeom {
     int phase_rows;
 };
 
+#ifdef __HIPCC__
 // phase of row m in a phase_rows launch (0 otherwise) -- three compares, no division
 __device__ __forceinline__ int conv_phase_of(int m, int R) { return R > 0 ? (int)(m >= R) + (int)(m >= 2 * R) + (int)(m >= 3 * R) : 0; }
+#endif
 
 struct GemmParams {
     const void* A;     // dense A [M][lda]  or conv source 1 (NHWC)
@@ -100,6 +107,7 @@ struct GemmParams {
     ConvGeom g;
 };
 
+#ifdef __HIPCC__
 // logical block id of a launch of BMT-row tiles: the XCD remap, in two pieces under the second-half predicate
 __device__ __forceinline__ unsigned gemm_block_lin(const GemmParams& p, unsigned nblk, int tiles_n, int S, int BMT) {
     if (!p.skip_if) return mve_xcd_remap(blockIdx.x, nblk);
@@ -236,7 +244,7 @@ __device__ __forceinline__ void gemm_epilogue_store(const GemmParams& p, int m, 
 // (relaxed agent-scope atomic) and polls, relaxed, until the tile's S slices are all there; the partial tiles are read with sc1 loads -- correct
 // for any placement of the slices on XCDs / CUs, without a release or acquire fence (MI355X_MICROARCH.md, inter-workgroup visibility).  Every block then folds rows [PBM s / S, PBM (s + 1) / S) of the tile over the slices in slice order 0 .. S - 1 starting from 0.0f and hands the
 // sums to gemm_epilogue_store: exactly k_splitk_reduce's arithmetic, so the result is bit-identical to partials + reducer launch on any tile
-// width and for any arrival order.  Waiting on siblings cannot deadlock: the launchers (gemm.hip: launch_red, launch_v) fold inside the launch only
+// width and for any arrival order.  Waiting on siblings cannot deadlock: the launchers (gemm_dispatch.h: plan_pp_fold, plan_v128) fold inside the launch only
 // where the whole grid is resident at once (at most one ping-pong block, or two 128-row blocks, per CU), so a waiting block never holds the slot
 // a sibling needs; a block only waits AFTER its own K loop.  Departure: the block that leaves last zeroes the counter for the next launch.
 template <class Tag, int BN2, int PBM, int PNTH>
@@ -288,5 +296,7 @@ __device__ __forceinline__ void gemm_reduce_slices(const GemmParams& p, unsigned
     }
 }
 
+
+#endif      // __HIPCC__
 
 }  // namespace

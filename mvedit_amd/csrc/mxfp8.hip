@@ -267,18 +267,9 @@ __global__ __launch_bounds__(256) void k_mxfp8_gemm(const MxGemmArgs p) {
 
 template <class TO>
 int launch_gemm(const MxGemmArgs& a, hipStream_t s) {
-    static bool configured[64] = {};                      // 66 KiB of dynamic LDS: above the 64 KiB a kernel gets without asking
-    int dev = 0;
-    MVE_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !configured[dev]) {
-        MVE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mxfp8_gemm<TO>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE_BYTES));
-        if (dev >= 0 && dev < 64) configured[dev] = true;
-    }
     const size_t blocks = (size_t)mve_cdiv(a.M, GT) * mve_cdiv(a.N, GT);
     MVE_CHECK(blocks < (1ull << 31), MVE_ERR_ARG, "mve_mxfp8_gemm: M=%d x N=%d is too large for one launch", a.M, a.N);
-    k_mxfp8_gemm<TO><<<dim3((unsigned)blocks), 256, 2 * STAGE_BYTES, s>>>(a);
-    MVE_LAUNCH_CHECK();
-    return MVE_OK;
+    return mve_launch_dyn_lds<&k_mxfp8_gemm<TO>>(dim3((unsigned)blocks), 256, 2 * STAGE_BYTES, s, a);      // 66 KiB of dynamic LDS: above the 64 KiB a kernel gets without asking
 }
 
 int elem_size(int dtype) { return dtype == MVE_F32 ? 4 : 2; }
