@@ -428,6 +428,20 @@ MVE_API int mve_act(int dtype, int kind, const void* d_x, void* d_y, size_t n, v
  * equals eos_token_id, position 0 when there is none.  d_x [B,L,C], d_out [B,C] in `dtype`. */
 MVE_API int mve_clip_pool(int dtype, const void* d_x, const int32_t* d_ids, void* d_out, int B, int L, int C, int eos_token_id, void* stream);
 
+/* ---- 2d. CLIP vision tower primitives (csrc/clip_vision.hip): the arithmetic of transformers' CLIPVisionEmbeddings (models/clip/modeling_clip.py)
+ * under `IPAdapter.image_encoder` (lib/models/architecture/ip_adapter/ip_adapter.py:51-53, :130, :138), `Zero123PlusPipeline.vision_encoder`
+ * (lib/pipelines/zero123plus.py:372) and `Zero123Pipeline.image_encoder` (lib/pipelines/zero123.py:260).  `dtype` is f16 or bf16, pointers are
+ * 16-byte aligned; every argument error returns MVE_ERR_ARG with a message that names the argument, before the device is touched. */
+
+/* The operand rows of `patch_embedding` = Conv2d(3, C, kernel = stride = P, bias=False) as a GEMM: with G = H / P, row b*G*G + gy*G + gx of
+ * d_rows [B*G*G][ld] holds the patch (gy, gx) of image b in (channel, ky, kx) order -- the order of weight.reshape(C, 3*P*P) -- and the columns
+ * from 3*P*P up to ld = 8 * ceil(3*P*P / 8) are zero (mve_gemm wants K % 8 == 0: patch 14 gives 588 -> 592).  d_pixels [B,3,H,W] NCHW.
+ * Pure data movement, no arithmetic.  H % P == 0, W == H. */
+MVE_API int mve_clip_patchify(int dtype, const void* d_pixels, int B, int H, int W, int P, void* d_rows, int ld, void* stream);
+/* CLIPVisionEmbeddings' sum: out[b,0,:] = round_once(float(cls) + float(pos[0])), out[b,1+p,:] = round_once(float(patch[b,p]) + float(pos[1+p])).
+ * d_patch [B*G2][C], d_cls [C], d_pos [G2+1][C], d_out [B][G2+1][C]; C % 8 == 0. */
+MVE_API int mve_clip_vision_embed(int dtype, const void* d_patch, const void* d_cls, const void* d_pos, void* d_out, int B, int G2, int C, void* stream);
+
 /* GroupNorm over NHWC input (optionally the channel-concat of two tensors) with optional fused SiLU:
  *   out[B*HW][C1+C2] = act( (x - mean_g) * rstd_g * gamma + beta ), torch.nn.GroupNorm semantics.
  * gamma/beta: [C1+C2] f32.  d_workspace: >= mve_groupnorm_workspace_bytes(B,HW,C,G) bytes.
@@ -717,6 +731,43 @@ MVE_API int mve_clip_text_plan(void* handle, int B, int L, size_t* workspace_byt
 MVE_API int mve_clip_text_forward(void* handle, const int32_t* d_ids, int B, int L, int eos_token_id, void* d_last_hidden_state,
                                   void* d_pooler_output, void* d_text_embeds, void* const* d_hidden_states, void* d_workspace, size_t workspace_bytes, float* op_ms,
                                   void* stream);
+/* CLIP vision tower (transformers CLIPVisionModel / CLIPVisionModelWithProjection; the reference's `IPAdapter.image_encoder`,
+ * `Zero123PlusPipeline.vision_encoder`, `Zero123Pipeline.image_encoder`).  An executor handle like the text tower: parameters through
+ * mve_unet_load_param under transformers' own names (`vision_model.embeddings.{class_embedding, patch_embedding.weight, position_embedding.weight}`,
+ * `vision_model.pre_layrnorm.*` (sic), `vision_model.encoder.layers.N.{layer_norm1, self_attn.{q,k,v,out}_proj, layer_norm2, mlp.{fc1,fc2}}.*`,
+ * `vision_model.post_layernorm.*`, `visual_projection.weight` when projection_dim > 0); the patch weight is stored [C][Kp], zero-padded, at load;
+ * mve_unet_missing_params / mve_unet_op_info / mve_unet_destroy apply.
+ * Plan: mve_clip_patchify, patch GEMM, mve_clip_vision_embed, pre_layrnorm; per layer LayerNorm, one q|k|v GEMM over the packed [3C, C] weight,
+ * mve_attention (Lq = Lk = G*G + 1, scale = head_dim^-1/2), out_proj GEMM + residual, LayerNorm, fc1 GEMM, mve_act, fc2 GEMM + residual; then
+ * last_hidden_state = the encoder output WITHOUT post_layernorm (transformers' definition; the text tower's differs), pooler_output =
+ * post_layernorm(last_hidden_state[:, 0]) (one mve_layernorm over B rows with ldx = (G*G+1) * C), image_embeds = the bias-free projection GEMM.
+ * GEMMs never split K: an item's result does not depend on the batch.
+ * Refused at create: hidden / heads not 64 or 80 (OpenCLIP bigG's 104 is refused, not approximated), hidden > 2048 (mve_layernorm),
+ * image_size % patch_size != 0, intermediate_size or projection_dim not a multiple of 8 (projection_dim 0 = no projection), act outside
+ * {MVE_ACT_QUICK_GELU, MVE_ACT_GELU}.
+ * d_pixels [B,3,S,S] NCHW in the handle's dtype, 16-byte aligned.  Outputs in the handle's dtype: d_last_hidden_state [B,G*G+1,C], d_pooler_output
+ * [B,C], d_image_embeds [B,P] (required when the handle has a projection, NULL otherwise); d_hidden_states: NULL, or layers + 1 pointers to
+ * [B,G*G+1,C] tensors -- entry 0 is the pre_layrnorm output, as in transformers' `output_hidden_states=True`. */
+MVE_API int mve_clip_vision_create(void** handle, int dtype, int image_size, int patch_size, int hidden_size, int num_layers, int num_heads,
+                                   int intermediate_size, int act, float layer_norm_eps, int projection_dim);
+MVE_API int mve_clip_vision_plan(void* handle, int B, size_t* workspace_bytes, int* n_ops, double* flops);
+MVE_API int mve_clip_vision_forward(void* handle, const void* d_pixels, int B, void* d_last_hidden_state, void* d_pooler_output, void* d_image_embeds,
+                                    void* const* d_hidden_states, void* d_workspace, size_t workspace_bytes, float* op_ms, void* stream);
+/* IP-Adapter "plus" image projection: the reference's Resampler (lib/models/architecture/ip_adapter/resampler.py:77-120) with dim_head = 64.
+ * An executor handle: parameters through mve_unet_load_param under the module's state_dict() names (`latents`, `proj_in.*`,
+ * `layers.N.0.{norm1,norm2}.*`, `layers.N.0.{to_q,to_kv,to_out}.weight`, `layers.N.1.0.*` (LayerNorm), `layers.N.1.{1,3}.weight`, `proj_out.*`,
+ * `norm_out.*`).  Plan: proj_in; per layer norm1(x), norm2(latents), to_q on the latents, to_kv on the image rows and on the latent rows,
+ * mve_attention with Lq = num_queries, first KV segment the n1 image keys, second segment the num_queries latent keys (the reference's
+ * cat(x, latents) is never formed), to_out + residual, LayerNorm, bias-free Linear, GELU, bias-free Linear + residual; then proj_out and norm_out.
+ * The ONE intended rounding difference: the reference scales q and k by dim_head^-1/4 each and rounds the softmax to 16 bit; here the logits are
+ * scaled by 1/8 in fp32 and the probabilities are mve_attention's fp32 softmax.
+ * dim, embedding_dim, output_dim multiples of 8; dim, output_dim <= 2048; the feed-forward width is dim * ff_mult.
+ * d_x [B,n1,embedding_dim], d_out [B,num_queries,output_dim], both in the handle's dtype and 16-byte aligned. */
+MVE_API int mve_ip_resampler_create(void** handle, int dtype, int dim, int depth, int heads, int num_queries, int embedding_dim, int output_dim,
+                                    int ff_mult);
+MVE_API int mve_ip_resampler_plan(void* handle, int B, int n1, size_t* workspace_bytes, int* n_ops, double* flops);
+MVE_API int mve_ip_resampler_forward(void* handle, const void* d_x, int B, int n1, void* d_out, void* d_workspace, size_t workspace_bytes,
+                                     float* op_ms, void* stream);
 /* LPIPS(net='vgg') perceptual loss, forward and backward w.r.t. the prediction: the `patch_loss` of the reference's reconstruct step
  * (lib/models/losses/lpips_loss.py:8-42 -> lpips==0.1.4 `LPIPS.forward`; lib/models/autoencoders/base_nerf.py:337-344, 8 patches of
  * 128 x 128 per optimisation iteration).  An executor handle: parameters through mve_unet_load_param under lpips' own state-dict

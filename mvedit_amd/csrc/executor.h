@@ -58,6 +58,8 @@ int mve_attention_causal(int, const void*, int, const void*, int, const void*, i
 int mve_clip_embed(int, const int32_t*, const void*, const void*, void*, int, int, int, int, int, void*);
 int mve_act(int, int, const void*, void*, size_t, void*);
 int mve_clip_pool(int, const void*, const int32_t*, void*, int, int, int, int, void*);
+int mve_clip_patchify(int, const void*, int, int, int, int, void*, int, void*);
+int mve_clip_vision_embed(int, const void*, const void*, const void*, void*, int, int, int, void*);
 }
 
 namespace {
@@ -131,6 +133,12 @@ struct Config {
     // CLIPTextModel(WithProjection) (transformers models/clip/modeling_clip.py): ch[0] = hidden_size, heads[0] = num_attention_heads,
     // layers_per_block = num_hidden_layers, eps = layer_norm_eps; clip_proj = projection_dim (0: no text_projection)
     int clip = 0, clip_vocab = 0, clip_max_pos = 0, clip_inter = 0, clip_act = 0, clip_proj = 0;
+    // CLIPVisionModel(WithProjection): ch[0] / heads[0] / layers_per_block / eps / clip_inter / clip_act / clip_proj as for the text tower;
+    // cv_image = image_size, cv_patch = patch_size (builder_clip_vision.h)
+    int clipv = 0, cv_image = 0, cv_patch = 0;
+    // IP-Adapter Resampler (lib/models/architecture/ip_adapter/resampler.py): ch[0] = dim, heads[0] = heads (dim_head 64), layers_per_block = depth,
+    // rs_queries = num_queries, rs_embed = embedding_dim, rs_out = output_dim, rs_inner = int(dim * ff_mult)
+    int resampler = 0, rs_queries = 0, rs_embed = 0, rs_out = 0, rs_inner = 0;
     int dtype, in_ch, out_ch, n_levels, layers_per_block, ctx_dim, groups, linear_proj;
     // UNet2DConditionModel / ControlNetModel addition_embed_type (mve_unet_set_addition_embed): 0 none, 1 'text_time' (SDXL);
     // add_time_dim = addition_time_embed_dim, add_P = projection_class_embeddings_input_dim (in_features of add_embedding.linear_1)
@@ -334,7 +342,7 @@ struct XfDesc { std::string name; int c, heads, layers; };
 
 void enumerate(const Config& c, std::vector<ResnetDesc>& rs, std::vector<XfDesc>& xs) {
     const int n = c.n_levels, L = c.layers_per_block;
-    if (c.sr || c.lpips || c.clip) return;     // plain conv stacks / the text tower (builder_clip.h)
+    if (c.sr || c.lpips || c.clip || c.clipv || c.resampler) return;     // plain conv stacks / the CLIP towers and the Resampler (builder_clip*.h)
     if (c.vae) {      // diffusers Encoder / Decoder (autoencoders/vae.py): resnets only, one attention in the mid block
         const int Cm = c.ch[n - 1];
         if (c.vae == 2) {

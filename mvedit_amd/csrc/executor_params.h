@@ -76,6 +76,66 @@ void layout_params(Unet& u) {
         u.slab_bytes = sb.top;
         return;
     }
+    if (c.clipv) {
+        // transformers' names, packed as for the text tower; the patch convolution's weight is [C][Kp]: (channel, ky, kx) columns, zero-padded
+        // from 3 * P * P to a multiple of 8 (mve_clip_patchify lays out the matching operand rows)
+        const size_t C = c.ch[0], I = c.clip_inter, Kp = (3 * (size_t)c.cv_patch * c.cv_patch + 7) / 8 * 8, G = c.cv_image / c.cv_patch;
+        const std::string em = "vision_model.embeddings.";
+        sb.add(em + "class_embedding", C, false); need(em + "class_embedding");
+        sb.add(em + "patch_embedding.w", C * Kp, false); need(em + "patch_embedding.weight");
+        sb.add(em + "position_embedding.w", (G * G + 1) * C, false); need(em + "position_embedding.weight");
+        auto norm = [&](const std::string& n) {
+            sb.add(n + ".g", C, true); need(n + ".weight");
+            sb.add(n + ".b", C, true); need(n + ".bias");
+        };
+        auto linear = [&](const std::string& n, size_t rows, size_t cols) {
+            sb.add(n + ".w", rows * cols, false); need(n + ".weight");
+            sb.add(n + ".b", rows, true); need(n + ".bias");
+        };
+        norm("vision_model.pre_layrnorm");
+        for (int k = 0; k < c.layers_per_block; ++k) {
+            const std::string b = "vision_model.encoder.layers." + std::to_string(k);
+            norm(b + ".layer_norm1");
+            sb.add(b + ".self_attn.qkv.w", 3 * C * C, false);
+            sb.add(b + ".self_attn.qkv.b", 3 * C, true);
+            for (const char* pj : {"q_proj", "k_proj", "v_proj"}) { need(b + ".self_attn." + pj + ".weight"); need(b + ".self_attn." + pj + ".bias"); }
+            linear(b + ".self_attn.out_proj", C, C);
+            norm(b + ".layer_norm2");
+            linear(b + ".mlp.fc1", I, C);
+            linear(b + ".mlp.fc2", C, I);
+        }
+        norm("vision_model.post_layernorm");
+        if (c.clip_proj) { sb.add("visual_projection.w", (size_t)c.clip_proj * C, false); need("visual_projection.weight"); }
+        u.slab_bytes = sb.top;
+        return;
+    }
+    if (c.resampler) {
+        // the reference's state_dict() names; Linear weights as they come ([out][in]), LayerNorm affine parameters and biases in fp32
+        const size_t D = c.ch[0], inner = (size_t)c.heads[0] * 64, F = c.rs_inner, E = c.rs_embed, O = c.rs_out, Q = c.rs_queries;
+        sb.add("latents", Q * D, false); need("latents");
+        sb.add("proj_in.w", D * E, false); need("proj_in.weight");
+        sb.add("proj_in.b", D, true); need("proj_in.bias");
+        for (int k = 0; k < c.layers_per_block; ++k) {
+            const std::string a = "layers." + std::to_string(k) + ".0", f = "layers." + std::to_string(k) + ".1";
+            for (const char* n : {".norm1", ".norm2"}) {
+                sb.add(a + n + ".g", D, true); need(a + n + ".weight");
+                sb.add(a + n + ".b", D, true); need(a + n + ".bias");
+            }
+            sb.add(a + ".to_q.w", inner * D, false); need(a + ".to_q.weight");
+            sb.add(a + ".to_kv.w", 2 * inner * D, false); need(a + ".to_kv.weight");
+            sb.add(a + ".to_out.w", D * inner, false); need(a + ".to_out.weight");
+            sb.add(f + ".0.g", D, true); need(f + ".0.weight");
+            sb.add(f + ".0.b", D, true); need(f + ".0.bias");
+            sb.add(f + ".1.w", F * D, false); need(f + ".1.weight");
+            sb.add(f + ".3.w", D * F, false); need(f + ".3.weight");
+        }
+        sb.add("proj_out.w", O * D, false); need("proj_out.weight");
+        sb.add("proj_out.b", O, true); need("proj_out.bias");
+        sb.add("norm_out.g", O, true); need("norm_out.weight");
+        sb.add("norm_out.b", O, true); need("norm_out.bias");
+        u.slab_bytes = sb.top;
+        return;
+    }
     if (c.sr) {
         // body.0: conv in_ch -> F; body.(2k), k = 1..num_conv: conv F -> F; body.(2k+1): PReLU slopes; last: conv F -> out_ch * r * r
         const size_t F = c.ch[0];
@@ -323,7 +383,56 @@ int load_param(Unet& u, const std::string& name, const void* src, int src_dtype,
     const int Cm_ = c.ch[c.n_levels - 1];
     const int vin = c.vae == 1 ? Cm_ : c.ch[0], vout = c.vae == 1 ? c.ch[0] : Cm_;     // widths after conv_in / before conv_out
     const std::string va = "mid_block.attentions.0";
-    if (c.clip) {
+    if (c.clipv) {
+        const long long C = c.ch[0], I = c.clip_inter, PP3 = 3ll * c.cv_patch * c.cv_patch, Kp = (PP3 + 7) / 8 * 8, G = c.cv_image / c.cv_patch;
+        const std::string em = "vision_model.embeddings.";
+        int which = -1;
+        for (int k = 0; k < 3; ++k)
+            if (ends_with(name, std::string(".self_attn.") + "qkv"[k] + "_proj.weight") || ends_with(name, std::string(".self_attn.") + "qkv"[k] + "_proj.bias")) which = k;
+        if (name == em + "class_embedding") rc = vec(P(em + "class_embedding"), 0, C, 1);
+        else if (name == em + "patch_embedding.weight") {      // [C, 3, P, P] -> [C][Kp], tail columns zero (k_pack writes them)
+            Param* p = P(em + "patch_embedding.w");
+            MVE_CHECK(p, MVE_ERR_ARG, "load_param: no slot for %s", name.c_str());
+            MVE_CHECK(numel() == C * PP3, MVE_ERR_ARG, "load_param(%s): expected [%lld,3,%d,%d], got %lld elements", name.c_str(), C, c.cv_patch, c.cv_patch, numel());
+            d = PackDims{{1, 1, C, Kp}, {0, 0, PP3, 1}, {0, 0, Kp, 1}, PP3};
+            rc = pack(src_dtype, c.dtype, src, dstp(p, 0), d, s);
+        } else if (name == em + "position_embedding.weight") rc = mat(P(em + "position_embedding.w"), 0, G * G + 1, C, C);
+        else if (which >= 0 && ends_with(name, ".weight"))
+            rc = mat(P(name.substr(0, name.size() - std::string("q_proj.weight").size()) + "qkv.w"), (size_t)which * C * C, C, C, C);
+        else if (which >= 0) rc = vec(P(name.substr(0, name.size() - std::string("q_proj.bias").size()) + "qkv.b"), (size_t)which * C, C, 1);
+        else if (ends_with(name, ".self_attn.out_proj.weight")) rc = mat(P(strip(name, ".weight") + ".w"), 0, C, C, C);
+        else if (ends_with(name, ".mlp.fc1.weight")) rc = mat(P(strip(name, ".weight") + ".w"), 0, I, C, C);
+        else if (ends_with(name, ".mlp.fc2.weight")) rc = mat(P(strip(name, ".weight") + ".w"), 0, C, I, I);
+        else if (ends_with(name, ".mlp.fc1.bias")) rc = vec(P(strip(name, ".bias") + ".b"), 0, I, 1);
+        else if (ends_with(name, ".self_attn.out_proj.bias") || ends_with(name, ".mlp.fc2.bias")) rc = vec(P(strip(name, ".bias") + ".b"), 0, C, 1);
+        else if (c.clip_proj && name == "visual_projection.weight") rc = mat(P("visual_projection.w"), 0, c.clip_proj, C, C);
+        else if (ends_with(name, ".weight") && P(strip(name, ".weight") + ".g")) rc = vec(P(strip(name, ".weight") + ".g"), 0, C, 1);   // the LayerNorms
+        else if (ends_with(name, ".bias") && P(strip(name, ".bias") + ".b") && P(strip(name, ".bias") + ".g")) rc = vec(P(strip(name, ".bias") + ".b"), 0, C, 1);
+        else {
+            mve_set_error("load_param: %s is not a parameter of this CLIP vision model", name.c_str());
+            return MVE_ERR_ARG;
+        }
+    } else if (c.resampler) {
+        const long long D = c.ch[0], inner = (long long)c.heads[0] * 64, F = c.rs_inner, E = c.rs_embed, O = c.rs_out, Q = c.rs_queries;
+        if (name == "latents") rc = mat(P("latents"), 0, Q, D, D);
+        else if (name == "proj_in.weight") rc = mat(P("proj_in.w"), 0, D, E, E);
+        else if (name == "proj_in.bias") rc = vec(P("proj_in.b"), 0, D, 1);
+        else if (name == "proj_out.weight") rc = mat(P("proj_out.w"), 0, O, D, D);
+        else if (name == "proj_out.bias") rc = vec(P("proj_out.b"), 0, O, 1);
+        else if (name == "norm_out.weight") rc = vec(P("norm_out.g"), 0, O, 1);
+        else if (name == "norm_out.bias") rc = vec(P("norm_out.b"), 0, O, 1);
+        else if (ends_with(name, ".0.to_q.weight")) rc = mat(P(strip(name, ".weight") + ".w"), 0, inner, D, D);
+        else if (ends_with(name, ".0.to_kv.weight")) rc = mat(P(strip(name, ".weight") + ".w"), 0, 2 * inner, D, D);
+        else if (ends_with(name, ".0.to_out.weight")) rc = mat(P(strip(name, ".weight") + ".w"), 0, D, inner, inner);
+        else if (ends_with(name, ".1.1.weight")) rc = mat(P(strip(name, ".weight") + ".w"), 0, F, D, D);
+        else if (ends_with(name, ".1.3.weight")) rc = mat(P(strip(name, ".weight") + ".w"), 0, D, F, F);
+        else if (ends_with(name, ".weight") && P(strip(name, ".weight") + ".g")) rc = vec(P(strip(name, ".weight") + ".g"), 0, D, 1);   // norm1 / norm2 / the FF's LayerNorm
+        else if (ends_with(name, ".bias") && P(strip(name, ".bias") + ".b") && P(strip(name, ".bias") + ".g")) rc = vec(P(strip(name, ".bias") + ".b"), 0, D, 1);
+        else {
+            mve_set_error("load_param: %s is not a parameter of this Resampler", name.c_str());
+            return MVE_ERR_ARG;
+        }
+    } else if (c.clip) {
         const long long C = c.ch[0], I = c.clip_inter;
         const std::string em = "text_model.embeddings.";
         int which = -1;

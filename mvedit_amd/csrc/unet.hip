@@ -17,13 +17,14 @@
 //   * per-op HIP-event profiling and analytic FLOP accounting are built in (bench.py's roofline).
 //
 // Source layout (one translation unit): executor.h (types) -> executor_params.h (parameter slab + loader) -> executor_builder.h (plan
-// builder, shared blocks) -> builder_{unet,vae,sr,lpips,clip}.h (one plan builder per network) -> this file (plan cache + C ABI).
+// builder, shared blocks) -> builder_{unet,vae,sr,lpips,clip,clip_vision}.h (one plan builder per network) -> this file (plan cache + C ABI).
 #include "executor_builder.h"
 #include "builder_unet.h"
 #include "builder_vae.h"
 #include "builder_sr.h"
 #include "builder_lpips.h"
 #include "builder_clip.h"
+#include "builder_clip_vision.h"
 
 namespace {
 
@@ -43,7 +44,7 @@ int ensure_plan(Unet& u, int B, int H, int W, int n_img, int has_res, int io_dty
     Builder b(u, *np);
     b.ctx_rows_per_img = ctx_len;
     u.cur = nullptr;
-    const int rc = u.cfg.clip ? b.build_clip(B, H) : u.cfg.lpips ? b.build_lpips(B, H, W, io_dtype) : u.cfg.sr ? b.build_sr(B, H, W, io_dtype) : u.cfg.vae ? b.build_vae(B, H, W, io_dtype) : b.build(B, H, W, n_img, has_res, io_dtype, res_nhwc);
+    const int rc = u.cfg.clipv ? b.build_clip_vision(B) : u.cfg.resampler ? b.build_resampler(B, H) : u.cfg.clip ? b.build_clip(B, H) : u.cfg.lpips ? b.build_lpips(B, H, W, io_dtype) : u.cfg.sr ? b.build_sr(B, H, W, io_dtype) : u.cfg.vae ? b.build_vae(B, H, W, io_dtype) : b.build(B, H, W, n_img, has_res, io_dtype, res_nhwc);
     if (rc != MVE_OK) return rc;
     np->ctx_len = ctx_len;
     np->last_use = u.tick;
@@ -383,6 +384,158 @@ int mve_clip_text_forward(void* handle, const int32_t* d_ids, int B, int L, int 
     return MVE_OK;
 }
 
+// the op list of the current plan on one stream, with optional per-op timing (CLIP vision tower, Resampler)
+static int run_plan_ops(const Plan& pl, const Run& r, float* op_ms) {
+    std::vector<hipEvent_t> ev;
+    if (op_ms) {
+        ev.resize(pl.ops.size() + 1);
+        for (auto& e : ev) MVE_HIP(hipEventCreate(&e));
+        MVE_HIP(hipEventRecord(ev[0], r.stream));
+    }
+    for (size_t i = 0; i < pl.ops.size(); ++i) {
+        const int rc = pl.ops[i].fn(r);
+        if (rc) return rc;
+        if (op_ms) MVE_HIP(hipEventRecord(ev[i + 1], r.stream));
+    }
+    if (op_ms) {
+        MVE_HIP(hipStreamSynchronize(r.stream));
+        for (size_t i = 0; i < pl.ops.size(); ++i) MVE_HIP(hipEventElapsedTime(&op_ms[i], ev[i], ev[i + 1]));
+        for (auto& e : ev) (void)hipEventDestroy(e);
+    }
+    return MVE_OK;
+}
+
+int mve_clip_vision_create(void** handle, int dtype, int image_size, int patch_size, int hidden_size, int num_layers, int num_heads, int intermediate_size,
+                           int act, float layer_norm_eps, int projection_dim) {
+    MVE_CHECK(handle, MVE_ERR_ARG, "clip_vision_create: null handle");
+    MVE_CHECK(dtype == MVE_F16 || dtype == MVE_BF16, MVE_ERR_ARG, "clip_vision_create: dtype must be f16 or bf16");
+    MVE_CHECK(image_size >= 1 && patch_size >= 1 && patch_size <= image_size && image_size <= 4096, MVE_ERR_ARG, "clip_vision_create: bad image_size %d / patch_size %d",
+              image_size, patch_size);
+    MVE_CHECK(image_size % patch_size == 0, MVE_ERR_ARG, "clip_vision_create: image_size %d must be a multiple of patch_size %d", image_size, patch_size);
+    MVE_CHECK(num_layers >= 1 && num_heads >= 1, MVE_ERR_ARG, "clip_vision_create: bad num_layers %d / num_heads %d", num_layers, num_heads);
+    MVE_CHECK(hidden_size == num_heads * 64 || hidden_size == num_heads * 80, MVE_ERR_ARG,
+              "clip_vision_create: hidden_size %d / num_heads %d: head_dim must be 64 or 80 (%d heads)", hidden_size, num_heads, num_heads);
+    MVE_CHECK(hidden_size <= 2048, MVE_ERR_ARG, "clip_vision_create: hidden_size %d exceeds the 2048 channels of mve_layernorm", hidden_size);
+    MVE_CHECK(intermediate_size >= 8 && intermediate_size % 8 == 0, MVE_ERR_ARG, "clip_vision_create: intermediate_size %d must be a multiple of 8", intermediate_size);
+    MVE_CHECK(act == MVE_ACT_QUICK_GELU || act == MVE_ACT_GELU, MVE_ERR_ARG, "clip_vision_create: act %d (0 = quick_gelu, 1 = gelu)", act);
+    MVE_CHECK(projection_dim >= 0 && projection_dim % 8 == 0, MVE_ERR_ARG, "clip_vision_create: projection_dim %d must be a multiple of 8 (0 = none)", projection_dim);
+    MVE_CHECK(layer_norm_eps > 0.f, MVE_ERR_ARG, "clip_vision_create: layer_norm_eps must be positive");
+    Unet* u = new Unet();
+    Config& c = u->cfg;
+    c.clipv = 1; c.cv_image = image_size; c.cv_patch = patch_size; c.clip_inter = intermediate_size; c.clip_act = act; c.clip_proj = projection_dim;
+    c.dtype = dtype; c.in_ch = 3; c.out_ch = 1; c.n_levels = 1; c.layers_per_block = num_layers;
+    c.ctx_dim = 8; c.groups = 1; c.eps = layer_norm_eps; c.linear_proj = 0;
+    c.ch[0] = hidden_size; c.attn[0] = 0; c.heads[0] = num_heads; c.tlayers[0] = 0;
+    layout_params(*u);
+    *handle = u;
+    return MVE_OK;
+}
+
+int mve_clip_vision_plan(void* handle, int B, size_t* workspace_bytes, int* n_ops, double* flops) {
+    MVE_CHECK(handle && B > 0, MVE_ERR_ARG, "clip_vision_plan: bad arguments");
+    Unet* u = (Unet*)handle;
+    MVE_CHECK(u->cfg.clipv, MVE_ERR_ARG, "clip_vision_plan: handle is not a CLIP vision tower");
+    int rc = ensure_plan(*u, B, u->cfg.cv_image, u->cfg.cv_image, 1, 0, u->cfg.dtype, 0, 0);
+    if (rc) return rc;
+    if (workspace_bytes) *workspace_bytes = u->cur->ws_bytes;
+    if (n_ops) *n_ops = (int)u->cur->ops.size();
+    if (flops) for (int i = 0; i < OC_COUNT; ++i) flops[i] = u->cur->flops[i];
+    return MVE_OK;
+}
+
+int mve_clip_vision_forward(void* handle, const void* d_pixels, int B, void* d_last_hidden_state, void* d_pooler_output, void* d_image_embeds,
+                            void* const* d_hidden_states, void* d_workspace, size_t workspace_bytes, float* op_ms, void* stream) {
+    MVE_CHECK(handle, MVE_ERR_ARG, "clip_vision_forward: null handle");
+    Unet* u = (Unet*)handle;
+    MVE_CHECK(u->cfg.clipv, MVE_ERR_ARG, "clip_vision_forward: handle is not a CLIP vision tower");
+    {
+        char first[256];
+        const int miss = mve_unet_missing_params(handle, first, sizeof(first));
+        MVE_CHECK(miss == 0, MVE_ERR_STATE, "clip_vision_forward: %d parameters not loaded (first: %s)", miss, first);
+    }
+    MVE_CHECK(d_pixels && d_last_hidden_state && d_pooler_output, MVE_ERR_ARG, "clip_vision_forward: null pointer (d_pixels / d_last_hidden_state / d_pooler_output)");
+    MVE_CHECK(u->cfg.clip_proj ? d_image_embeds != nullptr : d_image_embeds == nullptr, MVE_ERR_ARG,
+              "clip_vision_forward: d_image_embeds must be given exactly when the handle has a visual_projection (projection_dim %d)", u->cfg.clip_proj);
+    MVE_CHECK(B > 0, MVE_ERR_ARG, "clip_vision_forward: bad B %d", B);
+    MVE_CHECK(((uintptr_t)d_pixels & 15) == 0, MVE_ERR_ARG, "clip_vision_forward: d_pixels must be 16-byte aligned");
+    int rc = ensure_plan(*u, B, u->cfg.cv_image, u->cfg.cv_image, 1, 0, u->cfg.dtype, 0, 0);
+    if (rc) return rc;
+    const Plan& pl = *u->cur;
+    MVE_CHECK(d_workspace && workspace_bytes >= pl.ws_bytes, MVE_ERR_NOMEM, "clip_vision_forward: workspace %zu < required %zu", workspace_bytes, pl.ws_bytes);
+    const int n_hidden = u->cfg.layers_per_block + 1;
+    std::vector<void*> outs(CLIP_OUT_HIDDEN0 + n_hidden, nullptr);
+    outs[CLIP_OUT_LAST] = d_last_hidden_state; outs[CLIP_OUT_POOLED] = d_pooler_output; outs[CLIP_OUT_EMBEDS] = d_image_embeds;
+    if (d_hidden_states)
+        for (int i = 0; i < n_hidden; ++i) {
+            MVE_CHECK(d_hidden_states[i], MVE_ERR_ARG, "clip_vision_forward: null d_hidden_states[%d]", i);
+            outs[CLIP_OUT_HIDDEN0 + i] = d_hidden_states[i];
+        }
+    Run r;
+    r.ws = (unsigned char*)d_workspace; r.wt = u->slab;
+    r.sample = d_pixels; r.timesteps = nullptr; r.ctx = nullptr; r.out = nullptr;
+    r.down_res = nullptr; r.mid_res = nullptr; r.ref_store = nullptr;
+    r.cn_out = outs.data();
+    r.stream = (hipStream_t)stream;
+    return run_plan_ops(pl, r, op_ms);
+}
+
+int mve_ip_resampler_create(void** handle, int dtype, int dim, int depth, int heads, int num_queries, int embedding_dim, int output_dim, int ff_mult) {
+    MVE_CHECK(handle, MVE_ERR_ARG, "ip_resampler_create: null handle");
+    MVE_CHECK(dtype == MVE_F16 || dtype == MVE_BF16, MVE_ERR_ARG, "ip_resampler_create: dtype must be f16 or bf16");
+    MVE_CHECK(depth >= 1 && heads >= 1 && num_queries >= 1, MVE_ERR_ARG, "ip_resampler_create: bad depth %d / heads %d / num_queries %d", depth, heads, num_queries);
+    MVE_CHECK(dim >= 8 && dim % 8 == 0 && dim <= 2048, MVE_ERR_ARG, "ip_resampler_create: dim %d must be a multiple of 8, at most the 2048 channels of mve_layernorm", dim);
+    MVE_CHECK(embedding_dim >= 8 && embedding_dim % 8 == 0, MVE_ERR_ARG, "ip_resampler_create: embedding_dim %d must be a multiple of 8", embedding_dim);
+    MVE_CHECK(output_dim >= 8 && output_dim % 8 == 0 && output_dim <= 2048, MVE_ERR_ARG,
+              "ip_resampler_create: output_dim %d must be a multiple of 8, at most the 2048 channels of mve_layernorm", output_dim);
+    MVE_CHECK(ff_mult >= 1 && ff_mult <= 16, MVE_ERR_ARG, "ip_resampler_create: ff_mult %d must be in [1, 16]", ff_mult);
+    const int inner = dim * ff_mult;      // int(dim * mult), resampler.py:10
+    Unet* u = new Unet();
+    Config& c = u->cfg;
+    c.resampler = 1; c.rs_queries = num_queries; c.rs_embed = embedding_dim; c.rs_out = output_dim; c.rs_inner = inner;
+    c.dtype = dtype; c.in_ch = 1; c.out_ch = 1; c.n_levels = 1; c.layers_per_block = depth;
+    c.ctx_dim = 8; c.groups = 1; c.eps = 1e-5f; c.linear_proj = 0;
+    c.ch[0] = dim; c.attn[0] = 0; c.heads[0] = heads; c.tlayers[0] = 0;
+    layout_params(*u);
+    *handle = u;
+    return MVE_OK;
+}
+
+int mve_ip_resampler_plan(void* handle, int B, int n1, size_t* workspace_bytes, int* n_ops, double* flops) {
+    MVE_CHECK(handle && B > 0 && n1 > 0, MVE_ERR_ARG, "ip_resampler_plan: bad arguments");
+    Unet* u = (Unet*)handle;
+    MVE_CHECK(u->cfg.resampler, MVE_ERR_ARG, "ip_resampler_plan: handle is not a Resampler");
+    int rc = ensure_plan(*u, B, n1, 1, 1, 0, u->cfg.dtype, 0, 0);
+    if (rc) return rc;
+    if (workspace_bytes) *workspace_bytes = u->cur->ws_bytes;
+    if (n_ops) *n_ops = (int)u->cur->ops.size();
+    if (flops) for (int i = 0; i < OC_COUNT; ++i) flops[i] = u->cur->flops[i];
+    return MVE_OK;
+}
+
+int mve_ip_resampler_forward(void* handle, const void* d_x, int B, int n1, void* d_out, void* d_workspace, size_t workspace_bytes, float* op_ms, void* stream) {
+    MVE_CHECK(handle, MVE_ERR_ARG, "ip_resampler_forward: null handle");
+    Unet* u = (Unet*)handle;
+    MVE_CHECK(u->cfg.resampler, MVE_ERR_ARG, "ip_resampler_forward: handle is not a Resampler");
+    {
+        char first[256];
+        const int miss = mve_unet_missing_params(handle, first, sizeof(first));
+        MVE_CHECK(miss == 0, MVE_ERR_STATE, "ip_resampler_forward: %d parameters not loaded (first: %s)", miss, first);
+    }
+    MVE_CHECK(d_x && d_out, MVE_ERR_ARG, "ip_resampler_forward: null pointer (d_x / d_out)");
+    MVE_CHECK(B > 0 && n1 > 0, MVE_ERR_ARG, "ip_resampler_forward: bad B %d / n1 %d", B, n1);
+    MVE_CHECK(((uintptr_t)d_x & 15) == 0 && ((uintptr_t)d_out & 15) == 0, MVE_ERR_ARG, "ip_resampler_forward: d_x / d_out must be 16-byte aligned");
+    int rc = ensure_plan(*u, B, n1, 1, 1, 0, u->cfg.dtype, 0, 0);
+    if (rc) return rc;
+    const Plan& pl = *u->cur;
+    MVE_CHECK(d_workspace && workspace_bytes >= pl.ws_bytes, MVE_ERR_NOMEM, "ip_resampler_forward: workspace %zu < required %zu", workspace_bytes, pl.ws_bytes);
+    Run r;
+    r.ws = (unsigned char*)d_workspace; r.wt = u->slab;
+    r.sample = d_x; r.timesteps = nullptr; r.ctx = nullptr; r.out = d_out;
+    r.down_res = nullptr; r.mid_res = nullptr; r.ref_store = nullptr;
+    r.stream = (hipStream_t)stream;
+    return run_plan_ops(pl, r, op_ms);
+}
+
 int mve_lpips_create(void** handle, int dtype, int normalize_inputs) {
     MVE_CHECK(handle, MVE_ERR_ARG, "lpips_create: null handle");
     MVE_CHECK(dtype == MVE_F16 || dtype == MVE_BF16, MVE_ERR_ARG, "lpips_create: dtype must be f16 or bf16");
@@ -523,7 +676,8 @@ int mve_unet_forward(void* handle, int phase, const void* d_sample, int io_dtype
                      float* op_ms /* optional host array [n_ops]: per-op milliseconds (synchronises) */, void* stream) {
     MVE_CHECK(handle, MVE_ERR_ARG, "unet_forward: null handle");
     Unet* u = (Unet*)handle;
-    MVE_CHECK(!u->cfg.controlnet && !u->cfg.vae && !u->cfg.sr && !u->cfg.lpips && !u->cfg.clip, MVE_ERR_ARG, "unet_forward: handle is a ControlNet / VAE / SRVGG / CLIP text tower (use their own forward calls)");
+    MVE_CHECK(!u->cfg.controlnet && !u->cfg.vae && !u->cfg.sr && !u->cfg.lpips && !u->cfg.clip && !u->cfg.clipv && !u->cfg.resampler, MVE_ERR_ARG,
+              "unet_forward: handle is a ControlNet / VAE / SRVGG / CLIP text or vision tower / Resampler (use their own forward calls)");
     {
         char first[256];
         const int miss = mve_unet_missing_params(handle, first, sizeof(first));
@@ -640,7 +794,7 @@ int mve_unet_set_attention(void* handle, int ip_tokens, float ip_scale, int ref_
 int mve_unet_set_residual_mode(void* handle, int pair) {
     MVE_CHECK(handle, MVE_ERR_ARG, "unet_set_residual_mode: null handle");
     Unet* u = (Unet*)handle;
-    MVE_CHECK(!u->cfg.vae && !u->cfg.sr && !u->cfg.lpips && !u->cfg.clip, MVE_ERR_ARG, "unet_set_residual_mode: a UNet / ControlNet handle is needed");
+    MVE_CHECK(!u->cfg.vae && !u->cfg.sr && !u->cfg.lpips && !u->cfg.clip && !u->cfg.clipv && !u->cfg.resampler, MVE_ERR_ARG, "unet_set_residual_mode: a UNet / ControlNet handle is needed");
     const int old = u->ao.residual_pair;
     if (pair >= 0) u->ao.residual_pair = pair ? 1 : 0;     // part of the plan key: plans of either mode stay cached side by side
     return old;
@@ -669,7 +823,7 @@ int mve_unet_set_addition_embed(void* handle, int addition_type, int addition_ti
     MVE_CHECK(handle, MVE_ERR_ARG, "unet_set_addition_embed: null handle");
     Unet* u = (Unet*)handle;
     Config& c = u->cfg;
-    MVE_CHECK(!c.vae && !c.sr && !c.lpips && !c.clip, MVE_ERR_ARG, "unet_set_addition_embed: a UNet / ControlNet handle is needed");
+    MVE_CHECK(!c.vae && !c.sr && !c.lpips && !c.clip && !c.clipv && !c.resampler, MVE_ERR_ARG, "unet_set_addition_embed: a UNet / ControlNet handle is needed");
     MVE_CHECK(addition_type == 0 || addition_type == 1, MVE_ERR_ARG, "unet_set_addition_embed: addition type %d (0 = none, 1 = text_time)", addition_type);
     MVE_CHECK(!u->slab && u->loaded.empty(), MVE_ERR_STATE, "unet_set_addition_embed: parameters are already loaded; declare the embedding right after create");
     MVE_CHECK(!c.add_type, MVE_ERR_STATE, "unet_set_addition_embed: the handle already has an addition embedding");

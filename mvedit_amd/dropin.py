@@ -34,7 +34,9 @@ What `install()` rebinds -- the operator seams of SURVEY.md section 8(b), nothin
      base_mesh_renderer imported before `install()` gets `dr` rebound.
 
 Not part of `install()`: `swap_text_encoder(pipe)` puts native CLIP text towers (mvedit_amd/text_encoder.py) behind `pipe.text_encoder` /
-`pipe.text_encoder_2` of ONE pipeline object, on request.
+`pipe.text_encoder_2` of ONE pipeline object, on request; `swap_image_encoder(obj)` puts the native CLIP vision tower
+(mvedit_amd/vision_encoder.py) behind `image_encoder` / `vision_encoder` and the native image projection (mvedit_amd/ip_adapter.py) behind
+`image_proj_model` of ONE object (an `IPAdapter`, a `Zero123PlusPipeline`, a `Zero123Pipeline`), on request.
 
 Nothing here computes: every replacement is one of the engines / mirrors INTEGRATION.md documents seam by seam, and a conversion that fails
 raises -- there is no fallback to the torch module.  `uninstall()` restores everything (tests).
@@ -180,6 +182,52 @@ def swap_text_encoder(pipe):
             object.__setattr__(m, '_mve_engine', cached)
         object.__setattr__(pipe, name, cached[1])
     return pipe
+
+
+def make_image_encoder(m):
+    """transformers CLIPVisionModelWithProjection / CLIPVisionModel (`IPAdapter.image_encoder`, lib/models/architecture/ip_adapter/ip_adapter.py:51-53;
+    `Zero123PlusPipeline.vision_encoder`, lib/pipelines/zero123plus.py:372; `Zero123Pipeline.image_encoder`, lib/pipelines/zero123.py:260)."""
+    from .vision_encoder import CLIPVisionEngine
+    dtype, device = _module_dtype_device(m)
+    return CLIPVisionEngine.from_module(m, dtype=dtype, device=device)
+
+
+IMAGE_PROJ_CLASSES = ('Resampler', 'ImageProjModel')          # lib/models/architecture/ip_adapter/{resampler.py:77, ip_adapter.py:15} (recognised by class name)
+
+
+def make_image_proj(m):
+    """`IPAdapter.image_proj_model`: the reference's Resampler ("plus" checkpoints) or ImageProjModel (ip_adapter.py:58, :64-83)."""
+    from .ip_adapter import ImageProjEngine, ResamplerEngine
+    kind = type(m).__name__
+    if kind not in IMAGE_PROJ_CLASSES:
+        raise TypeError(f'{kind} is not an IP-Adapter image projection model ({" / ".join(IMAGE_PROJ_CLASSES)})')
+    dtype, device = _module_dtype_device(m)
+    return (ResamplerEngine if kind == 'Resampler' else ImageProjEngine).from_module(m, dtype=dtype, device=device)
+
+
+IMAGE_ENCODER_ATTRS = ('image_encoder', 'vision_encoder')
+
+
+def swap_image_encoder(obj):
+    """Opt-in (install() / swap_engines leave the image towers alone): replaces `obj.image_encoder` / `obj.vision_encoder` and, when it is a
+    Resampler or an ImageProjModel, `obj.image_proj_model` by native engines built from those modules -- an IPAdapter, a Zero123PlusPipeline or a
+    Zero123Pipeline.  Idempotent; the engine is cached on the source module like the other seams'.  An `image_proj_model` of any other class is
+    left alone."""
+    for name in IMAGE_ENCODER_ATTRS + ('image_proj_model',):
+        m = getattr(obj, name, None)
+        if m is None or getattr(m, '_mve_is_engine', False) or not hasattr(m, 'state_dict'):
+            continue
+        if name == 'image_proj_model' and type(m).__name__ not in IMAGE_PROJ_CLASSES:
+            continue
+        fp = _fingerprint(m)
+        cached = getattr(m, '_mve_engine', None)
+        if cached is None or cached[0] != fp:
+            eng = (make_image_proj if name == 'image_proj_model' else make_image_encoder)(m)
+            object.__setattr__(eng, '_mve_is_engine', True)
+            cached = (fp, eng)
+            object.__setattr__(m, '_mve_engine', cached)
+        object.__setattr__(obj, name, cached[1])
+    return obj
 
 
 MAKERS = dict(unet=make_unet, controlnet=make_controlnet, vae=make_vae, image_enhancer=make_image_enhancer, segmentation=make_segmentation,
