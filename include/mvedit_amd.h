@@ -96,6 +96,21 @@ MVE_API int mve_march_rays_train_write(const float* d_rays_o, const float* d_ray
                                        const int32_t* d_rays, uint32_t capacity,
                                        float* d_xyzs, float* d_dirs, float* d_ts, void* stream);
 
+/* Capacity form of the training iteration: no host read between the passes.  The caller sizes the sample tensors by a CAPACITY it
+ * chooses; how many samples are live is a count in device memory that every following `_n` entry point reads.  None of the `_n` entry
+ * points (nor the calls they share kernels with) allocates, copies synchronously or synchronises, so the host never waits inside an
+ * iteration.  With any count in [0, capacity], and with a marched total above the capacity, no kernel touches memory outside the
+ * capacity-sized buffers: an overflow is a flag, never a fault.  (Bounds rules: mvedit_amd/csrc/capacity_core.h.)
+ *
+ *  _clamp : runs between _count and _write.  d_n_samples[0] = *d_total, the marched total, also when it exceeds the capacity (so a
+ *           caller can size a retry); *d_count = d_n_samples[1] = the samples of the longest prefix of whole rays that fit the
+ *           capacity (= the total when nothing overflows); *d_overflow = 1 when total > capacity, otherwise it is left as it is
+ *           (sticky: the caller zeroes it).  d_total may alias d_n_samples.  _write, given the same capacity, skips the rays that do
+ *           not fit, and so do the composite kernels given M = capacity; rows at and beyond the count are whatever the caller put
+ *           there (zeros). */
+MVE_API int mve_march_rays_train_clamp(const int32_t* d_rays, uint32_t N, const int32_t* d_total, uint32_t capacity,
+                                       int32_t* d_n_samples, int32_t* d_count, int32_t* d_overflow, void* stream);
+
 /* raymarching.cu:501-579 / :606-695.  sigmas[M], rgbs[M,3], ts[M,2], rays[N,2];
  * weights[M] must be zero-initialised by the caller (raymarching.py:330). */
 MVE_API int mve_composite_rays_train_forward(const float* d_sigmas, const float* d_rgbs, const float* d_ts,
@@ -137,6 +152,14 @@ MVE_API int mve_cull_samples(const float* d_weights, uint32_t M, float threshold
                              const float* d_xyzs, const float* d_dirs, const float* d_ts, float* d_out_xyzs, float* d_out_dirs,
                              float* d_out_ts, int32_t* d_out_rays, int32_t* d_pref, int32_t* d_n_out, void* d_scratch,
                              void* stream);
+/* Capacity form: the input count is read from the device (*d_count live rows of `capacity`), the kept count is written to *d_n_out
+ * (a different address).  Outputs and d_pref [capacity + 1] are capacity-sized; output rows at and beyond the kept count are zeros.
+ * A ray with offset + count above the live count did not fit: it becomes (kept count, 0), and d_pref is never read past the live count.
+ * For rays that fit, d_out_rays and the kept count equal mve_cull_samples(M = count).  d_scratch: mve_cull_scratch_bytes(capacity). */
+MVE_API int mve_cull_samples_n(const float* d_weights, uint32_t capacity, const int32_t* d_count, float threshold, const int32_t* d_rays,
+                               uint32_t N, const float* d_xyzs, const float* d_dirs, const float* d_ts, float* d_out_xyzs,
+                               float* d_out_dirs, float* d_out_ts, int32_t* d_out_rays, int32_t* d_pref, int32_t* d_n_out,
+                               void* d_scratch, void* stream);
 
 /* Density-grid refresh, the device part of update_extra_state (base_volume_renderer.py:105-177).
  *   density_grid_points : cell coords [N,3] int32 (NULL = every cell of the grid in meshgrid order) + uniform noise [N,3] in
@@ -565,6 +588,14 @@ MVE_API int mve_recon_loss_forward(const MveReconLossDesc* desc, void* d_ws, siz
 MVE_API int mve_recon_loss_backward(const MveReconLossDesc* desc, void* d_ws, size_t ws_bytes, const float* d_g_out_rgbs,
                                     const float* d_g_out_normals, const float* d_g_loss, float* d_g_image, float* d_g_weights_sum, float* d_g_depth,
                                     float* d_g_weights, void* stream);
+/* Capacity forms: desc->M is the capacity of weights / ts / g_weights (it sizes the workspace), *d_count the live samples.  Only the
+ * entropy term sees samples: one at or beyond the count adds nothing to the loss and gets a zero gradient, whatever its row holds.
+ * losses, out_rgbs, out_normals and the gradients' live rows equal the exact call on M = count bit for bit. */
+MVE_API int mve_recon_loss_forward_n(const MveReconLossDesc* desc, const int32_t* d_count, void* d_ws, size_t ws_bytes, float* d_losses,
+                                     float* d_out_rgbs, float* d_out_normals, void* stream);
+MVE_API int mve_recon_loss_backward_n(const MveReconLossDesc* desc, const int32_t* d_count, void* d_ws, size_t ws_bytes,
+                                      const float* d_g_out_rgbs, const float* d_g_out_normals, const float* d_g_loss, float* d_g_image,
+                                      float* d_g_weights_sum, float* d_g_depth, float* d_g_weights, void* stream);
 
 /* The same for one MESH optimisation iteration: lib/pipelines/mvedit_3d_pipeline.py:745-782 (`mesh_optim`, from `out_alphas =
  * render_out['rgba']...` to the regularised sum; the two mesh regularisers of that sum are mve_mesh_reg_*).  N = n * size * size pixels,
@@ -893,6 +924,13 @@ MVE_API int mve_hashgrid_mlp_decode(const float* d_xyz, uint32_t M, const float*
                                     const uint32_t* level_size, const float* d_w1, const float* d_b1, const float* d_w2,
                                     const float* d_b2, int hidden, float bound, float blob_density, float blob_radius,
                                     float sigmoid_saturation, float* d_sigmas, float* d_rgbs, void* stream);
+/* Capacity form: the grid is sized by `capacity`; a row at or beyond *d_count (device int32) loads nothing and gets sigma = 0,
+ * rgb = 0, so no consumer ever reads uninitialised memory.  Rows below the count equal mve_hashgrid_mlp_decode bit for bit. */
+MVE_API int mve_hashgrid_mlp_decode_n(const float* d_xyz, uint32_t capacity, const int32_t* d_count, const float* d_table, int n_levels,
+                                      const float* level_scale, const uint32_t* level_res, const uint32_t* level_offset,
+                                      const uint32_t* level_size, const float* d_w1, const float* d_b1, const float* d_w2,
+                                      const float* d_b2, int hidden, float bound, float blob_density, float blob_radius,
+                                      float sigmoid_saturation, float* d_sigmas, float* d_rgbs, void* stream);
 
 /* Decoder backward (the reconstruct step): gradients of  sum(g_sigma * sigma) + sum(g_rgb * rgb)  for the M
  * points of a training batch w.r.t. the hash table and the MLP of iNGPDecoder.point_decode (lib/models/decoders/ingp_decoder.py:106-120;
@@ -906,9 +944,26 @@ MVE_API int mve_hashgrid_mlp_backward(const float* d_xyz, uint32_t M, const floa
                                       float blob_density, float blob_radius, float sigmoid_saturation, const float* d_grad_sigma,
                                       const float* d_grad_rgb, float* d_grad_table, float* d_grad_w1, float* d_grad_b1,
                                       float* d_grad_w2, float* d_grad_b2, void* d_workspace, size_t workspace_bytes, void* stream);
+/* Capacity form: workspace >= mve_hashgrid_mlp_backward_workspace_bytes(capacity, n_levels); rows at or beyond *d_count contribute
+ * nothing and are never read.  The fixed-order reduction runs over the live 256-row blocks only, in the exact call's order, so the four
+ * MLP gradients equal mve_hashgrid_mlp_backward(M = count) bit for bit; the table gradient keeps its float atomics. */
+MVE_API int mve_hashgrid_mlp_backward_n(const float* d_xyz, uint32_t capacity, const int32_t* d_count, const float* d_table, int n_levels,
+                                        const float* level_scale, const uint32_t* level_res, const uint32_t* level_offset,
+                                        const uint32_t* level_size, const float* d_w1, const float* d_b1, const float* d_w2,
+                                        const float* d_b2, int hidden, float bound, float blob_density, float blob_radius,
+                                        float sigmoid_saturation, const float* d_grad_sigma, const float* d_grad_rgb, float* d_grad_table,
+                                        float* d_grad_w1, float* d_grad_b1, float* d_grad_w2, float* d_grad_b2, void* d_workspace,
+                                        size_t workspace_bytes, void* stream);
 /* torch.optim.Adam step (no weight decay, no amsgrad) in place on param / exp_avg / exp_avg_sq; step counts from 1. */
 MVE_API int mve_adam_step(float* d_param, const float* d_grad, float* d_exp_avg, float* d_exp_avg_sq, size_t n, float lr, float beta1,
                           float beta2, float eps, int step, void* stream);
+/* The same step with its state on the device: *d_step (int32) counts the steps already taken, the launch applies step *d_step + 1
+ * with the bias corrections computed in the kernel.  *d_skip != 0 (int32, e.g. the overflow flag of the capacity forward): the launch
+ * changes nothing -- not the parameter, not the moments.  mve_adam_advance_n, once after the parameters of one optimiser step, adds one
+ * to *d_step unless *d_skip != 0. */
+MVE_API int mve_adam_step_n(float* d_param, const float* d_grad, float* d_exp_avg, float* d_exp_avg_sq, size_t n, float lr, float beta1,
+                            float beta2, float eps, const int32_t* d_step, const int32_t* d_skip, void* stream);
+MVE_API int mve_adam_advance_n(int32_t* d_step, const int32_t* d_skip, void* stream);
 
 /* VolumeRenderer.forward, eval branch (lib/models/decoders/base_volume_renderer.py:264-329) as ONE launch:
  * near/far from the aabb, occupancy-grid march (cascade count 1, no contraction, noise 0), hash-grid + MLP decode and

@@ -20,6 +20,7 @@
 #include "raymarch_core.h"
 
 #include "hashgrid.h"
+#include "capacity_core.h"
 
 namespace {
 
@@ -153,11 +154,14 @@ __device__ __forceinline__ void decode_point2(const DecoderParams& p, const floa
 // factors of the weight gradients (dh, relu(h), enc, do) in a workspace; k_xty reduces them deterministically.
 // ---------------------------------------------------------------------------------------------------------------------
 template <int NL>
-__global__ __launch_bounds__(NB, 2) void k_decode_backward(DecoderParams p, const float* __restrict__ xyz, uint32_t M,
-                                                           const float* __restrict__ g_sigma, const float* __restrict__ g_rgb,
+__global__ __launch_bounds__(NB, 2) void k_decode_backward(DecoderParams p, const float* __restrict__ xyz, uint32_t M_rows,
+                                                           const int32_t* __restrict__ d_count, const float* __restrict__ g_sigma, const float* __restrict__ g_rgb,
                                                            float* __restrict__ g_table, float* __restrict__ ws_dh /*[M][64]*/,
                                                            float* __restrict__ ws_hr /*[M][64]*/, float* __restrict__ ws_enc /*[M][2NL]*/,
                                                            float* __restrict__ ws_do /*[M][4]*/) {
+    // (capacity form: M_rows is the capacity and the live rows are [0, *d_count); a block with no live row has nothing to do -- block-uniform)
+    const uint32_t M = cap_live(M_rows, d_count);
+    if (blockIdx.x * NB >= M) return;
     __shared__ __attribute__((aligned(16))) float w1t[HID * 2 * NL];
     stage_w1<NL>(p, w1t);
     __syncthreads();
@@ -346,9 +350,12 @@ __global__ __launch_bounds__(NB, 2) void k_decode_backward(DecoderParams p, cons
 // out[p][q] = sum_m X[m][p] * Y[m][q]  (and colsum: sum_m X[m][p]): per-block partials over XTY_ROWS-row chunks, reduced in a
 // fixed order by k_xty_reduce -> deterministic.  P, Q <= 64, P * Q <= 2048.
 constexpr int XTY_ROWS = 256, XTY_STEP = 32;       // (256-row chunks since round 4: 948 blocks for a 242 k-point batch instead of 237 on 256 CUs -- the kernel is LDS-read bound per block)
-__global__ __launch_bounds__(256) void k_xty(const float* __restrict__ X, int P, const float* __restrict__ Y, int Q, uint32_t M,
-                                             float* __restrict__ partial /*[nblk][P*Q + P]*/) {
+// (capacity form: blocks past the live rows leave their partials unwritten and k_xty_reduce, told the same count, never reads them)
+__global__ __launch_bounds__(256) void k_xty(const float* __restrict__ X, int P, const float* __restrict__ Y, int Q, uint32_t M_rows,
+                                             const int32_t* __restrict__ d_count, float* __restrict__ partial /*[nblk][P*Q + P]*/) {
     __shared__ float xs[XTY_STEP][64], ys[XTY_STEP][64];
+    const uint32_t M = cap_live(M_rows, d_count);
+    if (blockIdx.x * XTY_ROWS >= M) return;
     const uint32_t r0 = blockIdx.x * XTY_ROWS, r1 = min(M, r0 + XTY_ROWS);
     const int nout = P * Q;
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -375,10 +382,12 @@ __global__ __launch_bounds__(256) void k_xty(const float* __restrict__ X, int P,
     for (int k = 0; k < 8; ++k) { const int oi = threadIdx.x + 256 * k; if (oi < nout) out[oi] = acc[k]; }
     if ((int)threadIdx.x < P) out[nout + threadIdx.x] = cs;
 }
-__global__ __launch_bounds__(256) void k_xty_reduce(const float* __restrict__ partial, int nblk, int n, int n_mat, float* __restrict__ out_mat,
-                                                    float* __restrict__ out_col) {
+// (capacity form: the live block count comes from the device count -- the same blocks in the same order as the exact call on that many rows)
+__global__ __launch_bounds__(256) void k_xty_reduce(const float* __restrict__ partial, int nblk, uint32_t M_rows, const int32_t* __restrict__ d_count,
+                                                    int n, int n_mat, float* __restrict__ out_mat, float* __restrict__ out_col) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
+    if (d_count) nblk = (int)((cap_live(M_rows, d_count) + XTY_ROWS - 1) / XTY_ROWS);
     // eight independent chains (fixed order: deterministic): one chain waits out a load per partial
     float a8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     int b = 0;
@@ -404,14 +413,47 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ w, const float
     w[i] -= lr * (a / bc1) / (sqrtf(b / bc2) + eps);
 }
 
+// the same update with the step counter and a skip flag on the device: *d_skip != 0 leaves everything untouched.  *d_step counts the
+// steps already taken; the bias corrections of step *d_step + 1 are computed once per block in the host's form, 1 - powf(beta, step).
+// Same formula, but the device's powf and the host's are two libraries: exact at step 1 (beta^1), within their rounding of each other after.
+__global__ __launch_bounds__(256) void k_adam_n(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m1, float* __restrict__ m2,
+                                                size_t n, float lr, float b1, float b2, float eps, const int32_t* __restrict__ d_step,
+                                                const int32_t* __restrict__ d_skip) {
+    if (*d_skip != 0) return;
+    __shared__ float bc[2];
+    if (threadIdx.x == 0) {
+        const float step = (float)(*d_step + 1);
+        bc[0] = 1.0f - powf(b1, step);
+        bc[1] = 1.0f - powf(b2, step);
+    }
+    __syncthreads();
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float bc1 = bc[0], bc2 = bc[1];
+    const float gi = g[i];
+    const float a = b1 * m1[i] + (1.0f - b1) * gi;
+    const float b = b2 * m2[i] + (1.0f - b2) * gi * gi;
+    m1[i] = a; m2[i] = b;
+    w[i] -= lr * (a / bc1) / (sqrtf(b / bc2) + eps);
+}
+__global__ void k_adam_advance(int32_t* __restrict__ d_step, const int32_t* __restrict__ d_skip) {
+    if (blockIdx.x == 0 && threadIdx.x == 0 && *d_skip == 0) *d_step += 1;
+}
+
+// (capacity form, d_count != nullptr: M is the capacity; a row at or beyond the live count loads nothing and gets zeros)
 template <int NL>
 __global__ __launch_bounds__(NB, 4) void k_point_decode2(DecoderParams p, const float* __restrict__ xyz, uint32_t M,
-                                                         float* __restrict__ sigmas, float* __restrict__ rgbs) {
+                                                         const int32_t* __restrict__ d_count, float* __restrict__ sigmas, float* __restrict__ rgbs) {
     __shared__ __attribute__((aligned(16))) float w1t[HID * 2 * NL];
     stage_w1<NL>(p, w1t);
     __syncthreads();
     const uint32_t i = blockIdx.x * NB + threadIdx.x;
     if (i >= M) return;
+    if (i >= cap_live(M, d_count)) {
+        sigmas[i] = 0.0f;
+        if (rgbs) reinterpret_cast<float3p*>(rgbs)[i] = float3p{0.0f, 0.0f, 0.0f};
+        return;
+    }
     const float3p q = reinterpret_cast<const float3p*>(xyz)[i];
     float s, c[3];
     decode_point2<NL>(p, w1t, q.x, q.y, q.z, s, c);
@@ -460,9 +502,14 @@ __global__ __launch_bounds__(NB, 3) void k_render_rays2(DecoderParams dp, MarchP
 
 template <int NL>
 __global__ __launch_bounds__(NB) void k_point_decode(DecoderParams p, const float* __restrict__ xyz, uint32_t M,
-                                                     float* __restrict__ sigmas, float* __restrict__ rgbs) {
+                                                     const int32_t* __restrict__ d_count, float* __restrict__ sigmas, float* __restrict__ rgbs) {
     const uint32_t i = blockIdx.x * NB + threadIdx.x;
     if (i >= M) return;
+    if (i >= cap_live(M, d_count)) {
+        sigmas[i] = 0.0f;
+        if (rgbs) reinterpret_cast<float3p*>(rgbs)[i] = float3p{0.0f, 0.0f, 0.0f};
+        return;
+    }
     const float3p q = reinterpret_cast<const float3p*>(xyz)[i];
     float s, c[3];
     decode_point<NL>(p, q.x, q.y, q.z, s, c);
@@ -633,13 +680,13 @@ int fill_decoder(DecoderParams& p, const float* table, int n_levels, const float
 
 extern "C" {
 
-int mve_hashgrid_mlp_decode(const float* d_xyz, uint32_t M, const float* d_table, int n_levels, const float* level_scale,
-                            const uint32_t* level_res, const uint32_t* level_offset, const uint32_t* level_size,
-                            const float* d_w1, const float* d_b1, const float* d_w2, const float* d_b2, int hidden, float bound,
-                            float blob_density, float blob_radius, float sigmoid_saturation, float* d_sigmas, float* d_rgbs,
-                            void* stream) {
+// shared body of mve_hashgrid_mlp_decode (d_count == nullptr) and mve_hashgrid_mlp_decode_n (M = capacity)
+static int decode_impl(const char* who, const float* d_xyz, uint32_t M, const int32_t* d_count, const float* d_table, int n_levels,
+                       const float* level_scale, const uint32_t* level_res, const uint32_t* level_offset, const uint32_t* level_size,
+                       const float* d_w1, const float* d_b1, const float* d_w2, const float* d_b2, int hidden, float bound,
+                       float blob_density, float blob_radius, float sigmoid_saturation, float* d_sigmas, float* d_rgbs, void* stream) {
     if (M == 0) return MVE_OK;
-    MVE_CHECK(d_xyz && d_sigmas, MVE_ERR_ARG, "hashgrid_mlp_decode: null pointer");
+    MVE_CHECK(d_xyz && d_sigmas, MVE_ERR_ARG, "%s: null pointer", who);
     DecoderParams p;
     int rc = fill_decoder(p, d_table, n_levels, level_scale, level_res, level_offset, level_size, d_w1, d_b1, d_w2, d_b2, hidden,
                           bound, blob_density, blob_radius, sigmoid_saturation);
@@ -647,14 +694,33 @@ int mve_hashgrid_mlp_decode(const float* d_xyz, uint32_t M, const float* d_table
     const unsigned grid = mve_cdiv(M, NB);
     hipStream_t s = (hipStream_t)stream;
     if (hidden == HID) {
-        if (n_levels == 12) k_point_decode2<12><<<grid, NB, 0, s>>>(p, d_xyz, M, d_sigmas, d_rgbs);
-        else if (n_levels == 14) k_point_decode2<14><<<grid, NB, 0, s>>>(p, d_xyz, M, d_sigmas, d_rgbs);
-        else k_point_decode2<16><<<grid, NB, 0, s>>>(p, d_xyz, M, d_sigmas, d_rgbs);
-    } else if (n_levels == 12) k_point_decode<12><<<grid, NB, 0, s>>>(p, d_xyz, M, d_sigmas, d_rgbs);
-    else if (n_levels == 14) k_point_decode<14><<<grid, NB, 0, s>>>(p, d_xyz, M, d_sigmas, d_rgbs);
-    else k_point_decode<16><<<grid, NB, 0, s>>>(p, d_xyz, M, d_sigmas, d_rgbs);
+        if (n_levels == 12) k_point_decode2<12><<<grid, NB, 0, s>>>(p, d_xyz, M, d_count, d_sigmas, d_rgbs);
+        else if (n_levels == 14) k_point_decode2<14><<<grid, NB, 0, s>>>(p, d_xyz, M, d_count, d_sigmas, d_rgbs);
+        else k_point_decode2<16><<<grid, NB, 0, s>>>(p, d_xyz, M, d_count, d_sigmas, d_rgbs);
+    } else if (n_levels == 12) k_point_decode<12><<<grid, NB, 0, s>>>(p, d_xyz, M, d_count, d_sigmas, d_rgbs);
+    else if (n_levels == 14) k_point_decode<14><<<grid, NB, 0, s>>>(p, d_xyz, M, d_count, d_sigmas, d_rgbs);
+    else k_point_decode<16><<<grid, NB, 0, s>>>(p, d_xyz, M, d_count, d_sigmas, d_rgbs);
     MVE_LAUNCH_CHECK();
     return MVE_OK;
+}
+
+int mve_hashgrid_mlp_decode(const float* d_xyz, uint32_t M, const float* d_table, int n_levels, const float* level_scale,
+                            const uint32_t* level_res, const uint32_t* level_offset, const uint32_t* level_size,
+                            const float* d_w1, const float* d_b1, const float* d_w2, const float* d_b2, int hidden, float bound,
+                            float blob_density, float blob_radius, float sigmoid_saturation, float* d_sigmas, float* d_rgbs,
+                            void* stream) {
+    return decode_impl("hashgrid_mlp_decode", d_xyz, M, nullptr, d_table, n_levels, level_scale, level_res, level_offset, level_size, d_w1, d_b1,
+                       d_w2, d_b2, hidden, bound, blob_density, blob_radius, sigmoid_saturation, d_sigmas, d_rgbs, stream);
+}
+
+int mve_hashgrid_mlp_decode_n(const float* d_xyz, uint32_t capacity, const int32_t* d_count, const float* d_table, int n_levels,
+                              const float* level_scale, const uint32_t* level_res, const uint32_t* level_offset, const uint32_t* level_size,
+                              const float* d_w1, const float* d_b1, const float* d_w2, const float* d_b2, int hidden, float bound,
+                              float blob_density, float blob_radius, float sigmoid_saturation, float* d_sigmas, float* d_rgbs,
+                              void* stream) {
+    MVE_CHECK(d_count, MVE_ERR_ARG, "hashgrid_mlp_decode_n: null count");
+    return decode_impl("hashgrid_mlp_decode_n", d_xyz, capacity, d_count, d_table, n_levels, level_scale, level_res, level_offset, level_size, d_w1,
+                       d_b1, d_w2, d_b2, hidden, bound, blob_density, blob_radius, sigmoid_saturation, d_sigmas, d_rgbs, stream);
 }
 
 size_t mve_hashgrid_mlp_backward_workspace_bytes(uint32_t M, int n_levels) {
@@ -662,14 +728,15 @@ size_t mve_hashgrid_mlp_backward_workspace_bytes(uint32_t M, int n_levels) {
     return sizeof(float) * ((size_t)M * (HID + HID + 2 * n_levels + 4) + nblk * (size_t)(HID * 2 * n_levels + HID + 4 * HID + 4) + 64);
 }
 
-int mve_hashgrid_mlp_backward(const float* d_xyz, uint32_t M, const float* d_table, int n_levels, const float* level_scale,
+// shared body of mve_hashgrid_mlp_backward (d_count == nullptr) and mve_hashgrid_mlp_backward_n (M = capacity: sizes the workspace and the grids)
+static int backward_impl(const char* who, const float* d_xyz, uint32_t M, const int32_t* d_count, const float* d_table, int n_levels, const float* level_scale,
                               const uint32_t* level_res, const uint32_t* level_offset, const uint32_t* level_size, const float* d_w1,
                               const float* d_b1, const float* d_w2, const float* d_b2, int hidden, float bound, float blob_density,
                               float blob_radius, float sigmoid_saturation, const float* d_grad_sigma, const float* d_grad_rgb,
                               float* d_grad_table, float* d_grad_w1, float* d_grad_b1, float* d_grad_w2, float* d_grad_b2,
                               void* d_workspace, size_t workspace_bytes, void* stream) {
-    MVE_CHECK(d_grad_table && d_grad_w1 && d_grad_b1 && d_grad_w2 && d_grad_b2, MVE_ERR_ARG, "hashgrid_mlp_backward: null gradient output");
-    MVE_CHECK(hidden == HID, MVE_ERR_ARG, "hashgrid_mlp_backward: hidden width must be %d", HID);
+    MVE_CHECK(d_grad_table && d_grad_w1 && d_grad_b1 && d_grad_w2 && d_grad_b2, MVE_ERR_ARG, "%s: null gradient output", who);
+    MVE_CHECK(hidden == HID, MVE_ERR_ARG, "%s: hidden width must be %d", who, HID);
     hipStream_t s = (hipStream_t)stream;
     const int nin = 2 * n_levels;
     if (M == 0) {
@@ -679,8 +746,8 @@ int mve_hashgrid_mlp_backward(const float* d_xyz, uint32_t M, const float* d_tab
         MVE_HIP(hipMemsetAsync(d_grad_b2, 0, sizeof(float) * 4, s));
         return MVE_OK;
     }
-    MVE_CHECK(d_xyz && d_grad_sigma && d_workspace, MVE_ERR_ARG, "hashgrid_mlp_backward: null pointer");
-    MVE_CHECK(workspace_bytes >= mve_hashgrid_mlp_backward_workspace_bytes(M, n_levels), MVE_ERR_NOMEM, "hashgrid_mlp_backward: workspace too small");
+    MVE_CHECK(d_xyz && d_grad_sigma && d_workspace, MVE_ERR_ARG, "%s: null pointer", who);
+    MVE_CHECK(workspace_bytes >= mve_hashgrid_mlp_backward_workspace_bytes(M, n_levels), MVE_ERR_NOMEM, "%s: workspace too small", who);
     DecoderParams p;
     int rc = fill_decoder(p, d_table, n_levels, level_scale, level_res, level_offset, level_size, d_w1, d_b1, d_w2, d_b2, hidden,
                           bound, blob_density, blob_radius, sigmoid_saturation);
@@ -692,22 +759,45 @@ int mve_hashgrid_mlp_backward(const float* d_xyz, uint32_t M, const float* d_tab
     float* dout = ws; ws += (size_t)M * 4;
     float* part = ws;
     const unsigned grid = mve_cdiv(M, NB);
-    if (n_levels == 12) k_decode_backward<12><<<grid, NB, 0, s>>>(p, d_xyz, M, d_grad_sigma, d_grad_rgb, d_grad_table, dh, hr, enc, dout);
-    else if (n_levels == 14) k_decode_backward<14><<<grid, NB, 0, s>>>(p, d_xyz, M, d_grad_sigma, d_grad_rgb, d_grad_table, dh, hr, enc, dout);
-    else k_decode_backward<16><<<grid, NB, 0, s>>>(p, d_xyz, M, d_grad_sigma, d_grad_rgb, d_grad_table, dh, hr, enc, dout);
+    if (n_levels == 12) k_decode_backward<12><<<grid, NB, 0, s>>>(p, d_xyz, M, d_count, d_grad_sigma, d_grad_rgb, d_grad_table, dh, hr, enc, dout);
+    else if (n_levels == 14) k_decode_backward<14><<<grid, NB, 0, s>>>(p, d_xyz, M, d_count, d_grad_sigma, d_grad_rgb, d_grad_table, dh, hr, enc, dout);
+    else k_decode_backward<16><<<grid, NB, 0, s>>>(p, d_xyz, M, d_count, d_grad_sigma, d_grad_rgb, d_grad_table, dh, hr, enc, dout);
     MVE_LAUNCH_CHECK();
     const int nblk = (int)mve_cdiv(M, XTY_ROWS);
     // dW1 [64][2NL] = dh^T enc, db1 = colsum(dh)
-    k_xty<<<nblk, 256, 0, s>>>(dh, HID, enc, nin, M, part);
+    k_xty<<<nblk, 256, 0, s>>>(dh, HID, enc, nin, M, d_count, part);
     MVE_LAUNCH_CHECK();
-    k_xty_reduce<<<mve_cdiv(HID * nin + HID, 256), 256, 0, s>>>(part, nblk, HID * nin + HID, HID * nin, d_grad_w1, d_grad_b1);
+    k_xty_reduce<<<mve_cdiv(HID * nin + HID, 256), 256, 0, s>>>(part, nblk, M, d_count, HID * nin + HID, HID * nin, d_grad_w1, d_grad_b1);
     MVE_LAUNCH_CHECK();
     // dW2 [4][64] = do^T relu(h), db2 = colsum(do)
-    k_xty<<<nblk, 256, 0, s>>>(dout, 4, hr, HID, M, part);
+    k_xty<<<nblk, 256, 0, s>>>(dout, 4, hr, HID, M, d_count, part);
     MVE_LAUNCH_CHECK();
-    k_xty_reduce<<<mve_cdiv(4 * HID + 4, 256), 256, 0, s>>>(part, nblk, 4 * HID + 4, 4 * HID, d_grad_w2, d_grad_b2);
+    k_xty_reduce<<<mve_cdiv(4 * HID + 4, 256), 256, 0, s>>>(part, nblk, M, d_count, 4 * HID + 4, 4 * HID, d_grad_w2, d_grad_b2);
     MVE_LAUNCH_CHECK();
     return MVE_OK;
+}
+
+int mve_hashgrid_mlp_backward(const float* d_xyz, uint32_t M, const float* d_table, int n_levels, const float* level_scale,
+                              const uint32_t* level_res, const uint32_t* level_offset, const uint32_t* level_size, const float* d_w1,
+                              const float* d_b1, const float* d_w2, const float* d_b2, int hidden, float bound, float blob_density,
+                              float blob_radius, float sigmoid_saturation, const float* d_grad_sigma, const float* d_grad_rgb,
+                              float* d_grad_table, float* d_grad_w1, float* d_grad_b1, float* d_grad_w2, float* d_grad_b2,
+                              void* d_workspace, size_t workspace_bytes, void* stream) {
+    return backward_impl("hashgrid_mlp_backward", d_xyz, M, nullptr, d_table, n_levels, level_scale, level_res, level_offset, level_size, d_w1, d_b1,
+                         d_w2, d_b2, hidden, bound, blob_density, blob_radius, sigmoid_saturation, d_grad_sigma, d_grad_rgb, d_grad_table,
+                         d_grad_w1, d_grad_b1, d_grad_w2, d_grad_b2, d_workspace, workspace_bytes, stream);
+}
+
+int mve_hashgrid_mlp_backward_n(const float* d_xyz, uint32_t capacity, const int32_t* d_count, const float* d_table, int n_levels,
+                                const float* level_scale, const uint32_t* level_res, const uint32_t* level_offset, const uint32_t* level_size,
+                                const float* d_w1, const float* d_b1, const float* d_w2, const float* d_b2, int hidden, float bound,
+                                float blob_density, float blob_radius, float sigmoid_saturation, const float* d_grad_sigma,
+                                const float* d_grad_rgb, float* d_grad_table, float* d_grad_w1, float* d_grad_b1, float* d_grad_w2,
+                                float* d_grad_b2, void* d_workspace, size_t workspace_bytes, void* stream) {
+    MVE_CHECK(d_count, MVE_ERR_ARG, "hashgrid_mlp_backward_n: null count");
+    return backward_impl("hashgrid_mlp_backward_n", d_xyz, capacity, d_count, d_table, n_levels, level_scale, level_res, level_offset, level_size,
+                         d_w1, d_b1, d_w2, d_b2, hidden, bound, blob_density, blob_radius, sigmoid_saturation, d_grad_sigma, d_grad_rgb,
+                         d_grad_table, d_grad_w1, d_grad_b1, d_grad_w2, d_grad_b2, d_workspace, workspace_bytes, stream);
 }
 
 int mve_adam_step(float* d_param, const float* d_grad, float* d_exp_avg, float* d_exp_avg_sq, size_t n, float lr, float beta1, float beta2,
@@ -716,6 +806,22 @@ int mve_adam_step(float* d_param, const float* d_grad, float* d_exp_avg, float* 
     MVE_CHECK(d_param && d_grad && d_exp_avg && d_exp_avg_sq && step >= 1, MVE_ERR_ARG, "adam_step: bad arguments");
     const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
     k_adam<<<mve_cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(d_param, d_grad, d_exp_avg, d_exp_avg_sq, n, lr, beta1, beta2, eps, bc1, bc2);
+    MVE_LAUNCH_CHECK();
+    return MVE_OK;
+}
+
+int mve_adam_step_n(float* d_param, const float* d_grad, float* d_exp_avg, float* d_exp_avg_sq, size_t n, float lr, float beta1, float beta2,
+                    float eps, const int32_t* d_step, const int32_t* d_skip, void* stream) {
+    if (n == 0) return MVE_OK;
+    MVE_CHECK(d_param && d_grad && d_exp_avg && d_exp_avg_sq && d_step && d_skip, MVE_ERR_ARG, "adam_step_n: bad arguments");
+    k_adam_n<<<mve_cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(d_param, d_grad, d_exp_avg, d_exp_avg_sq, n, lr, beta1, beta2, eps, d_step, d_skip);
+    MVE_LAUNCH_CHECK();
+    return MVE_OK;
+}
+
+int mve_adam_advance_n(int32_t* d_step, const int32_t* d_skip, void* stream) {
+    MVE_CHECK(d_step && d_skip, MVE_ERR_ARG, "adam_advance_n: null pointer");
+    k_adam_advance<<<1, 64, 0, (hipStream_t)stream>>>(d_step, d_skip);
     MVE_LAUNCH_CHECK();
     return MVE_OK;
 }

@@ -17,6 +17,8 @@
 // oracle/raymarching_oracle.c.
 #include "raymarch_core.h"
 
+#include "capacity_core.h"
+
 namespace {
 
 constexpr int kBlock = 256;              // 4 waves
@@ -392,42 +394,72 @@ __global__ __launch_bounds__(kBlock) void k_alive_scatter(const int32_t* __restr
 // train branch: cull samples whose composited weight is below a threshold and re-index the rays
 // (lib/models/decoders/base_volume_renderer.py:222-243: boolean-mask gathers + cumsum on the host side there)
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void k_cull_count(const float* __restrict__ weights, uint32_t M, float th,
-                                                       int32_t* __restrict__ block_sums) {
+// (d_count == nullptr: every one of the M rows is live, the exact form.  Otherwise M is the capacity and the live rows are [0, *d_count):
+// rows beyond it are never read, keep nothing, and the outputs' rows at and beyond the kept total are written as zeros.)
+__global__ __launch_bounds__(kBlock) void k_cull_count(const float* __restrict__ weights, uint32_t M, const int32_t* __restrict__ d_count,
+                                                       float th, int32_t* __restrict__ block_sums) {
     __shared__ int lds[kBlock / 64 + 1];
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    const int keep = (i < M && weights[i] > th) ? 1 : 0;
+    const uint32_t live = cap_live(M, d_count);
+    const int keep = (i < live && weights[i] > th) ? 1 : 0;
     int tot;
     (void)block_excl_scan<kBlock>(keep, &tot, lds);
     if (threadIdx.x == 0) block_sums[blockIdx.x] = tot;
 }
-__global__ __launch_bounds__(kBlock) void k_cull_scatter(const float* __restrict__ weights, uint32_t M, float th,
-                                                         const int32_t* __restrict__ block_bases, const int32_t* __restrict__ total,
+__global__ __launch_bounds__(kBlock) void k_cull_scatter(const float* __restrict__ weights, uint32_t M, const int32_t* __restrict__ d_count,
+                                                         float th, const int32_t* __restrict__ block_bases, const int32_t* __restrict__ total,
                                                          const float* __restrict__ xyzs, const float* __restrict__ dirs,
                                                          const float* __restrict__ ts, float* __restrict__ o_xyzs,
                                                          float* __restrict__ o_dirs, float* __restrict__ o_ts, int32_t* __restrict__ pref) {
     __shared__ int lds[kBlock / 64 + 1];
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    const int keep = (i < M && weights[i] > th) ? 1 : 0;
+    const uint32_t live = cap_live(M, d_count);
+    const int keep = (i < live && weights[i] > th) ? 1 : 0;
     int tot;
     const int ex = block_excl_scan<kBlock>(keep, &tot, lds);
     const int dst = block_bases[blockIdx.x] + ex;
-    if (i < M) pref[i] = dst;                 // = cumsum(mask)[i - 1], the reference's filt_inds[i]
-    if (i == 0) pref[M] = *total;
+    const int kept = *total;
+    if (i < M) pref[i] = i < live ? dst : kept;   // = cumsum(mask)[i - 1], the reference's filt_inds[i]
+    if (i == 0) pref[M] = kept;
     if (keep) {
         reinterpret_cast<float3p*>(o_xyzs)[dst] = reinterpret_cast<const float3p*>(xyzs)[i];
         reinterpret_cast<float3p*>(o_dirs)[dst] = reinterpret_cast<const float3p*>(dirs)[i];
         reinterpret_cast<float2p*>(o_ts)[dst] = reinterpret_cast<const float2p*>(ts)[i];
     }
+    if (d_count && i < M && i >= (uint32_t)kept) {   // zero tail (dst < kept for every kept sample: no row is written twice)
+        reinterpret_cast<float3p*>(o_xyzs)[i] = float3p{0.f, 0.f, 0.f};
+        reinterpret_cast<float3p*>(o_dirs)[i] = float3p{0.f, 0.f, 0.f};
+        reinterpret_cast<float2p*>(o_ts)[i] = float2p{0.f, 0.f};
+    }
 }
 __global__ __launch_bounds__(kBlock) void k_cull_rays(const int32_t* __restrict__ rays, uint32_t N, const int32_t* __restrict__ pref,
-                                                      int32_t* __restrict__ o_rays) {
+                                                      uint32_t M, const int32_t* __restrict__ d_count, int32_t* __restrict__ o_rays) {
     const uint32_t n = blockIdx.x * kBlock + threadIdx.x;
     if (n >= N) return;
     const int off = rays[2 * n], cnt = rays[2 * n + 1];
+    if (d_count) {   // a ray that did not fit keeps nothing and pref is not read past the live count
+        cap_cull_ray(off, cnt, cap_live(M, d_count), pref, o_rays + 2 * n, o_rays + 2 * n + 1);
+        return;
+    }
     const int a = pref[off], b = pref[off + cnt];
     o_rays[2 * n] = a;
     o_rays[2 * n + 1] = b - a;
+}
+
+// clamp step of the capacity form: marched total -> live count of whole rays that fit, sticky overflow flag
+__global__ __launch_bounds__(kBlock) void k_march_clamp(const int32_t* __restrict__ rays, uint32_t N, const int32_t* __restrict__ d_total,
+                                                        uint32_t capacity, int32_t* __restrict__ n_samples, int32_t* __restrict__ d_count,
+                                                        int32_t* __restrict__ d_overflow) {
+    const uint32_t n = blockIdx.x * kBlock + threadIdx.x;
+    if (n == 0) {
+        const int32_t total = *d_total;
+        n_samples[0] = total;
+        if (total < 0 || (uint32_t)total > capacity) *d_overflow = 1;
+        if (N == 0) { *d_count = 0; n_samples[1] = 0; }
+    }
+    if (n >= N) return;
+    int32_t count;
+    if (cap_clamp_decides(rays, n, N, capacity, &count)) { *d_count = count; n_samples[1] = count; }
 }
 
 // ---------------------------------------------------------------------------
@@ -663,30 +695,54 @@ int mve_compact_alive(const int32_t* rays_alive, uint32_t n_alive, int32_t* out,
 
 size_t mve_cull_scratch_bytes(uint32_t M) { return sizeof(int32_t) * ((size_t)mve_cdiv(M, kBlock) + 64); }
 
-int mve_cull_samples(const float* weights, uint32_t M, float threshold, const int32_t* rays, uint32_t N, const float* xyzs,
-                     const float* dirs, const float* ts, float* out_xyzs, float* out_dirs, float* out_ts, int32_t* out_rays,
-                     int32_t* pref /* [M + 1] */, int32_t* n_out, void* scratch, void* stream) {
-    MVE_CHECK(n_out && pref, MVE_ERR_ARG, "cull_samples: null n_out / pref");
+// shared body of mve_cull_samples (d_count == nullptr, M exact) and mve_cull_samples_n (M = capacity, live rows from the device)
+static int cull_samples_impl(const char* who, const float* weights, uint32_t M, const int32_t* d_count, float threshold, const int32_t* rays,
+                             uint32_t N, const float* xyzs, const float* dirs, const float* ts, float* out_xyzs, float* out_dirs, float* out_ts,
+                             int32_t* out_rays, int32_t* pref /* [M + 1] */, int32_t* n_out, void* scratch, void* stream) {
+    MVE_CHECK(n_out && pref, MVE_ERR_ARG, "%s: null n_out / pref", who);
     hipStream_t s = (hipStream_t)stream;
     if (M == 0) {
         MVE_HIP(hipMemsetAsync(n_out, 0, sizeof(int32_t), s));
         MVE_HIP(hipMemsetAsync(pref, 0, sizeof(int32_t), s));
     } else {
-        MVE_CHECK(weights && xyzs && dirs && ts && out_xyzs && out_dirs && out_ts && scratch, MVE_ERR_ARG, "cull_samples: null pointer");
+        MVE_CHECK(weights && xyzs && dirs && ts && out_xyzs && out_dirs && out_ts && scratch, MVE_ERR_ARG, "%s: null pointer", who);
         const uint32_t nblk = mve_cdiv(M, kBlock);
         int32_t* bs = (int32_t*)scratch;
-        k_cull_count<<<nblk, kBlock, 0, s>>>(weights, M, threshold, bs);
+        k_cull_count<<<nblk, kBlock, 0, s>>>(weights, M, d_count, threshold, bs);
         MVE_LAUNCH_CHECK();
         k_scan_block_sums<<<1, 1024, 0, s>>>(bs, nblk, n_out);
         MVE_LAUNCH_CHECK();
-        k_cull_scatter<<<nblk, kBlock, 0, s>>>(weights, M, threshold, bs, n_out, xyzs, dirs, ts, out_xyzs, out_dirs, out_ts, pref);
+        k_cull_scatter<<<nblk, kBlock, 0, s>>>(weights, M, d_count, threshold, bs, n_out, xyzs, dirs, ts, out_xyzs, out_dirs, out_ts, pref);
         MVE_LAUNCH_CHECK();
     }
     if (N) {
-        MVE_CHECK(rays && out_rays, MVE_ERR_ARG, "cull_samples: null rays");
-        k_cull_rays<<<mve_cdiv(N, kBlock), kBlock, 0, s>>>(rays, N, pref, out_rays);
+        MVE_CHECK(rays && out_rays, MVE_ERR_ARG, "%s: null rays", who);
+        k_cull_rays<<<mve_cdiv(N, kBlock), kBlock, 0, s>>>(rays, N, pref, M, d_count, out_rays);
         MVE_LAUNCH_CHECK();
     }
+    return MVE_OK;
+}
+
+int mve_cull_samples(const float* weights, uint32_t M, float threshold, const int32_t* rays, uint32_t N, const float* xyzs,
+                     const float* dirs, const float* ts, float* out_xyzs, float* out_dirs, float* out_ts, int32_t* out_rays,
+                     int32_t* pref /* [M + 1] */, int32_t* n_out, void* scratch, void* stream) {
+    return cull_samples_impl("cull_samples", weights, M, nullptr, threshold, rays, N, xyzs, dirs, ts, out_xyzs, out_dirs, out_ts, out_rays, pref,
+                             n_out, scratch, stream);
+}
+
+int mve_cull_samples_n(const float* weights, uint32_t capacity, const int32_t* d_count, float threshold, const int32_t* rays, uint32_t N,
+                       const float* xyzs, const float* dirs, const float* ts, float* out_xyzs, float* out_dirs, float* out_ts,
+                       int32_t* out_rays, int32_t* pref /* [capacity + 1] */, int32_t* n_out, void* scratch, void* stream) {
+    MVE_CHECK(d_count && d_count != n_out, MVE_ERR_ARG, "cull_samples_n: the input count must be a device int32 other than n_out");
+    return cull_samples_impl("cull_samples_n", weights, capacity, d_count, threshold, rays, N, xyzs, dirs, ts, out_xyzs, out_dirs, out_ts,
+                             out_rays, pref, n_out, scratch, stream);
+}
+
+int mve_march_rays_train_clamp(const int32_t* rays, uint32_t N, const int32_t* d_total, uint32_t capacity, int32_t* d_n_samples,
+                               int32_t* d_count, int32_t* d_overflow, void* stream) {
+    MVE_CHECK(d_total && d_n_samples && d_count && d_overflow && (N == 0 || rays), MVE_ERR_ARG, "march_rays_train_clamp: null pointer");
+    k_march_clamp<<<N ? mve_cdiv(N, kBlock) : 1, kBlock, 0, (hipStream_t)stream>>>(rays, N, d_total, capacity, d_n_samples, d_count, d_overflow);
+    MVE_LAUNCH_CHECK();
     return MVE_OK;
 }
 

@@ -9,6 +9,7 @@
 
 #include "recon_loss_core.h"
 #include "mesh_loss_core.h"
+#include "capacity_core.h"
 
 namespace {
 
@@ -74,13 +75,16 @@ __global__ __launch_bounds__(NT) void k_rl_tv(RlParams q, const float* __restric
 }
 
 // forward (g_w == nullptr): entropy partials; backward: per-sample gradient
+// (capacity form, d_count != nullptr: M is the capacity; a sample at or beyond the live count adds nothing and its gradient is zero)
 __global__ __launch_bounds__(NT) void k_rl_entropy(RlParams q, const float* __restrict__ weights, const float* __restrict__ ts, unsigned M,
-                                                   const float* __restrict__ d_gl, Ws w, float* __restrict__ g_w) {
+                                                   const int32_t* __restrict__ d_count, const float* __restrict__ d_gl, Ws w,
+                                                   float* __restrict__ g_w) {
     __shared__ float sh[NT];
     const unsigned i = blockIdx.x * NT + threadIdx.x;
     const float gl = d_gl ? *d_gl : 1.0f;
     float v = 0.f;
-    if (i < M) v = rl_entropy_sample(q, weights[i], ts[2 * i + 1], gl, g_w ? g_w + i : nullptr);
+    if (i < cap_live(M, d_count)) v = rl_entropy_sample(q, weights[i], ts[2 * i + 1], gl, g_w ? g_w + i : nullptr);
+    else if (i < M && g_w) g_w[i] = 0.f;
     if (g_w) return;
     const float s = mve_block_sum<NT>(v, sh);
     if (threadIdx.x == 0)
@@ -226,8 +230,9 @@ size_t mve_recon_loss_workspace_bytes(int P, int ps, uint32_t M) {
     return ws_floats((size_t)P * ps * ps, M) * sizeof(float);
 }
 
-int mve_recon_loss_forward(const MveReconLossDesc* d, void* d_ws, size_t ws_bytes, float* d_losses, float* d_out_rgbs, float* d_out_normals,
-                           void* stream) {
+// shared bodies of the exact entry points (d_count == nullptr) and the capacity forms (desc->M = capacity, live samples from the device)
+static int recon_forward_impl(const MveReconLossDesc* d, const int32_t* d_count, void* d_ws, size_t ws_bytes, float* d_losses, float* d_out_rgbs,
+                              float* d_out_normals, void* stream) {
     if (int rc = check_desc(d, "recon_loss_forward")) return rc;
     MVE_CHECK(d_ws && d_losses && d_out_rgbs && d_out_normals, MVE_ERR_ARG, "recon_loss_forward: null output");
     const size_t N = (size_t)d->P * d->ps * d->ps;
@@ -244,7 +249,7 @@ int mve_recon_loss_forward(const MveReconLossDesc* d, void* d_ws, size_t ws_byte
     k_rl_tv<<<w.nbp, NT, 0, s>>>(q, d->d_target_n, w);
     MVE_LAUNCH_CHECK();
     if (w.nbs) {
-        k_rl_entropy<<<w.nbs, NT, 0, s>>>(q, d->d_weights, d->d_ts, d->M, nullptr, w, nullptr);
+        k_rl_entropy<<<w.nbs, NT, 0, s>>>(q, d->d_weights, d->d_ts, d->M, d_count, nullptr, w, nullptr);
         MVE_LAUNCH_CHECK();
     }
     k_rl_reduce<<<1, NT, 0, s>>>(w, d_losses);
@@ -252,8 +257,20 @@ int mve_recon_loss_forward(const MveReconLossDesc* d, void* d_ws, size_t ws_byte
     return MVE_OK;
 }
 
-int mve_recon_loss_backward(const MveReconLossDesc* d, void* d_ws, size_t ws_bytes, const float* d_g_out_rgbs, const float* d_g_out_normals,
-                            const float* d_g_loss, float* d_g_image, float* d_g_weights_sum, float* d_g_depth, float* d_g_weights, void* stream) {
+int mve_recon_loss_forward(const MveReconLossDesc* d, void* d_ws, size_t ws_bytes, float* d_losses, float* d_out_rgbs, float* d_out_normals,
+                           void* stream) {
+    return recon_forward_impl(d, nullptr, d_ws, ws_bytes, d_losses, d_out_rgbs, d_out_normals, stream);
+}
+
+int mve_recon_loss_forward_n(const MveReconLossDesc* d, const int32_t* d_count, void* d_ws, size_t ws_bytes, float* d_losses, float* d_out_rgbs,
+                             float* d_out_normals, void* stream) {
+    MVE_CHECK(d_count, MVE_ERR_ARG, "recon_loss_forward_n: null count");
+    return recon_forward_impl(d, d_count, d_ws, ws_bytes, d_losses, d_out_rgbs, d_out_normals, stream);
+}
+
+static int recon_backward_impl(const MveReconLossDesc* d, const int32_t* d_count, void* d_ws, size_t ws_bytes, const float* d_g_out_rgbs,
+                               const float* d_g_out_normals, const float* d_g_loss, float* d_g_image, float* d_g_weights_sum, float* d_g_depth,
+                               float* d_g_weights, void* stream) {
     if (int rc = check_desc(d, "recon_loss_backward")) return rc;
     MVE_CHECK(d_ws && d_g_image && d_g_weights_sum && d_g_depth && (d->M == 0 || d_g_weights), MVE_ERR_ARG, "recon_loss_backward: null output");
     const size_t N = (size_t)d->P * d->ps * d->ps;
@@ -268,10 +285,24 @@ int mve_recon_loss_backward(const MveReconLossDesc* d, void* d_ws, size_t ws_byt
     k_rl_depth_bwd<<<w.nbp, NT, 0, s>>>(q, *d, w, d_g_loss, d_g_weights_sum, d_g_depth);
     MVE_LAUNCH_CHECK();
     if (w.nbs) {
-        k_rl_entropy<<<w.nbs, NT, 0, s>>>(q, d->d_weights, d->d_ts, d->M, d_g_loss, w, d_g_weights);
+        k_rl_entropy<<<w.nbs, NT, 0, s>>>(q, d->d_weights, d->d_ts, d->M, d_count, d_g_loss, w, d_g_weights);
         MVE_LAUNCH_CHECK();
     }
     return MVE_OK;
+}
+
+int mve_recon_loss_backward(const MveReconLossDesc* d, void* d_ws, size_t ws_bytes, const float* d_g_out_rgbs, const float* d_g_out_normals,
+                            const float* d_g_loss, float* d_g_image, float* d_g_weights_sum, float* d_g_depth, float* d_g_weights, void* stream) {
+    return recon_backward_impl(d, nullptr, d_ws, ws_bytes, d_g_out_rgbs, d_g_out_normals, d_g_loss, d_g_image, d_g_weights_sum, d_g_depth, d_g_weights,
+                               stream);
+}
+
+int mve_recon_loss_backward_n(const MveReconLossDesc* d, const int32_t* d_count, void* d_ws, size_t ws_bytes, const float* d_g_out_rgbs,
+                              const float* d_g_out_normals, const float* d_g_loss, float* d_g_image, float* d_g_weights_sum, float* d_g_depth,
+                              float* d_g_weights, void* stream) {
+    MVE_CHECK(d_count, MVE_ERR_ARG, "recon_loss_backward_n: null count");
+    return recon_backward_impl(d, d_count, d_ws, ws_bytes, d_g_out_rgbs, d_g_out_normals, d_g_loss, d_g_image, d_g_weights_sum, d_g_depth, d_g_weights,
+                               stream);
 }
 
 size_t mve_mesh_loss_workspace_bytes(int n, int size) {

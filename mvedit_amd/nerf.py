@@ -56,6 +56,23 @@ class _PointDecodeFn(torch.autograd.Function):
         return None, None, g['table'], g['w1'], g['b1'], g['w2'], g['b2']
 
 
+class _PointDecodeNFn(torch.autograd.Function):
+    """Capacity form of `_PointDecodeFn`: xyzs has `capacity` rows of which `count` (device int32 [1]) are live; nothing is read on the host."""
+
+    @staticmethod
+    def forward(ctx, dec, xyzs, count, table, w1, b1, w2, b2):
+        ctx.dec = dec
+        ctx.save_for_backward(xyzs, count)
+        sigmas, rgbs = dec.point_decode_n(xyzs, count)
+        return sigmas, rgbs
+
+    @staticmethod
+    def backward(ctx, g_sigma, g_rgb):
+        xyzs, count = ctx.saved_tensors
+        g = ctx.dec.point_decode_backward_n(xyzs, count, g_sigma.contiguous(), g_rgb.contiguous())
+        return None, None, None, g['table'], g['w1'], g['b1'], g['w2'], g['b2']
+
+
 class INGPDecoderParams:
     """Device-resident state of an iNGPDecoder (hash table + MLP) in the layout the kernels read."""
 
@@ -98,6 +115,23 @@ class INGPDecoderParams:
                       _lib.stream_ptr(self.device))
         return sigmas, rgbs
 
+    def _count_arg(self, count):
+        assert count.is_cuda and count.dtype == torch.int32 and count.numel() == 1, 'count: one int32 on the device'
+        return _lib.ptr(count)
+
+    def point_decode_n(self, xyzs, count, density_only=False):
+        """Capacity form of `point_decode`: xyzs [capacity, 3], `count` (device int32 [1]) live rows; the rows at and beyond the count come
+        out as zeros.  No host read."""
+        xyzs = xyzs.to(self.device, torch.float32).contiguous().view(-1, 3)
+        M = xyzs.shape[0]
+        sigmas = torch.empty(M, dtype=torch.float32, device=self.device)
+        rgbs = None if density_only else torch.empty(M, 3, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.call('mve_hashgrid_mlp_decode_n', _lib.ptr(xyzs), M, self._count_arg(count), *self._grid_args(), *self._mlp_args(), self.bound,
+                      self.blob_density, self.blob_radius, self.sigmoid_saturation, _lib.ptr(sigmas), _lib.ptr(rgbs),
+                      _lib.stream_ptr(self.device))
+        return sigmas, rgbs
+
     # reconstruct step: gradients and optimiser (SURVEY section 8(f) rank 1) -------------------------------------------------
     def parameters(self):
         return dict(table=self.table, w1=self.w1, b1=self.b1, w2=self.w2, b2=self.b2)
@@ -119,13 +153,64 @@ class INGPDecoderParams:
                       _lib.ptr(grads['b1']), _lib.ptr(grads['w2']), _lib.ptr(grads['b2']), _lib.ptr(ws), nbytes, _lib.stream_ptr(self.device))
         return grads
 
+    def point_decode_backward_n(self, xyzs, count, grad_sigmas, grad_rgbs=None, grads=None):
+        """Capacity form of `point_decode_backward`: rows at and beyond `count` (device int32 [1]) contribute nothing.  The MLP gradients
+        equal the exact call on the first `count` rows bit for bit."""
+        xyzs = xyzs.to(self.device, torch.float32).contiguous().view(-1, 3)
+        M = xyzs.shape[0]
+        gs = grad_sigmas.to(self.device, torch.float32).contiguous().view(-1)
+        gr = grad_rgbs.to(self.device, torch.float32).contiguous().view(-1, 3) if grad_rgbs is not None else None
+        assert gs.shape[0] == M and (gr is None or gr.shape[0] == M)
+        if grads is None:
+            grads = {k: torch.zeros_like(v) for k, v in self.parameters().items()}
+        nbytes = _lib.raw('mve_hashgrid_mlp_backward_workspace_bytes')(M, self.n_levels)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.call('mve_hashgrid_mlp_backward_n', _lib.ptr(xyzs), M, self._count_arg(count), *self._grid_args(), *self._mlp_args(), self.bound,
+                      self.blob_density, self.blob_radius, self.sigmoid_saturation, _lib.ptr(gs), _lib.ptr(gr), _lib.ptr(grads['table']),
+                      _lib.ptr(grads['w1']), _lib.ptr(grads['b1']), _lib.ptr(grads['w2']), _lib.ptr(grads['b2']), _lib.ptr(ws), nbytes,
+                      _lib.stream_ptr(self.device))
+        return grads
+
+    def point_decode_autograd_n(self, xyzs, count):
+        """Capacity form of `point_decode_autograd`."""
+        return _PointDecodeNFn.apply(self, xyzs, count, self.table, self.w1, self.b1, self.w2, self.b2)
+
     def point_decode_autograd(self, xyzs):
         """point_decode whose outputs carry autograd history w.r.t. parameters(): mark the parameter tensors with
         requires_grad_(True) and use any torch optimiser on them, as the reference's nerf_optim does with tinycudann modules."""
         return _PointDecodeFn.apply(self, xyzs, self.table, self.w1, self.b1, self.w2, self.b2)
 
-    def adam_step(self, grads, state, lr=1e-2, betas=(0.9, 0.999), eps=1e-15):
-        """One torch.optim.Adam step on every parameter, in place.  `state` is a dict the caller keeps between steps."""
+    def adam_state(self):
+        """A zeroed optimiser state for `adam_step(..., skip_if=flag)`: both moments of every parameter and the step counter, all on
+        the device."""
+        state = {k: (torch.zeros_like(w), torch.zeros_like(w)) for k, w in self.parameters().items()}
+        state['step'] = torch.zeros(1, dtype=torch.int32, device=self.device)
+        return state
+
+    def adam_step(self, grads, state, lr=1e-2, betas=(0.9, 0.999), eps=1e-15, skip_if=None):
+        """One torch.optim.Adam step on every parameter, in place.  `state` is a dict the caller keeps between steps.
+
+        skip_if (device int32 [1], e.g. the `overflow` of a capacity forward): the step counter lives on the device (state['step'],
+        int32 [1]) and the whole step -- parameters, moments, counter -- is left undone when the flag is non-zero.  No host read."""
+        if skip_if is not None:
+            assert skip_if.is_cuda and skip_if.dtype == torch.int32 and skip_if.numel() == 1, 'skip_if: one int32 on the device'
+            if 'step' not in state:
+                state['step'] = torch.zeros(1, dtype=torch.int32, device=self.device)
+            if not torch.is_tensor(state['step']):
+                raise ValueError('this optimiser state counts its steps on the host: use one state per mode')
+            with torch.cuda.device(self.device):
+                for k, w in self.parameters().items():
+                    if k not in state:
+                        state[k] = (torch.zeros_like(w), torch.zeros_like(w))
+                    m1, m2 = state[k]
+                    _lib.call('mve_adam_step_n', _lib.ptr(w), _lib.ptr(grads[k]), _lib.ptr(m1), _lib.ptr(m2), w.numel(), float(lr),
+                              float(betas[0]), float(betas[1]), float(eps), _lib.ptr(state['step']), _lib.ptr(skip_if),
+                              _lib.stream_ptr(self.device))
+                _lib.call('mve_adam_advance_n', _lib.ptr(state['step']), _lib.ptr(skip_if), _lib.stream_ptr(self.device))
+            return state
+        if torch.is_tensor(state.get('step', 0)):
+            raise ValueError('this optimiser state counts its steps on the device: pass skip_if')
         state['step'] = state.get('step', 0) + 1
         with torch.cuda.device(self.device):
             for k, w in self.parameters().items():
@@ -278,11 +363,28 @@ class VolumeRenderer:
         rm.packbits(density_grid, thresh, density_bitfield)
         return iter_density + 1, thresh
 
-    def forward(self, rays_o, rays_d, density_bitfield, grid_size, dt_gamma=0.0, perturb=False, noises=None):
+    def forward(self, rays_o, rays_d, density_bitfield, grid_size, dt_gamma=0.0, perturb=False, noises=None, capacity=None):
         """rays_o, rays_d [N,3] of one scene.  Returns the reference's result dict (weights, weights_sum, depth, image, rays,
-        ts; lists of one entry where the reference returns per-scene lists)."""
+        ts; lists of one entry where the reference returns per-scene lists).
+
+        capacity (training mode only; None = the exact form above, unchanged): a number of samples the CALLER chooses.  The sample
+        tensors (`weights`, `ts`) then have `capacity` rows whatever the rays meet, rows beyond the live samples are zeros, and the dict
+        gains two device tensors: `n_samples` (int32 [2]: samples marched, samples kept after culling) and `overflow` (int32 [1]).
+        Nothing inside reads a count on the host, so the host runs ahead of the device.  Intended protocol:
+          * pass `n_samples` to `nerf_optim_loss(..., n_samples=n_samples)` and `overflow` to `adam_step(..., skip_if=overflow)`;
+          * read `n_samples` / `overflow` only where the loop synchronises anyway, e.g. at the `update_extra_state` interval;
+          * every forward returns fresh `n_samples` / `overflow` tensors.  overflow != 0 means this iteration marched more samples than
+            the capacity: the rays that did not fit rendered as empty and, with `skip_if`, its optimiser step was skipped.  To learn
+            of an overflow in ANY iteration since the last look, fold the flags on the device (`seen.copy_(torch.maximum(seen,
+            overflow))`); then grow the capacity (n_samples[0] is the marched total, also when it overflowed) and continue."""
         from . import raymarching as rm
         dec = self.decoder
+        if capacity is not None:
+            if not self.training:
+                raise ValueError('capacity applies to the training branch only (the eval branch keeps no samples)')
+            if int(capacity) <= 0:
+                raise ValueError(f'capacity must be a positive number of samples (got {capacity})')
+            return self._forward_capacity(rays_o, rays_d, density_bitfield, grid_size, dt_gamma, perturb, noises, int(capacity))
         if not self.training:
             ws, depth, image = dec.render_rays(rays_o, rays_d, density_bitfield, grid_size, dt_gamma)
             return dict(weights=None, weights_sum=[ws], depth=[depth], image=[image], rays=None, normal=[None], ts=None)
@@ -299,3 +401,23 @@ class VolumeRenderer:
         sigmas, rgbs = dec.point_decode_autograd(xyzs) if differentiable else dec.point_decode(xyzs)
         weights, weights_sum, depth, image = rm.batch_composite_rays_train(sigmas, rgbs, [ts], [rays], [ts.shape[0]])
         return dict(weights=weights, weights_sum=weights_sum, depth=depth, image=image, rays=[rays], normal=None, ts=[ts])
+
+    def _forward_capacity(self, rays_o, rays_d, density_bitfield, grid_size, dt_gamma, perturb, noises, capacity):
+        """the training branch over capacity-sized sample tensors and device counts: the same launches as the exact form plus the clamp"""
+        from . import raymarching as rm
+        dec = self.decoder
+        nears, fars = rm.near_far_from_aabb(rays_o, rays_d, dec.aabb, self.min_near)
+        xyzs, dirs, ts, rays, n_samples, count, overflow = rm.march_rays_train_n(
+            rays_o, rays_d, self.bound, density_bitfield, 1, grid_size, nears, fars, capacity, perturb=perturb, dt_gamma=float(dt_gamma),
+            max_steps=self.max_steps, noises=noises)
+        if self.weight_culling_th > 0:
+            with torch.no_grad():
+                sigmas, _ = dec.point_decode_n(xyzs, count, density_only=True)
+                weights, _, _, _ = rm.batch_composite_rays_train(sigmas, sigmas.new_zeros(capacity, 3), [ts], [rays], [capacity])
+                xyzs, dirs, ts, rays, count = rm.cull_samples_n(weights, self.weight_culling_th, xyzs, dirs, ts, rays, count, n_samples[1:2])
+        differentiable = torch.is_grad_enabled() and any(t.requires_grad for t in dec.parameters().values())
+        sigmas, rgbs = dec.point_decode_autograd_n(xyzs, count) if differentiable else dec.point_decode_n(xyzs, count)
+        weights, weights_sum, depth, image = rm.batch_composite_rays_train(sigmas, rgbs, [ts], [rays], [capacity])
+        return dict(weights=weights, weights_sum=weights_sum, depth=depth, image=image, rays=[rays], normal=None, ts=[ts],
+                    n_samples=n_samples, overflow=overflow)
+

@@ -22,7 +22,8 @@ from . import _lib
 
 __all__ = ['near_far_from_aabb', 'sph_from_ray', 'morton3D', 'morton3D_invert', 'packbits', 'flatten_rays',
            'march_rays_train', 'composite_rays_train', 'march_rays', 'composite_rays',
-           'batch_near_far_from_aabb', 'batch_composite_rays_train', 'compact_alive']
+           'batch_near_far_from_aabb', 'batch_composite_rays_train', 'compact_alive',
+           'march_rays_train_n', 'cull_samples_n']
 
 
 def _gpu_f32(x):
@@ -171,6 +172,48 @@ def march_rays_train(rays_o, rays_d, bound, density_bitfield, C, H, nears, fars,
     return xyzs, dirs, ts, rays
 
 
+def march_rays_train_n(rays_o, rays_d, bound, density_bitfield, C, H, nears, fars, capacity,
+                       perturb=False, dt_gamma=0, max_steps=1024, contract=False, noises=None):
+    """Capacity form of `march_rays_train`: no host read.  -> xyzs [capacity,3], dirs [capacity,3], ts [capacity,2], rays [N,2] int32,
+    n_samples int32 [2], count int32 [1], overflow int32 [1] (the last three on the device).
+
+    n_samples[0] is the marched total (also when it exceeds the capacity); count = n_samples[1] is the number of live rows: the samples
+    of the whole rays that fit, rows at and beyond it are zeros; overflow is 1 when the total exceeds the capacity (the rays that do not
+    fit then composite to zero).  `composite_rays_train` runs on these tensors as it is."""
+    capacity = int(capacity)
+    if capacity <= 0:
+        raise ValueError(f'capacity must be a positive number of samples (got {capacity})')
+    rays_o = _gpu_f32(rays_o).view(-1, 3)
+    rays_d = _gpu_f32(rays_d).view(-1, 3)
+    dev = rays_o.device
+    density_bitfield = _gpu(density_bitfield).contiguous()
+    nears = _gpu_f32(nears)
+    fars = _gpu_f32(fars)
+    N = rays_o.shape[0]
+    if noises is not None:
+        noises = _gpu_f32(noises)
+    elif perturb:
+        noises = torch.rand(N, dtype=torch.float32, device=dev)
+    else:
+        noises = torch.zeros(N, dtype=torch.float32, device=dev)
+    rays = torch.empty(N, 2, dtype=torch.int32, device=dev)
+    st = torch.zeros(4, dtype=torch.int32, device=dev)      # marched total, kept after culling, live count after the march, overflow
+    n_samples, count, overflow = st[0:2], st[2:3], st[3:4]
+    scratch = torch.empty(_lib.raw('mve_march_scratch_bytes')(N), dtype=torch.uint8, device=dev)
+    xyzs = torch.zeros(capacity, 3, dtype=torch.float32, device=dev)
+    dirs = torch.zeros(capacity, 3, dtype=torch.float32, device=dev)
+    ts = torch.zeros(capacity, 2, dtype=torch.float32, device=dev)
+    common = (_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(density_bitfield), float(bound), int(bool(contract)),
+              float(dt_gamma), int(max_steps), N, int(C), int(H), _lib.ptr(nears), _lib.ptr(fars), _lib.ptr(noises))
+    with torch.cuda.device(dev):
+        _lib.call('mve_march_rays_train_count', *common, _lib.ptr(rays), _lib.ptr(n_samples), _lib.ptr(scratch), _s(rays_o))
+        _lib.call('mve_march_rays_train_clamp', _lib.ptr(rays), N, _lib.ptr(n_samples), capacity, _lib.ptr(n_samples), _lib.ptr(count),
+                  _lib.ptr(overflow), _s(rays_o))
+        _lib.call('mve_march_rays_train_write', *common, _lib.ptr(rays), capacity, _lib.ptr(xyzs), _lib.ptr(dirs),
+                  _lib.ptr(ts), _s(rays_o))
+    return xyzs, dirs, ts, rays, n_samples, count, overflow
+
+
 class _composite_rays_train(Function):
     """raymarching.py:314-372 (autograd Function with the analytic backward)."""
 
@@ -317,3 +360,26 @@ def cull_samples(weights, threshold, xyzs, dirs, ts, rays):
                   _lib.ptr(scratch), _s(weights))
     k = int(total.item())      # the reference's boolean-mask indexing synchronises here as well
     return o_xyzs[:k], o_dirs[:k], o_ts[:k], o_rays
+
+
+def cull_samples_n(weights, threshold, xyzs, dirs, ts, rays, count, n_out=None):
+    """Capacity form of `cull_samples`: `count` (device int32 [1]) live rows go in, the kept count comes out in `n_out` (device int32
+    [1], a new tensor unless given; not `count` itself), nothing is read on the host.  -> xyzs', dirs', ts' (capacity-sized, zero beyond
+    the kept count), rays', n_out."""
+    weights = _gpu_f32(weights)
+    dev = weights.device
+    M, N = weights.shape[0], rays.shape[0]
+    assert xyzs.shape[0] == M and dirs.shape[0] == M and ts.shape[0] == M
+    assert count.is_cuda and count.dtype == torch.int32 and count.numel() == 1
+    o_xyzs, o_dirs, o_ts = torch.empty_like(xyzs), torch.empty_like(dirs), torch.empty_like(ts)
+    o_rays = torch.empty_like(rays)
+    pref = torch.empty(M + 1, dtype=torch.int32, device=dev)
+    if n_out is None:
+        n_out = torch.zeros(1, dtype=torch.int32, device=dev)
+    assert n_out.is_cuda and n_out.dtype == torch.int32 and n_out.numel() == 1
+    scratch = torch.empty(_lib.raw('mve_cull_scratch_bytes')(M), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.call('mve_cull_samples_n', _lib.ptr(weights), M, _lib.ptr(count), float(threshold), _lib.ptr(rays), N, _lib.ptr(xyzs),
+                  _lib.ptr(dirs), _lib.ptr(ts), _lib.ptr(o_xyzs), _lib.ptr(o_dirs), _lib.ptr(o_ts), _lib.ptr(o_rays), _lib.ptr(pref),
+                  _lib.ptr(n_out), _lib.ptr(scratch), _s(weights))
+    return o_xyzs, o_dirs, o_ts, o_rays, n_out

@@ -34,7 +34,7 @@ def _f32(t, device):
 
 class _ReconLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, image, weights_sum, depth, weights, consts, hyper):
+    def forward(ctx, image, weights_sum, depth, weights, consts, hyper, count=None):
         dev = image.device
         assert image.is_cuda, 'native path: CUDA tensors only'
         P, ps = consts['target_rgbs'].shape[:2]
@@ -60,8 +60,13 @@ class _ReconLossFn(torch.autograd.Function):
         out_rgbs = torch.empty(P, ps, ps, 3, dtype=torch.float32, device=dev)
         out_normals = torch.empty(P, ps, ps, 3, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _lib.call('mve_recon_loss_forward', ctypes.byref(d), _lib.ptr(ws), ws.numel(), _lib.ptr(losses), _lib.ptr(out_rgbs), _lib.ptr(out_normals),
-                      _lib.stream_ptr(dev))
+            if count is None:
+                _lib.call('mve_recon_loss_forward', ctypes.byref(d), _lib.ptr(ws), ws.numel(), _lib.ptr(losses), _lib.ptr(out_rgbs),
+                          _lib.ptr(out_normals), _lib.stream_ptr(dev))
+            else:                                                                      # M is the capacity, the live samples a device count
+                _lib.call('mve_recon_loss_forward_n', ctypes.byref(d), _lib.ptr(count), _lib.ptr(ws), ws.numel(), _lib.ptr(losses),
+                          _lib.ptr(out_rgbs), _lib.ptr(out_normals), _lib.stream_ptr(dev))
+        ctx.count = count
         # the descriptor holds raw device pointers into `keep` and `ws`: saved (alive + version-checked: an in-place change before backward
         # raises instead of silently giving wrong gradients) and re-read in backward before the pointers are used
         ctx.save_for_backward(ws, *[t for t in keep.values() if t is not None])
@@ -83,27 +88,40 @@ class _ReconLossFn(torch.autograd.Function):
         g_depth = torch.empty(N, dtype=torch.float32, device=dev)
         g_weights = torch.empty(M, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _lib.call('mve_recon_loss_backward', ctypes.byref(ctx.desc), _lib.ptr(ws), ws.numel(), _lib.ptr(g_rgbs), _lib.ptr(g_normals), _lib.ptr(gl),
-                      _lib.ptr(g_image), _lib.ptr(g_ws), _lib.ptr(g_depth), _lib.ptr(g_weights), _lib.stream_ptr(dev))
+            if ctx.count is None:
+                _lib.call('mve_recon_loss_backward', ctypes.byref(ctx.desc), _lib.ptr(ws), ws.numel(), _lib.ptr(g_rgbs), _lib.ptr(g_normals),
+                          _lib.ptr(gl), _lib.ptr(g_image), _lib.ptr(g_ws), _lib.ptr(g_depth), _lib.ptr(g_weights), _lib.stream_ptr(dev))
+            else:
+                _lib.call('mve_recon_loss_backward_n', ctypes.byref(ctx.desc), _lib.ptr(ctx.count), _lib.ptr(ws), ws.numel(), _lib.ptr(g_rgbs),
+                          _lib.ptr(g_normals), _lib.ptr(gl), _lib.ptr(g_image), _lib.ptr(g_ws), _lib.ptr(g_depth), _lib.ptr(g_weights),
+                          _lib.stream_ptr(dev))
         outs = [g.reshape(s).to(t) for g, s, t in zip((g_image, g_ws, g_depth, g_weights), ctx.in_shapes, ctx.in_dtypes)]
-        return (*outs, None, None)
+        return (*outs, None, None, None)
 
 
 def nerf_optim_loss(image, weights_sum, depth, weights, ts, target_rgbs, target_m_blur, target_dir, patch_w, patch_lights, *, target_n=None,
                     target_depth=None, tonemapping=None, shaded=True, is_init=False, ambient_light=0.2, bg_color=1.0, normal_bg=(0.5, 0.5, 1.0),
-                    pixel_loss_weight=1.2, normal_reg_weight=0.0, depth_weight=0.0, entropy_weight=0.0, bg_width=0.015):
+                    pixel_loss_weight=1.2, normal_reg_weight=0.0, depth_weight=0.0, entropy_weight=0.0, bg_width=0.015, n_samples=None):
     """image [N, 3] / weights_sum [N] / depth [N] / weights [M]: `outputs` of the decoder for N = P * ps * ps rays (patch-major), ts [M, 2];
     target_rgbs [P, ps, ps, 3], target_m_blur [P, ps, ps, 1], target_dir [P, ps, ps, 3], optional target_n [P, ps, ps, 3] and
     target_depth [P, ps, ps, 1]; patch_w [P], patch_lights [P, 3]; tonemapping: `mvedit_amd.tonemapping.Tonemapping` or None.
     -> dict(loss, pixel_rgb_loss, alphas_loss, normal_reg_loss, depth_loss, entropy_loss (the parts detached), out_rgbs [P, ps, ps, 3],
-    out_normals [P, ps, ps, 3]); `loss`, `out_rgbs` and `out_normals` are differentiable w.r.t. image, weights_sum, depth, weights."""
+    out_normals [P, ps, ps, 3]); `loss`, `out_rgbs` and `out_normals` are differentiable w.r.t. image, weights_sum, depth, weights.
+
+    n_samples (capacity mode, `VolumeRenderer.forward(..., capacity=C)`): the device count of live samples -- the forward's `n_samples`
+    (int32 [2], its last entry counts) or one int32.  weights / ts then have capacity rows; rows at and beyond the count add nothing to
+    the entropy term and get a zero gradient.  The count is never read on the host."""
+    count = None
+    if n_samples is not None:
+        assert n_samples.is_cuda and n_samples.dtype == torch.int32 and n_samples.numel() >= 1, 'n_samples: int32 on the device'
+        count = n_samples.reshape(-1)[-1:]
     consts = dict(ts=ts, target_rgbs=target_rgbs, target_m=target_m_blur, target_dir=target_dir, target_n=target_n, target_depth=target_depth,
                   patch_w=patch_w, patch_lights=patch_lights, lut_x=None if tonemapping is None else tonemapping.lut_x,
                   lut_y=None if tonemapping is None else tonemapping.lut_y)
     hyper = dict(shaded=bool(shaded), is_init=bool(is_init), ambient_light=float(ambient_light), bg_color=float(bg_color),
                  normal_bg=tuple(float(v) for v in normal_bg), pixel_loss_weight=float(pixel_loss_weight), normal_reg_weight=float(normal_reg_weight),
                  depth_weight=float(depth_weight), entropy_weight=float(entropy_weight), bg_width=float(bg_width))
-    loss, out_rgbs, out_normals, parts = _ReconLossFn.apply(image, weights_sum, depth, weights, consts, hyper)
+    loss, out_rgbs, out_normals, parts = _ReconLossFn.apply(image, weights_sum, depth, weights, consts, hyper, count)
     res = dict(zip(PARTS, parts.unbind(0)))
     res.update(loss=loss, out_rgbs=out_rgbs, out_normals=out_normals)
     return res
