@@ -465,7 +465,28 @@ MVE_API int mve_clip_patchify(int dtype, const void* d_pixels, int B, int H, int
  * d_patch [B*G2][C], d_cls [C], d_pos [G2+1][C], d_out [B][G2+1][C]; C % 8 == 0. */
 MVE_API int mve_clip_vision_embed(int dtype, const void* d_patch, const void* d_cls, const void* d_pos, void* d_out, int B, int G2, int C, void* stream);
 
-/* GroupNorm over NHWC input (optionally the channel-concat of two tensors) with optional fused SiLU:
+/* ---- 2e. DPT-hybrid primitives (csrc/dpt.hip): the row kernels of the Omnidata normal predictor, the reference's
+ * `DPTDepthModel(backbone='vitb_rn50_384', num_channels=3)` (omnidata_modules/midas/dpt_depth.py:87-107, loaded at lib/apis/adapter3d.py:338-352,
+ * called through `enable_normals`, lib/pipelines/mvedit_3d_pipeline.py:262-273), that the GEMM / conv / norm / attention primitives do not give.
+ * Activations NHWC, `dtype` f16 or bf16, C % 8 == 0, pointers 16-byte aligned; every argument error returns MVE_ERR_ARG before the device is
+ * touched. */
+
+/* The operand rows of the ResNetV2 stem: Conv2d(3, C, 7, stride 2) with TF "same" padding of an even image (2 before, 3 after) as a GEMM.
+ * Row (b*Ho + oy)*Ho + ox (Ho = S / 2) of d_rows [B*Ho*Ho][ld] holds pixels[b][c][2 oy - 2 + ky][2 ox - 2 + kx] in (c, ky, kx) order -- the order
+ * of weight.reshape(C, 147) -- zero outside the image; columns 147 .. ld - 1 are zero.  ld must be 152.  d_pixels [B,3,S,S] NCHW.  No arithmetic. */
+MVE_API int mve_dpt_stem_rows(int dtype, const void* d_pixels, int B, int S, void* d_rows, int ld, void* stream);
+/* Max-pool 3 x 3 / 2 with "same" padding of an even map (0 before, 1 after; taps outside the map are left out): x [B,H,W,C] -> y [B,H/2,W/2,C].
+ * transformers pads with 0, timm with -inf; behind a ReLU (x >= 0) they agree, and this kernel agrees with both.  Exact. */
+MVE_API int mve_dpt_maxpool(int dtype, const void* d_x, int B, int H, int W, int C, void* d_y, void* stream);
+/* y[b, oy, ox, :] = x[b, 2 oy, 2 ox, :]: the operand rows of a stride-2 1 x 1 convolution (the downsample shortcut).  H, W even.  Exact. */
+MVE_API int mve_dpt_gather_s2(int dtype, const void* d_x, int B, int H, int W, int C, void* d_y, void* stream);
+/* F.interpolate(x, scale_factor=2, mode='bilinear', align_corners=True): x [B,H,W,C] -> y [B,2H,2W,C], torch's fp32 arithmetic (source coordinate
+ * dst * (H-1)/(2H-1)), one rounding to `dtype`. */
+MVE_API int mve_dpt_upsample2x(int dtype, const void* d_x, int B, int H, int W, int C, void* d_y, void* stream);
+/* y = max(a + b, 0) elementwise, the sum in fp32, one rounding; d_b NULL: y = max(a, 0).  In place allowed (d_y == d_a).  n % 8 == 0. */
+MVE_API int mve_dpt_add_relu(int dtype, const void* d_a, const void* d_b, void* d_y, size_t n, void* stream);
+
+/* GroupNorm over NHWC input (optionally the channel-concat of two tensors) with optional fused SiLU (`silu` = 1) or ReLU (`silu` = 2):
  *   out[B*HW][C1+C2] = act( (x - mean_g) * rstd_g * gamma + beta ), torch.nn.GroupNorm semantics.
  * gamma/beta: [C1+C2] f32.  d_workspace: >= mve_groupnorm_workspace_bytes(B,HW,C,G) bytes.
  * (ResnetBlock2D.norm1/norm2 + nonlinearity, Transformer2DModel.norm, conv_norm_out of diffusers 0.27.2,
@@ -799,6 +820,29 @@ MVE_API int mve_ip_resampler_create(void** handle, int dtype, int dim, int depth
 MVE_API int mve_ip_resampler_plan(void* handle, int B, int n1, size_t* workspace_bytes, int* n_ops, double* flops);
 MVE_API int mve_ip_resampler_forward(void* handle, const void* d_x, int B, int n1, void* d_out, void* d_workspace, size_t workspace_bytes,
                                      float* op_ms, void* stream);
+/* DPT-hybrid dense predictor (the reference's `normal_model`: DPTDepthModel over timm's vit_base_resnet50_384; the same architecture as transformers'
+ * DPTForDepthEstimation with is_hybrid=True over a BitBackbone).  An executor handle; parameters through mve_unet_load_param under the ENGINE's slot
+ * names, each a tensor of exactly the slot's size (mvedit_amd/normal_model.py maps checkpoint keys onto them and standardises the ResNetV2 weights
+ * once, in float64, before the single rounding): `stem.w` [Cs][152]; `stem.{g,b}`; per bottleneck `sS.bM.{c1.w [mid][cin], c2.w (mve_conv3x3 K order),
+ * c3.w [cout][mid], n1,n2,n3.{g,b}}` and for M = 0 `ds.w [cout][cin]`, `dn.{g,b}`; `proj.{w,b}`, `cls`, `pos`; per ViT block `lK.{n1,n2}.{g,b}`,
+ * `lK.{qkv,o,fc1,fc2}.{w,b}`; `r3 / r4 .{wt,wc} [C][C]` (token / class halves of the readout Linear), `.b`, `.p.{w,b}`, `r4.z.{w,b}`; `rn1..4.w`;
+ * `fK.{u1,u2}.{c1,c2}.{w,b}`, `fK.out.{w,b}` (no `f4.u1`); `h0.{w,b}`, `h2.{w,b}`, `h4.{w [8][32], b [8]}` (rows >= num_channels zero).
+ * mve_unet_missing_params / mve_unet_op_info / mve_unet_destroy apply.
+ * Plan (csrc/builder_dpt.h): mve_dpt_stem_rows + GEMM, GroupNorm + ReLU, mve_dpt_maxpool; bottlenecks (1 x 1 GEMM, GN + ReLU, 3 x 3 conv with the
+ * stride and MVE_CONV_PAD_BR, GN + ReLU, 1 x 1 GEMM, GN; shortcut mve_dpt_gather_s2 + GEMM + GN; mve_dpt_add_relu); 1 x 1 projection,
+ * mve_clip_vision_embed, pre-norm ViT blocks on mve_layernorm / GEMMs / mve_attention (head_dim 64) / mve_act(GELU) up to the second tapped block;
+ * the "project" readout as one GEMM over the patch tokens with the class half as the epilogue's per-image row vector; the four `layerN_rn` convs;
+ * four fusion blocks (ReLU, conv, ReLU, conv + residual; add; again; mve_dpt_upsample2x; 1 x 1 GEMM); the head; NHWC -> NCHW.
+ * Refused at create: image_size not a multiple of 32, head_dim != 64, hidden > 2048, widths that are not multiples of 8 / of the group count,
+ * num_channels > 8.  d_pixels [B,3,S,S] NCHW with S = image_size, d_out [B,num_channels,S,S] NCHW, both in the handle's dtype, 16-byte aligned.
+ * d_taps: NULL, or 10 pointers (each may be NULL) that receive, in the handle's dtype: the stem output and the three stage outputs (NHWC), the
+ * two tapped token tensors [B,T,C], the four fusion outputs in execution order refinenet4 .. refinenet1 (NHWC). */
+MVE_API int mve_dpt_create(void** handle, int dtype, int image_size, int stem_width, const int* stage_widths, const int* stage_depths, int num_groups,
+                           int hidden_size, int num_layers, int num_heads, int intermediate_size, const int* tap_layers, const int* neck_channels,
+                           int features, int num_channels, float layer_norm_eps);
+MVE_API int mve_dpt_plan(void* handle, int B, size_t* workspace_bytes, int* n_ops, double* flops);
+MVE_API int mve_dpt_forward(void* handle, const void* d_pixels, int B, void* d_out, void* const* d_taps, void* d_workspace, size_t workspace_bytes,
+                            float* op_ms, void* stream);
 /* LPIPS(net='vgg') perceptual loss, forward and backward w.r.t. the prediction: the `patch_loss` of the reference's reconstruct step
  * (lib/models/losses/lpips_loss.py:8-42 -> lpips==0.1.4 `LPIPS.forward`; lib/models/autoencoders/base_nerf.py:337-344, 8 patches of
  * 128 x 128 per optimisation iteration).  An executor handle: parameters through mve_unet_load_param under lpips' own state-dict

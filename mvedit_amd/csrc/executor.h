@@ -60,6 +60,11 @@ int mve_act(int, int, const void*, void*, size_t, void*);
 int mve_clip_pool(int, const void*, const int32_t*, void*, int, int, int, int, void*);
 int mve_clip_patchify(int, const void*, int, int, int, int, void*, int, void*);
 int mve_clip_vision_embed(int, const void*, const void*, const void*, void*, int, int, int, void*);
+int mve_dpt_stem_rows(int, const void*, int, int, void*, int, void*);
+int mve_dpt_maxpool(int, const void*, int, int, int, int, void*, void*);
+int mve_dpt_gather_s2(int, const void*, int, int, int, int, void*, void*);
+int mve_dpt_upsample2x(int, const void*, int, int, int, int, void*, void*);
+int mve_dpt_add_relu(int, const void*, const void*, void*, size_t, void*);
 }
 
 namespace {
@@ -139,6 +144,11 @@ struct Config {
     // IP-Adapter Resampler (lib/models/architecture/ip_adapter/resampler.py): ch[0] = dim, heads[0] = heads (dim_head 64), layers_per_block = depth,
     // rs_queries = num_queries, rs_embed = embedding_dim, rs_out = output_dim, rs_inner = int(dim * ff_mult)
     int resampler = 0, rs_queries = 0, rs_embed = 0, rs_out = 0, rs_inner = 0;
+    // DPT-hybrid (omnidata_modules/midas/dpt_depth.py DPTDepthModel over vit_base_resnet50_384; builder_dpt.h): ch[0] = ViT width, heads[0],
+    // layers_per_block = ViT depth, eps = LayerNorm eps, groups = GroupNorm groups of the ResNetV2, out_ch = num_channels; dp_image = image size,
+    // dp_stem = stem width, dp_stage / dp_depth = the three stages' widths / depths, dp_tap = the two tapped ViT blocks (hooks[2], hooks[3]),
+    // dp_inter = MLP width, dp_neck = channels of act_postprocess3 / 4, dp_features = decoder width
+    int dpt = 0, dp_image = 0, dp_stem = 0, dp_stage[3] = {0, 0, 0}, dp_depth[3] = {0, 0, 0}, dp_tap[2] = {0, 0}, dp_inter = 0, dp_neck[2] = {0, 0}, dp_features = 0;
     int dtype, in_ch, out_ch, n_levels, layers_per_block, ctx_dim, groups, linear_proj;
     // UNet2DConditionModel / ControlNetModel addition_embed_type (mve_unet_set_addition_embed): 0 none, 1 'text_time' (SDXL);
     // add_time_dim = addition_time_embed_dim, add_P = projection_class_embeddings_input_dim (in_features of add_embedding.linear_1)
@@ -342,7 +352,7 @@ struct XfDesc { std::string name; int c, heads, layers; };
 
 void enumerate(const Config& c, std::vector<ResnetDesc>& rs, std::vector<XfDesc>& xs) {
     const int n = c.n_levels, L = c.layers_per_block;
-    if (c.sr || c.lpips || c.clip || c.clipv || c.resampler) return;     // plain conv stacks / the CLIP towers and the Resampler (builder_clip*.h)
+    if (c.sr || c.lpips || c.clip || c.clipv || c.resampler || c.dpt) return;     // plain conv stacks / the CLIP towers, the Resampler (builder_clip*.h), DPT (builder_dpt.h)
     if (c.vae) {      // diffusers Encoder / Decoder (autoencoders/vae.py): resnets only, one attention in the mid block
         const int Cm = c.ch[n - 1];
         if (c.vae == 2) {

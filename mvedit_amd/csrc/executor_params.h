@@ -109,6 +109,61 @@ void layout_params(Unet& u) {
         u.slab_bytes = sb.top;
         return;
     }
+    if (c.dpt) {
+        // Engine-side slot names: the Python side (mvedit_amd/normal_model.py) maps the checkpoint's keys onto them and does every transformation
+        // that is more than a copy -- weight standardisation, q|k|v concatenation, the readout's token / class halves, the conv K order, padding --
+        // so the loader below only converts a tensor of the slot's size (16-bit slots in the engine dtype, fp32 slots as they are).
+        auto w16 = [&](const std::string& n, size_t elems) { sb.add(n, elems, false); need(n); };
+        auto f32 = [&](const std::string& n, size_t elems) { sb.add(n, elems, true); need(n); };
+        auto gnorm = [&](const std::string& n, size_t C) { f32(n + ".g", C); f32(n + ".b", C); };
+        const size_t C = c.ch[0], I = c.dp_inter, F = c.dp_features, Gd = c.dp_image / 16, Cs = c.dp_stem;
+        w16("stem.w", Cs * 152); gnorm("stem", Cs);
+        size_t cin = Cs;
+        for (int s = 0; s < 3; ++s) {
+            const size_t cout = c.dp_stage[s], mid = cout / 4;
+            for (int m = 0; m < c.dp_depth[s]; ++m) {
+                const std::string b = "s" + std::to_string(s) + ".b" + std::to_string(m);
+                w16(b + ".c1.w", mid * cin); gnorm(b + ".n1", mid);
+                w16(b + ".c2.w", mid * 9 * mid); gnorm(b + ".n2", mid);
+                w16(b + ".c3.w", cout * mid); gnorm(b + ".n3", cout);
+                if (m == 0) { w16(b + ".ds.w", cout * cin); gnorm(b + ".dn", cout); }
+                cin = cout;
+            }
+        }
+        w16("proj.w", C * cin); f32("proj.b", C);
+        w16("cls", C); w16("pos", (Gd * Gd + 1) * C);
+        for (int k = 0; k <= c.dp_tap[1]; ++k) {
+            const std::string b = "l" + std::to_string(k);
+            gnorm(b + ".n1", C);
+            w16(b + ".qkv.w", 3 * C * C); f32(b + ".qkv.b", 3 * C);
+            w16(b + ".o.w", C * C); f32(b + ".o.b", C);
+            gnorm(b + ".n2", C);
+            w16(b + ".fc1.w", I * C); f32(b + ".fc1.b", I);
+            w16(b + ".fc2.w", C * I); f32(b + ".fc2.b", C);
+        }
+        for (int k = 0; k < 2; ++k) {
+            const std::string r = k == 0 ? "r3" : "r4";
+            const size_t N = c.dp_neck[k];
+            w16(r + ".wt", C * C); w16(r + ".wc", C * C); f32(r + ".b", C);
+            w16(r + ".p.w", N * C); f32(r + ".p.b", N);
+            if (k == 1) { w16("r4.z.w", N * 9 * N); f32("r4.z.b", N); }
+        }
+        w16("rn1.w", F * 9 * c.dp_stage[0]); w16("rn2.w", F * 9 * c.dp_stage[1]); w16("rn3.w", F * 9 * c.dp_neck[0]); w16("rn4.w", F * 9 * c.dp_neck[1]);
+        for (int k = 1; k <= 4; ++k) {
+            const std::string f = "f" + std::to_string(k);
+            for (const char* un : {".u1", ".u2"}) {
+                if (k == 4 && std::string(un) == ".u1") continue;       // refinenet4 has one input: its resConfUnit1 never runs
+                w16(f + un + ".c1.w", F * 9 * F); f32(f + un + ".c1.b", F);
+                w16(f + un + ".c2.w", F * 9 * F); f32(f + un + ".c2.b", F);
+            }
+            w16(f + ".out.w", F * F); f32(f + ".out.b", F);
+        }
+        w16("h0.w", (F / 2) * 9 * F); f32("h0.b", F / 2);
+        w16("h2.w", 32 * 9 * (F / 2)); f32("h2.b", 32);
+        w16("h4.w", 8 * 32); f32("h4.b", 8);          // num_channels rows, zero-padded to the GEMM's 8
+        u.slab_bytes = sb.top;
+        return;
+    }
     if (c.resampler) {
         // the reference's state_dict() names; Linear weights as they come ([out][in]), LayerNorm affine parameters and biases in fp32
         const size_t D = c.ch[0], inner = (size_t)c.heads[0] * 64, F = c.rs_inner, E = c.rs_embed, O = c.rs_out, Q = c.rs_queries;
@@ -383,7 +438,11 @@ int load_param(Unet& u, const std::string& name, const void* src, int src_dtype,
     const int Cm_ = c.ch[c.n_levels - 1];
     const int vin = c.vae == 1 ? Cm_ : c.ch[0], vout = c.vae == 1 ? c.ch[0] : Cm_;     // widths after conv_in / before conv_out
     const std::string va = "mid_block.attentions.0";
-    if (c.clipv) {
+    if (c.dpt) {
+        Param* p = P(name);
+        MVE_CHECK(p, MVE_ERR_ARG, "load_param: %s is not a slot of this DPT model", name.c_str());
+        rc = vec(p, 0, (long long)(p->bytes / (p->f32 ? 4 : 2)), 1);
+    } else if (c.clipv) {
         const long long C = c.ch[0], I = c.clip_inter, PP3 = 3ll * c.cv_patch * c.cv_patch, Kp = (PP3 + 7) / 8 * 8, G = c.cv_image / c.cv_patch;
         const std::string em = "vision_model.embeddings.";
         int which = -1;

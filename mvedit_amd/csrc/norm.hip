@@ -175,7 +175,8 @@ __global__ __launch_bounds__(GN_THREADS) void k_gn_apply(GNSrc s, int nsplit, in
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             float y = v[e] * sc[e] + sh[e];
-            if (silu) y = y / (1.0f + __expf(-y));
+            if (silu == 2) y = fmaxf(y, 0.f);      // selector 2: ReLU (the DPT-hybrid ResNetV2 norms, csrc/builder_dpt.h)
+            else if (silu) y = y / (1.0f + __expf(-y));
             pk[e] = Tag::from_f32(y);
         }
         *reinterpret_cast<V8*>(o + ((size_t)b * s.HW + r) * C + chunk * 8) = pk;
@@ -335,7 +336,8 @@ __global__ __launch_bounds__(NT) void k_gn_fused(GNSrc s, int G, int W8, int nch
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 float y = __builtin_fmaf(x8[e], tab[0][c8 * 8 + e], tab[1][c8 * 8 + e]);
-                if (silu) y = y / (1.0f + __expf(-y));
+                if (silu == 2) y = fmaxf(y, 0.f);      // selector 2: ReLU
+                else if (silu) y = y / (1.0f + __expf(-y));
                 pk[e] = Tag::from_f32(y);
             }
             *reinterpret_cast<V8*>(o + ((size_t)b * s.HW + row) * C + (size_t)(chunk * W8 + c8) * 8) = pk;

@@ -17,7 +17,7 @@
 //   * per-op HIP-event profiling and analytic FLOP accounting are built in (bench.py's roofline).
 //
 // Source layout (one translation unit): executor.h (types) -> executor_params.h (parameter slab + loader) -> executor_builder.h (plan
-// builder, shared blocks) -> builder_{unet,vae,sr,lpips,clip,clip_vision}.h (one plan builder per network) -> this file (plan cache + C ABI).
+// builder, shared blocks) -> builder_{unet,vae,sr,lpips,clip,clip_vision,dpt}.h (one plan builder per network) -> this file (plan cache + C ABI).
 #include "executor_builder.h"
 #include "builder_unet.h"
 #include "builder_vae.h"
@@ -25,6 +25,7 @@
 #include "builder_lpips.h"
 #include "builder_clip.h"
 #include "builder_clip_vision.h"
+#include "builder_dpt.h"
 
 namespace {
 
@@ -44,7 +45,7 @@ int ensure_plan(Unet& u, int B, int H, int W, int n_img, int has_res, int io_dty
     Builder b(u, *np);
     b.ctx_rows_per_img = ctx_len;
     u.cur = nullptr;
-    const int rc = u.cfg.clipv ? b.build_clip_vision(B) : u.cfg.resampler ? b.build_resampler(B, H) : u.cfg.clip ? b.build_clip(B, H) : u.cfg.lpips ? b.build_lpips(B, H, W, io_dtype) : u.cfg.sr ? b.build_sr(B, H, W, io_dtype) : u.cfg.vae ? b.build_vae(B, H, W, io_dtype) : b.build(B, H, W, n_img, has_res, io_dtype, res_nhwc);
+    const int rc = u.cfg.dpt ? b.build_dpt(B) : u.cfg.clipv ? b.build_clip_vision(B) : u.cfg.resampler ? b.build_resampler(B, H) : u.cfg.clip ? b.build_clip(B, H) : u.cfg.lpips ? b.build_lpips(B, H, W, io_dtype) : u.cfg.sr ? b.build_sr(B, H, W, io_dtype) : u.cfg.vae ? b.build_vae(B, H, W, io_dtype) : b.build(B, H, W, n_img, has_res, io_dtype, res_nhwc);
     if (rc != MVE_OK) return rc;
     np->ctx_len = ctx_len;
     np->last_use = u.tick;
@@ -536,6 +537,83 @@ int mve_ip_resampler_forward(void* handle, const void* d_x, int B, int n1, void*
     return run_plan_ops(pl, r, op_ms);
 }
 
+int mve_dpt_create(void** handle, int dtype, int image_size, int stem_width, const int* stage_widths, const int* stage_depths, int num_groups, int hidden_size,
+                   int num_layers, int num_heads, int intermediate_size, const int* tap_layers, const int* neck_channels, int features, int num_channels,
+                   float layer_norm_eps) {
+    MVE_CHECK(handle && stage_widths && stage_depths && tap_layers && neck_channels, MVE_ERR_ARG, "dpt_create: null pointer");
+    MVE_CHECK(dtype == MVE_F16 || dtype == MVE_BF16, MVE_ERR_ARG, "dpt_create: dtype must be f16 or bf16");
+    MVE_CHECK(image_size >= 32 && image_size % 32 == 0 && image_size <= 2048, MVE_ERR_ARG, "dpt_create: image_size %d must be a multiple of 32 in [32, 2048]", image_size);
+    MVE_CHECK(num_groups >= 1 && stem_width >= 8 && stem_width % 8 == 0 && stem_width % num_groups == 0, MVE_ERR_ARG,
+              "dpt_create: stem_width %d must be a multiple of 8 and of num_groups %d", stem_width, num_groups);
+    for (int s = 0; s < 3; ++s) {
+        MVE_CHECK(stage_depths[s] >= 1, MVE_ERR_ARG, "dpt_create: stage_depths[%d] = %d", s, stage_depths[s]);
+        MVE_CHECK(stage_widths[s] >= 32 && stage_widths[s] % 32 == 0 && (stage_widths[s] / 4) % num_groups == 0, MVE_ERR_ARG,
+                  "dpt_create: stage_widths[%d] = %d must be a multiple of 32 whose quarter (the bottleneck width) is divisible by num_groups %d", s, stage_widths[s], num_groups);
+    }
+    MVE_CHECK(num_heads >= 1 && hidden_size == num_heads * 64, MVE_ERR_ARG, "dpt_create: hidden_size %d / num_heads %d: head_dim must be 64", hidden_size, num_heads);
+    MVE_CHECK(hidden_size <= 2048, MVE_ERR_ARG, "dpt_create: hidden_size %d exceeds the 2048 channels of mve_layernorm", hidden_size);
+    MVE_CHECK(intermediate_size >= 8 && intermediate_size % 8 == 0, MVE_ERR_ARG, "dpt_create: intermediate_size %d must be a multiple of 8", intermediate_size);
+    MVE_CHECK(num_layers >= 1 && tap_layers[0] >= 0 && tap_layers[0] < tap_layers[1] && tap_layers[1] < num_layers, MVE_ERR_ARG,
+              "dpt_create: tap_layers {%d, %d} must be increasing block indices below num_layers %d", tap_layers[0], tap_layers[1], num_layers);
+    MVE_CHECK(neck_channels[0] >= 8 && neck_channels[0] % 8 == 0 && neck_channels[1] >= 8 && neck_channels[1] % 8 == 0, MVE_ERR_ARG,
+              "dpt_create: neck_channels {%d, %d} must be multiples of 8", neck_channels[0], neck_channels[1]);
+    MVE_CHECK(features >= 16 && features % 16 == 0, MVE_ERR_ARG, "dpt_create: features %d must be a multiple of 16 (the head halves it)", features);
+    MVE_CHECK(num_channels >= 1 && num_channels <= 8, MVE_ERR_ARG, "dpt_create: num_channels %d must be in [1, 8]", num_channels);
+    MVE_CHECK(layer_norm_eps > 0.f, MVE_ERR_ARG, "dpt_create: layer_norm_eps must be positive");
+    Unet* u = new Unet();
+    Config& c = u->cfg;
+    c.dpt = 1; c.dp_image = image_size; c.dp_stem = stem_width; c.dp_inter = intermediate_size; c.dp_features = features;
+    for (int s = 0; s < 3; ++s) { c.dp_stage[s] = stage_widths[s]; c.dp_depth[s] = stage_depths[s]; }
+    for (int k = 0; k < 2; ++k) { c.dp_tap[k] = tap_layers[k]; c.dp_neck[k] = neck_channels[k]; }
+    c.dtype = dtype; c.in_ch = 3; c.out_ch = num_channels; c.n_levels = 1; c.layers_per_block = num_layers;
+    c.ctx_dim = 8; c.groups = num_groups; c.eps = layer_norm_eps; c.linear_proj = 0;
+    c.ch[0] = hidden_size; c.attn[0] = 0; c.heads[0] = num_heads; c.tlayers[0] = 0;
+    layout_params(*u);
+    *handle = u;
+    return MVE_OK;
+}
+
+int mve_dpt_plan(void* handle, int B, size_t* workspace_bytes, int* n_ops, double* flops) {
+    MVE_CHECK(handle && B > 0, MVE_ERR_ARG, "dpt_plan: bad arguments");
+    Unet* u = (Unet*)handle;
+    MVE_CHECK(u->cfg.dpt, MVE_ERR_ARG, "dpt_plan: handle is not a DPT model");
+    int rc = ensure_plan(*u, B, u->cfg.dp_image, u->cfg.dp_image, 1, 0, u->cfg.dtype, 0, 0);
+    if (rc) return rc;
+    if (workspace_bytes) *workspace_bytes = u->cur->ws_bytes;
+    if (n_ops) *n_ops = (int)u->cur->ops.size();
+    if (flops) for (int i = 0; i < OC_COUNT; ++i) flops[i] = u->cur->flops[i];
+    return MVE_OK;
+}
+
+int mve_dpt_forward(void* handle, const void* d_pixels, int B, void* d_out, void* const* d_taps, void* d_workspace, size_t workspace_bytes, float* op_ms,
+                    void* stream) {
+    MVE_CHECK(handle, MVE_ERR_ARG, "dpt_forward: null handle");
+    Unet* u = (Unet*)handle;
+    MVE_CHECK(u->cfg.dpt, MVE_ERR_ARG, "dpt_forward: handle is not a DPT model");
+    {
+        char first[256];
+        const int miss = mve_unet_missing_params(handle, first, sizeof(first));
+        MVE_CHECK(miss == 0, MVE_ERR_STATE, "dpt_forward: %d parameters not loaded (first: %s)", miss, first);
+    }
+    MVE_CHECK(d_pixels && d_out, MVE_ERR_ARG, "dpt_forward: null pointer (d_pixels / d_out)");
+    MVE_CHECK(B > 0, MVE_ERR_ARG, "dpt_forward: bad B %d", B);
+    MVE_CHECK(((uintptr_t)d_pixels & 15) == 0 && ((uintptr_t)d_out & 15) == 0, MVE_ERR_ARG, "dpt_forward: d_pixels / d_out must be 16-byte aligned");
+    int rc = ensure_plan(*u, B, u->cfg.dp_image, u->cfg.dp_image, 1, 0, u->cfg.dtype, 0, 0);
+    if (rc) return rc;
+    const Plan& pl = *u->cur;
+    MVE_CHECK(d_workspace && workspace_bytes >= pl.ws_bytes, MVE_ERR_NOMEM, "dpt_forward: workspace %zu < required %zu", workspace_bytes, pl.ws_bytes);
+    std::vector<void*> taps(DPT_TAPS, nullptr);
+    if (d_taps)
+        for (int i = 0; i < DPT_TAPS; ++i) taps[i] = d_taps[i];      // a null entry: that tap is not wanted
+    Run r;
+    r.ws = (unsigned char*)d_workspace; r.wt = u->slab;
+    r.sample = d_pixels; r.timesteps = nullptr; r.ctx = nullptr; r.out = d_out;
+    r.down_res = nullptr; r.mid_res = nullptr; r.ref_store = nullptr;
+    r.cn_out = taps.data();
+    r.stream = (hipStream_t)stream;
+    return run_plan_ops(pl, r, op_ms);
+}
+
 int mve_lpips_create(void** handle, int dtype, int normalize_inputs) {
     MVE_CHECK(handle, MVE_ERR_ARG, "lpips_create: null handle");
     MVE_CHECK(dtype == MVE_F16 || dtype == MVE_BF16, MVE_ERR_ARG, "lpips_create: dtype must be f16 or bf16");
@@ -676,8 +754,8 @@ int mve_unet_forward(void* handle, int phase, const void* d_sample, int io_dtype
                      float* op_ms /* optional host array [n_ops]: per-op milliseconds (synchronises) */, void* stream) {
     MVE_CHECK(handle, MVE_ERR_ARG, "unet_forward: null handle");
     Unet* u = (Unet*)handle;
-    MVE_CHECK(!u->cfg.controlnet && !u->cfg.vae && !u->cfg.sr && !u->cfg.lpips && !u->cfg.clip && !u->cfg.clipv && !u->cfg.resampler, MVE_ERR_ARG,
-              "unet_forward: handle is a ControlNet / VAE / SRVGG / CLIP text or vision tower / Resampler (use their own forward calls)");
+    MVE_CHECK(!u->cfg.controlnet && !u->cfg.vae && !u->cfg.sr && !u->cfg.lpips && !u->cfg.clip && !u->cfg.clipv && !u->cfg.resampler && !u->cfg.dpt, MVE_ERR_ARG,
+              "unet_forward: handle is a ControlNet / VAE / SRVGG / CLIP text or vision tower / Resampler / DPT (use their own forward calls)");
     {
         char first[256];
         const int miss = mve_unet_missing_params(handle, first, sizeof(first));
@@ -794,7 +872,7 @@ int mve_unet_set_attention(void* handle, int ip_tokens, float ip_scale, int ref_
 int mve_unet_set_residual_mode(void* handle, int pair) {
     MVE_CHECK(handle, MVE_ERR_ARG, "unet_set_residual_mode: null handle");
     Unet* u = (Unet*)handle;
-    MVE_CHECK(!u->cfg.vae && !u->cfg.sr && !u->cfg.lpips && !u->cfg.clip && !u->cfg.clipv && !u->cfg.resampler, MVE_ERR_ARG, "unet_set_residual_mode: a UNet / ControlNet handle is needed");
+    MVE_CHECK(!u->cfg.vae && !u->cfg.sr && !u->cfg.lpips && !u->cfg.clip && !u->cfg.clipv && !u->cfg.resampler && !u->cfg.dpt, MVE_ERR_ARG, "unet_set_residual_mode: a UNet / ControlNet handle is needed");
     const int old = u->ao.residual_pair;
     if (pair >= 0) u->ao.residual_pair = pair ? 1 : 0;     // part of the plan key: plans of either mode stay cached side by side
     return old;
@@ -823,7 +901,7 @@ int mve_unet_set_addition_embed(void* handle, int addition_type, int addition_ti
     MVE_CHECK(handle, MVE_ERR_ARG, "unet_set_addition_embed: null handle");
     Unet* u = (Unet*)handle;
     Config& c = u->cfg;
-    MVE_CHECK(!c.vae && !c.sr && !c.lpips && !c.clip && !c.clipv && !c.resampler, MVE_ERR_ARG, "unet_set_addition_embed: a UNet / ControlNet handle is needed");
+    MVE_CHECK(!c.vae && !c.sr && !c.lpips && !c.clip && !c.clipv && !c.resampler && !c.dpt, MVE_ERR_ARG, "unet_set_addition_embed: a UNet / ControlNet handle is needed");
     MVE_CHECK(addition_type == 0 || addition_type == 1, MVE_ERR_ARG, "unet_set_addition_embed: addition type %d (0 = none, 1 = text_time)", addition_type);
     MVE_CHECK(!u->slab && u->loaded.empty(), MVE_ERR_STATE, "unet_set_addition_embed: parameters are already loaded; declare the embedding right after create");
     MVE_CHECK(!c.add_type, MVE_ERR_STATE, "unet_set_addition_embed: the handle already has an addition embedding");

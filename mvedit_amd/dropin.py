@@ -36,7 +36,8 @@ What `install()` rebinds -- the operator seams of SURVEY.md section 8(b), nothin
 Not part of `install()`: `swap_text_encoder(pipe)` puts native CLIP text towers (mvedit_amd/text_encoder.py) behind `pipe.text_encoder` /
 `pipe.text_encoder_2` of ONE pipeline object, on request; `swap_image_encoder(obj)` puts the native CLIP vision tower
 (mvedit_amd/vision_encoder.py) behind `image_encoder` / `vision_encoder` and the native image projection (mvedit_amd/ip_adapter.py) behind
-`image_proj_model` of ONE object (an `IPAdapter`, a `Zero123PlusPipeline`, a `Zero123Pipeline`), on request.
+`image_proj_model` of ONE object (an `IPAdapter`, a `Zero123PlusPipeline`, a `Zero123Pipeline`), on request; `swap_normal_model(pipe)` puts the
+native DPT-hybrid normal predictor (mvedit_amd/normal_model.py) behind `pipe.normal_model`, on request.
 
 Nothing here computes: every replacement is one of the engines / mirrors INTEGRATION.md documents seam by seam, and a conversion that fails
 raises -- there is no fallback to the torch module.  `uninstall()` restores everything (tests).
@@ -228,6 +229,32 @@ def swap_image_encoder(obj):
             object.__setattr__(m, '_mve_engine', cached)
         object.__setattr__(obj, name, cached[1])
     return obj
+
+
+def make_normal_model(m):
+    """Omnidata's `DPTDepthModel(backbone='vitb_rn50_384', num_channels=3)` (`MVEdit3DPipeline.normal_model`, lib/apis/adapter3d.py:338-352;
+    called by `enable_normals`, lib/pipelines/mvedit_3d_pipeline.py:262-273), or a transformers `DPTForDepthEstimation` of the same architecture."""
+    from .normal_model import DPTNormalEngine
+    dtype, device = _module_dtype_device(m)
+    return DPTNormalEngine.from_module(m, dtype=dtype, device=device)
+
+
+def swap_normal_model(pipe):
+    """Opt-in (install() / swap_engines leave `normal_model` alone): replaces `pipe.normal_model` by a native engine built from that module.
+    A pipeline without a normal predictor (`normal_model=None`) keeps `None`.  Idempotent; the engine is cached on the source module like the
+    other seams'."""
+    m = getattr(pipe, 'normal_model', None)
+    if m is None or getattr(m, '_mve_is_engine', False) or not hasattr(m, 'state_dict'):
+        return pipe
+    fp = _fingerprint(m)
+    cached = getattr(m, '_mve_engine', None)
+    if cached is None or cached[0] != fp:
+        eng = make_normal_model(m)
+        object.__setattr__(eng, '_mve_is_engine', True)
+        cached = (fp, eng)
+        object.__setattr__(m, '_mve_engine', cached)
+    object.__setattr__(pipe, 'normal_model', cached[1])
+    return pipe
 
 
 MAKERS = dict(unet=make_unet, controlnet=make_controlnet, vae=make_vae, image_enhancer=make_image_enhancer, segmentation=make_segmentation,
