@@ -486,6 +486,69 @@ MVE_API int mve_dpt_upsample2x(int dtype, const void* d_x, int B, int H, int W, 
 /* y = max(a + b, 0) elementwise, the sum in fp32, one rounding; d_b NULL: y = max(a, 0).  In place allowed (d_y == d_a).  n % 8 == 0. */
 MVE_API int mve_dpt_add_relu(int dtype, const void* d_a, const void* d_b, void* d_y, size_t n, void* stream);
 
+/* ---- 2f. LoFTR matcher primitives (csrc/loftr.hip): the kernels of the reference's detector-free feature matcher (loftr/, loaded at
+ * lib/apis/adapter3d.py:411-415, run once per Zero123++ view by lib/core/utils/pose_estimation.py:30-160) that the GEMM / conv / norm primitives do
+ * not give.  16-bit activations are `dtype` f16 or bf16 with C % 8 == 0 and 16-byte aligned pointers; similarity, confidence, statistics, key
+ * points and expectations are fp32; match ids are int64 (what the reference's callers index with).  Every reduction is fp32 in a fixed order (no
+ * float atomics): two runs give identical bits.  Every argument error returns MVE_ERR_ARG before the device is touched. */
+
+/* The operand rows of the stem Conv2d(1, C, 7, stride 2, padding 3) as a GEMM: row (b*Ho + oy)*Wo + ox (Ho = H/2, Wo = W/2) of d_rows [B*Ho*Wo][ld]
+ * holds pixels[b][0][2 oy - 3 + ky][2 ox - 3 + kx] at column ky*7 + kx -- the order of weight.reshape(C, 49) -- zero outside the image; columns
+ * 49 .. 55 are zero.  ld must be 56.  d_pixels [B,1,H,W], H and W even.  No arithmetic. */
+MVE_API int mve_loftr_stem_rows(int dtype, const void* d_pixels, int B, int H, int W, void* d_rows, int ld, void* stream);
+/* y = x (x >= 0), slope * x (x < 0), the product in fp32, one rounding (the FPN heads' LeakyReLU).  In place allowed.  n % 8 == 0. */
+MVE_API int mve_loftr_leaky_relu(int dtype, const void* d_x, void* d_y, size_t n, float slope, void* stream);
+/* y[b, p, :] = round_once(float(x[b, p, :]) + pos[p, :]): d_x, d_y [B][HW][C], d_pos fp32 [HW][C] (the sinusoidal table, built by the caller). */
+MVE_API int mve_loftr_pos_add(int dtype, const void* d_x, const float* d_pos, void* d_y, int B, int HW, int C, void* stream);
+
+/* Linear attention ("Transformers are RNNs") with phi(x) = elu(x) + 1 taken in fp32 from the 16-bit operand, in two steps.
+ *   mve_linattn_kv:    d_kv[(b*H + h)][0 .. D*D)   = KV[d][v] = sum_s phi(K[b,s,h,d]) V[b,s,h,v]   (row-major [D][D])
+ *                      d_kv[(b*H + h)][D*D .. +D)  = Ksum[d]  = sum_s phi(K[b,s,h,d])
+ *   mve_linattn_apply: out[b,l,h,:] = phi(Q[b,l,h,:]) . KV / (phi(Q[b,l,h,:]) . Ksum + eps), rounded once to `dtype`.
+ * K, V [B][S][ld], Q, out [B][L][ld]; head h occupies columns [h*D, (h+1)*D); D is 32 or 16; ld % 8 == 0.  d_kv fp32 [B*H][D*D + D].
+ * fp32 accumulators: S is cut into 128-row chunks, one block each, every thread sums its rows in ascending order and the chunk partials are
+ * added in ascending order (d_workspace >= mve_linattn_workspace_bytes; 0 for S <= 128).  The reference's division of V by S and
+ * multiplication back -- a guard against fp16 overflow, the identity in exact arithmetic -- is left out. */
+MVE_API size_t mve_linattn_workspace_bytes(int B, int S, int H, int D);
+MVE_API int mve_linattn_kv(int dtype, const void* d_k, int ldk, const void* d_v, int ldv, int B, int S, int H, int D, float* d_kv, void* d_workspace,
+                           size_t workspace_bytes, void* stream);
+MVE_API int mve_linattn_apply(int dtype, const void* d_q, int ldq, const float* d_kv, void* d_out, int ldo, int B, int L, int H, int D, float eps,
+                              void* stream);
+
+/* Dual softmax of a similarity d_sim fp32 [N][L][ld]; only columns [0, S) are read (ld > S: the padding of a GEMM's leading dimension).
+ *   mve_dsmax_stats: d_row_stats [N*L][2] = (max_j, sum_j exp(sim - max)), d_col_stats [N*S][2] = (max_i, sum_i exp(sim - max)).
+ *   mve_dsmax_conf:  d_conf fp32 [N][L][S] (compact) = softmax over i  *  softmax over j -- the reference's `conf_matrix`. */
+MVE_API int mve_dsmax_stats(const float* d_sim, int N, int L, int S, int ld, float* d_row_stats, float* d_col_stats, void* stream);
+MVE_API int mve_dsmax_conf(const float* d_sim, int N, int L, int S, int ld, const float* d_row_stats, const float* d_col_stats, float* d_conf, void* stream);
+/* Mutual-nearest selection (get_coarse_match without masks): cell i = y0*W0 + x0 of pair n matches j = y1*W1 + x1 when conf[n][i][j] > thr, every
+ * one of y0, x0, y1, x1 is at least `border` cells from both edges of its grid (border <= 0: no rule), and conf[n][i][j] equals the maximum of its
+ * row and of its column; of several such j (exactly equal floats) the lowest.  Survivors are compacted in ascending (n, i) order: d_b_ids / d_i_ids /
+ * d_j_ids int64 and d_mconf fp32 with room for N * L entries, d_count int32 [1] (device).  d_mkpts0_c / d_mkpts1_c (fp32 [N*L][2], may be NULL)
+ * receive (x, y) * scale.  d_conf [N][H0*W0][H1*W1] compact; d_workspace >= mve_dsmax_select_workspace_bytes(N, L, S). */
+MVE_API size_t mve_dsmax_select_workspace_bytes(int N, int L, int S);
+MVE_API int mve_dsmax_select(const float* d_conf, int N, int H0, int W0, int H1, int W1, float thr, int border, float scale, int64_t* d_b_ids,
+                             int64_t* d_i_ids, int64_t* d_j_ids, float* d_mconf, float* d_mkpts0_c, float* d_mkpts1_c, int* d_count, void* d_workspace,
+                             size_t workspace_bytes, void* stream);
+
+/* F.unfold(feat, 5, stride 4, padding 2) at the matched coarse cells only: d_rows[(m*25 + ky*5 + kx)][:] = feat[b_ids[m]][4 cy - 2 + ky][4 cx - 2 + kx][:],
+ * (cy, cx) = (ids[m] / (Wf/4), ids[m] % (Wf/4)), zero outside the map (and for an id outside its range).  d_feat [N][Hf][Wf][C] NHWC, Hf and Wf
+ * multiples of 4; d_b_ids / d_ids int64 [M] on the device; M >= 1 is a host value.  Exact. */
+MVE_API int mve_loftr_unfold(int dtype, const void* d_feat, int N, int Hf, int Wf, int C, const int64_t* d_b_ids, const int64_t* d_ids, int M, void* d_rows,
+                             void* stream);
+/* y[m, :] = x[m, :] + LayerNorm(o[m, :]) * gamma + beta (LoFTREncoderLayer's `x + norm2(message)`), fp32 throughout, one rounding; y may alias x.
+ * o [M][ldo], x [M][ldx], y [M][ldy]; C a multiple of 64, at most 512; gamma / beta fp32 [C]. */
+MVE_API int mve_loftr_ln_add(int dtype, const void* d_o, int ldo, const void* d_x, int ldx, void* d_y, int ldy, int M, int C, const float* d_gamma,
+                             const float* d_beta, float eps, void* stream);
+/* d_rows[m, :] = feat[b_ids[m]][ids[m]][:] (zero for an id outside its range): the coarse features at the matched cells.  d_feat [N][L][C]. */
+MVE_API int mve_loftr_gather_rows(int dtype, const void* d_feat, int N, int L, int C, const int64_t* d_b_ids, const int64_t* d_ids, int M, void* d_rows,
+                                  void* stream);
+/* FineMatching: for match m the centre row (12) of window 0 against the 25 rows of window 1 (d_feat0 / d_feat1 [M][25][C]), softmax at 1/sqrt(C),
+ * expectation over the normalised 5 x 5 grid in [-1, 1] (x fastest), all in fp32:
+ *   d_expec_f [M][3] = (E[x], E[y], sqrt(max(Var x, 1e-10)) + sqrt(max(Var y, 1e-10))),  d_mkpts1_f [M][2] = d_mkpts1_c[m] + (E[x], E[y]) * radius
+ * (radius = (window / 2) * image size / fine map size, in pixels). */
+MVE_API int mve_loftr_fine_match(int dtype, const void* d_feat0, const void* d_feat1, int M, int C, const float* d_mkpts1_c, float radius, float* d_expec_f,
+                                 float* d_mkpts1_f, void* stream);
+
 /* GroupNorm over NHWC input (optionally the channel-concat of two tensors) with optional fused SiLU (`silu` = 1) or ReLU (`silu` = 2):
  *   out[B*HW][C1+C2] = act( (x - mean_g) * rstd_g * gamma + beta ), torch.nn.GroupNorm semantics.
  * gamma/beta: [C1+C2] f32.  d_workspace: >= mve_groupnorm_workspace_bytes(B,HW,C,G) bytes.
@@ -843,6 +906,33 @@ MVE_API int mve_dpt_create(void** handle, int dtype, int image_size, int stem_wi
 MVE_API int mve_dpt_plan(void* handle, int B, size_t* workspace_bytes, int* n_ops, double* flops);
 MVE_API int mve_dpt_forward(void* handle, const void* d_pixels, int B, void* d_out, void* const* d_taps, void* d_workspace, size_t workspace_bytes,
                             float* op_ms, void* stream);
+/* LoFTR feature matcher (the reference's `matcher`: loftr/loftr.py with `default_cfg` -- ResNetFPN_8_2 1 -> 128 -> [128, 196, 256], a 256-wide
+ * 8-head linear-attention transformer over ['self', 'cross'] x 4, dual-softmax coarse matching, 5 x 5 fine windows with the coarse feature
+ * concatenated, a 128-wide 8-head ['self', 'cross'] fine transformer, FineMatching).  An executor handle; parameters through mve_unet_load_param
+ * under the ENGINE's slot names, each a tensor of exactly the slot's size (mvedit_amd/matcher.py maps the checkpoint's keys onto them, folds every
+ * eval-mode BatchNorm into the convolution in front of it in float64 and pads the 196-wide stage to 200 channels with zeros): `stem.{w [128][56], b}`;
+ * per BasicBlock `lS.bM.{c1,c2}.{w (mve_conv3x3 K order), b}` and for the strided ones `ds.{w [cout][cin], b}`; `l3oc.w`, `l2oc.w`, `l1oc.w` (1 x 1);
+ * `l2oc2.0.{w,b}`, `l2oc2.3.w`, `l1oc2.0.{w,b}`, `l1oc2.3.w`; per encoder layer `cK.` / `fK.` `{q.w [C][C], kv.w [2C][C], merge.w [C][C],
+ * mlp0.w [2C][2C], mlp2.w [C][2C], n1.{g,b}, n2.{g,b}}`; `dp.{w [128][256], b}`, `mf.{w [128][256], b}`.
+ * The forward is two calls with one host read between them (the match count M shapes every fine output):
+ *   mve_loftr_forward_coarse  d_images [2N,1,H,W] (image0 of the N pairs, then image1; the handle's dtype), H and W multiples of 8, at most 2048;
+ *                             d_pos fp32 [H/8 * W/8][256] the position table.  d_io[0] feat_f [2N,H/2,W/2,128] and d_io[1] feat_c [2N,L,256] (handle
+ *                             dtype; kept for the fine call), d_io[2] sim fp32 [N,L,ld] with ld = S rounded up to 8, d_io[3] conf fp32 [N,L,S],
+ *                             d_io[4..6] b_ids / i_ids / j_ids int64 [N*L], d_io[7] mconf fp32 [N*L], d_io[8..9] mkpts0_c / mkpts1_c fp32 [N*L][2],
+ *                             d_io[10] the match count int32 [1].  d_taps: NULL or 14 pointers (each may be NULL): stem, layer1, layer2 (200
+ *                             channels, the last 4 zero), layer3, fpn_c (NHWC, 2N images), the tokens after the position add and after each of
+ *                             the 8 layers ([2N,L,256]: feat0 of the N pairs, then feat1).
+ *   mve_loftr_forward_fine    M >= 1 matches (host value; at most N*min(L,S), the capacity the plan is made for): reads d_io[0], [1], [4..6], [9];
+ *                             writes d_io[11] expec_f fp32 [M][3] and d_io[12] mkpts1_f fp32 [M][2].  d_taps: NULL or 3 pointers: the unfolded
+ *                             windows, the merged windows, the windows after the fine transformer ([2M,25,128]: window 0 of every match, then window 1).
+ * thr / border are mve_dsmax_select's.  The linear attention leaves out the reference's V / S ... * S guard (fp32 accumulators). */
+MVE_API int mve_loftr_create(void** handle, int dtype);
+MVE_API int mve_loftr_plan(void* handle, int phase, int N, int H, int W, size_t* workspace_bytes, int* n_ops, double* flops);
+MVE_API int mve_loftr_forward_coarse(void* handle, const void* d_images, const float* d_pos, int N, int H, int W, float thr, int border, void* const* d_io,
+                                     void* const* d_taps, void* d_workspace, size_t workspace_bytes, float* op_ms, void* stream);
+MVE_API int mve_loftr_forward_fine(void* handle, int N, int H, int W, int M, void* const* d_io, void* const* d_taps, void* d_workspace, size_t workspace_bytes,
+                                   float* op_ms, void* stream);
+MVE_API int mve_loftr_destroy(void* handle);
 /* LPIPS(net='vgg') perceptual loss, forward and backward w.r.t. the prediction: the `patch_loss` of the reference's reconstruct step
  * (lib/models/losses/lpips_loss.py:8-42 -> lpips==0.1.4 `LPIPS.forward`; lib/models/autoencoders/base_nerf.py:337-344, 8 patches of
  * 128 x 128 per optimisation iteration).  An executor handle: parameters through mve_unet_load_param under lpips' own state-dict

@@ -65,6 +65,20 @@ int mve_dpt_maxpool(int, const void*, int, int, int, int, void*, void*);
 int mve_dpt_gather_s2(int, const void*, int, int, int, int, void*, void*);
 int mve_dpt_upsample2x(int, const void*, int, int, int, int, void*, void*);
 int mve_dpt_add_relu(int, const void*, const void*, void*, size_t, void*);
+int mve_loftr_stem_rows(int, const void*, int, int, int, void*, int, void*);
+int mve_loftr_leaky_relu(int, const void*, void*, size_t, float, void*);
+int mve_loftr_pos_add(int, const void*, const float*, void*, int, int, int, void*);
+size_t mve_linattn_workspace_bytes(int, int, int, int);
+int mve_linattn_kv(int, const void*, int, const void*, int, int, int, int, int, float*, void*, size_t, void*);
+int mve_linattn_apply(int, const void*, int, const float*, void*, int, int, int, int, int, float, void*);
+int mve_dsmax_stats(const float*, int, int, int, int, float*, float*, void*);
+int mve_dsmax_conf(const float*, int, int, int, int, const float*, const float*, float*, void*);
+size_t mve_dsmax_select_workspace_bytes(int, int, int);
+int mve_dsmax_select(const float*, int, int, int, int, int, float, int, float, int64_t*, int64_t*, int64_t*, float*, float*, float*, int*, void*, size_t, void*);
+int mve_loftr_unfold(int, const void*, int, int, int, int, const int64_t*, const int64_t*, int, void*, void*);
+int mve_loftr_ln_add(int, const void*, int, const void*, int, void*, int, int, int, const float*, const float*, float, void*);
+int mve_loftr_gather_rows(int, const void*, int, int, int, const int64_t*, const int64_t*, int, void*, void*);
+int mve_loftr_fine_match(int, const void*, const void*, int, int, const float*, float, float*, float*, void*);
 }
 
 namespace {
@@ -149,6 +163,8 @@ struct Config {
     // dp_stem = stem width, dp_stage / dp_depth = the three stages' widths / depths, dp_tap = the two tapped ViT blocks (hooks[2], hooks[3]),
     // dp_inter = MLP width, dp_neck = channels of act_postprocess3 / 4, dp_features = decoder width
     int dpt = 0, dp_image = 0, dp_stem = 0, dp_stage[3] = {0, 0, 0}, dp_depth[3] = {0, 0, 0}, dp_tap[2] = {0, 0}, dp_inter = 0, dp_neck[2] = {0, 0}, dp_features = 0;
+    // LoFTR matcher (loftr/loftr.py with default_cfg; builder_loftr.h): a fixed topology, nothing to configure but the dtype
+    int loftr = 0;
     int dtype, in_ch, out_ch, n_levels, layers_per_block, ctx_dim, groups, linear_proj;
     // UNet2DConditionModel / ControlNetModel addition_embed_type (mve_unet_set_addition_embed): 0 none, 1 'text_time' (SDXL);
     // add_time_dim = addition_time_embed_dim, add_P = projection_class_embeddings_input_dim (in_features of add_embedding.linear_1)
@@ -186,6 +202,8 @@ struct Run {
     const float* add_ids = nullptr;           //              (mve_unet_bind_added_cond)
     int add_text_dtype = 0, add_text_dim = 0, add_n_ids = 0;
     int clip_eos = 0;                         // CLIP text tower: eos_token_id of this forward (pooling rule of mve_clip_pool)
+    int loftr_M = 0, loftr_border = 2;        // LoFTR: match count of the fine call (host value), border / threshold of the coarse selection
+    float loftr_thr = 0.2f;
     hipStream_t stream;
     void* p(const Ref& r) const {
         switch (r.kind) {
@@ -352,7 +370,7 @@ struct XfDesc { std::string name; int c, heads, layers; };
 
 void enumerate(const Config& c, std::vector<ResnetDesc>& rs, std::vector<XfDesc>& xs) {
     const int n = c.n_levels, L = c.layers_per_block;
-    if (c.sr || c.lpips || c.clip || c.clipv || c.resampler || c.dpt) return;     // plain conv stacks / the CLIP towers, the Resampler (builder_clip*.h), DPT (builder_dpt.h)
+    if (c.sr || c.lpips || c.clip || c.clipv || c.resampler || c.dpt || c.loftr) return;     // plain conv stacks / the CLIP towers, the Resampler (builder_clip*.h), DPT (builder_dpt.h), LoFTR (builder_loftr.h)
     if (c.vae) {      // diffusers Encoder / Decoder (autoencoders/vae.py): resnets only, one attention in the mid block
         const int Cm = c.ch[n - 1];
         if (c.vae == 2) {

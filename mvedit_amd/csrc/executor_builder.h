@@ -485,13 +485,14 @@ struct Builder {
         return out;
     }
 
-    // network-specific plan builders (builder_unet.h, builder_vae.h, builder_sr.h, builder_lpips.h, builder_clip.h, builder_clip_vision.h, builder_dpt.h)
+    // network-specific plan builders (builder_unet.h, builder_vae.h, builder_sr.h, builder_lpips.h, builder_clip.h, builder_clip_vision.h, builder_dpt.h, builder_loftr.h)
     Ref vae_attention(const std::string& name, Ref x, int C, int H, int W);
     int build_lpips(int B_, int H, int W, int io_dtype);
     int build_clip(int B_, int L);
     int build_clip_vision(int B_);
     int build_resampler(int B_, int n1);
     int build_dpt(int B_);
+    int build_loftr(int N_, int H, int W, int phase);
     int build_sr(int B_, int H, int W, int io_dtype);
     int build_vae(int B_, int H, int W, int io_dtype);
     int build(int B_, int H, int W, int n_img, int has_res, int io_dtype, int res_nhwc);

@@ -109,6 +109,40 @@ void layout_params(Unet& u) {
         u.slab_bytes = sb.top;
         return;
     }
+    if (c.loftr) {
+        // Engine-side slot names (mvedit_amd/matcher.py maps the checkpoint's keys onto them: BatchNorm folded into the convolution in front of it,
+        // the 196-wide stage padded to 200 channels with zeros, k | v concatenated, conv K order): the loader converts a tensor of the slot's size.
+        auto w16 = [&](const std::string& n, size_t elems) { sb.add(n, elems, false); need(n); };
+        auto f32 = [&](const std::string& n, size_t elems) { sb.add(n, elems, true); need(n); };
+        const size_t Wd[3] = {128, 200, 256};
+        w16("stem.w", 128 * 56); f32("stem.b", 128);
+        size_t cin = 128;
+        for (int s = 0; s < 3; ++s) {
+            const size_t co = Wd[s];
+            for (int m = 0; m < 2; ++m) {
+                const std::string b = "l" + std::to_string(s + 1) + ".b" + std::to_string(m);
+                w16(b + ".c1.w", co * 9 * (m == 0 ? cin : co)); f32(b + ".c1.b", co);
+                w16(b + ".c2.w", co * 9 * co); f32(b + ".c2.b", co);
+                if (m == 0 && s > 0) { w16(b + ".ds.w", co * cin); f32(b + ".ds.b", co); }
+            }
+            cin = co;
+        }
+        w16("l3oc.w", 256 * 256); w16("l2oc.w", 256 * 200); w16("l1oc.w", 200 * 128);
+        w16("l2oc2.0.w", 256 * 9 * 256); f32("l2oc2.0.b", 256); w16("l2oc2.3.w", 200 * 9 * 256);
+        w16("l1oc2.0.w", 200 * 9 * 200); f32("l1oc2.0.b", 200); w16("l1oc2.3.w", 128 * 9 * 200);
+        for (int t = 0; t < 2; ++t) {
+            const size_t C = t == 0 ? 256 : 128;
+            for (int k = 0; k < (t == 0 ? 8 : 2); ++k) {
+                const std::string b = (t == 0 ? "c" : "f") + std::to_string(k);
+                w16(b + ".q.w", C * C); w16(b + ".kv.w", 2 * C * C); w16(b + ".merge.w", C * C);
+                w16(b + ".mlp0.w", 4 * C * C); w16(b + ".mlp2.w", 2 * C * C);
+                f32(b + ".n1.g", C); f32(b + ".n1.b", C); f32(b + ".n2.g", C); f32(b + ".n2.b", C);
+            }
+        }
+        w16("dp.w", 128 * 256); f32("dp.b", 128); w16("mf.w", 128 * 256); f32("mf.b", 128);
+        u.slab_bytes = sb.top;
+        return;
+    }
     if (c.dpt) {
         // Engine-side slot names: the Python side (mvedit_amd/normal_model.py) maps the checkpoint's keys onto them and does every transformation
         // that is more than a copy -- weight standardisation, q|k|v concatenation, the readout's token / class halves, the conv K order, padding --
@@ -438,9 +472,9 @@ int load_param(Unet& u, const std::string& name, const void* src, int src_dtype,
     const int Cm_ = c.ch[c.n_levels - 1];
     const int vin = c.vae == 1 ? Cm_ : c.ch[0], vout = c.vae == 1 ? c.ch[0] : Cm_;     // widths after conv_in / before conv_out
     const std::string va = "mid_block.attentions.0";
-    if (c.dpt) {
+    if (c.dpt || c.loftr) {
         Param* p = P(name);
-        MVE_CHECK(p, MVE_ERR_ARG, "load_param: %s is not a slot of this DPT model", name.c_str());
+        MVE_CHECK(p, MVE_ERR_ARG, "load_param: %s is not a slot of this %s model", name.c_str(), c.dpt ? "DPT" : "LoFTR");
         rc = vec(p, 0, (long long)(p->bytes / (p->f32 ? 4 : 2)), 1);
     } else if (c.clipv) {
         const long long C = c.ch[0], I = c.clip_inter, PP3 = 3ll * c.cv_patch * c.cv_patch, Kp = (PP3 + 7) / 8 * 8, G = c.cv_image / c.cv_patch;

@@ -17,7 +17,7 @@
 //   * per-op HIP-event profiling and analytic FLOP accounting are built in (bench.py's roofline).
 //
 // Source layout (one translation unit): executor.h (types) -> executor_params.h (parameter slab + loader) -> executor_builder.h (plan
-// builder, shared blocks) -> builder_{unet,vae,sr,lpips,clip,clip_vision,dpt}.h (one plan builder per network) -> this file (plan cache + C ABI).
+// builder, shared blocks) -> builder_{unet,vae,sr,lpips,clip,clip_vision,dpt,loftr}.h (one plan builder per network) -> this file (plan cache + C ABI).
 #include "executor_builder.h"
 #include "builder_unet.h"
 #include "builder_vae.h"
@@ -26,6 +26,7 @@
 #include "builder_clip.h"
 #include "builder_clip_vision.h"
 #include "builder_dpt.h"
+#include "builder_loftr.h"
 
 namespace {
 
@@ -45,7 +46,7 @@ int ensure_plan(Unet& u, int B, int H, int W, int n_img, int has_res, int io_dty
     Builder b(u, *np);
     b.ctx_rows_per_img = ctx_len;
     u.cur = nullptr;
-    const int rc = u.cfg.dpt ? b.build_dpt(B) : u.cfg.clipv ? b.build_clip_vision(B) : u.cfg.resampler ? b.build_resampler(B, H) : u.cfg.clip ? b.build_clip(B, H) : u.cfg.lpips ? b.build_lpips(B, H, W, io_dtype) : u.cfg.sr ? b.build_sr(B, H, W, io_dtype) : u.cfg.vae ? b.build_vae(B, H, W, io_dtype) : b.build(B, H, W, n_img, has_res, io_dtype, res_nhwc);
+    const int rc = u.cfg.loftr ? b.build_loftr(B, H, W, n_img) : u.cfg.dpt ? b.build_dpt(B) : u.cfg.clipv ? b.build_clip_vision(B) : u.cfg.resampler ? b.build_resampler(B, H) : u.cfg.clip ? b.build_clip(B, H) : u.cfg.lpips ? b.build_lpips(B, H, W, io_dtype) : u.cfg.sr ? b.build_sr(B, H, W, io_dtype) : u.cfg.vae ? b.build_vae(B, H, W, io_dtype) : b.build(B, H, W, n_img, has_res, io_dtype, res_nhwc);
     if (rc != MVE_OK) return rc;
     np->ctx_len = ctx_len;
     np->last_use = u.tick;
@@ -614,6 +615,97 @@ int mve_dpt_forward(void* handle, const void* d_pixels, int B, void* d_out, void
     return run_plan_ops(pl, r, op_ms);
 }
 
+int mve_loftr_create(void** handle, int dtype) {
+    MVE_CHECK(handle, MVE_ERR_ARG, "loftr_create: null handle");
+    MVE_CHECK(dtype == MVE_F16 || dtype == MVE_BF16, MVE_ERR_ARG, "loftr_create: dtype must be f16 or bf16");
+    Unet* u = new Unet();
+    Config& c = u->cfg;
+    c.loftr = 1;
+    c.dtype = dtype; c.in_ch = 1; c.out_ch = 1; c.n_levels = 1; c.layers_per_block = 8;
+    c.ctx_dim = 8; c.groups = 1; c.eps = 1e-5f; c.linear_proj = 0;
+    c.ch[0] = 256; c.attn[0] = 0; c.heads[0] = 8; c.tlayers[0] = 0;
+    layout_params(*u);
+    *handle = u;
+    return MVE_OK;
+}
+
+static int loftr_check_shape(const char* who, int phase, int N, int H, int W) {
+    MVE_CHECK(phase == 1 || phase == 2, MVE_ERR_ARG, "%s: phase %d (1 = coarse, 2 = fine)", who, phase);
+    MVE_CHECK(N >= 1 && N <= 4096, MVE_ERR_ARG, "%s: bad N %d", who, N);
+    MVE_CHECK(H >= 8 && W >= 8 && H % 8 == 0 && W % 8 == 0 && H <= 2048 && W <= 2048, MVE_ERR_ARG,
+              "%s: H %d / W %d must be multiples of 8 in [8, 2048] (the position table is 256 x 256 coarse cells)", who, H, W);
+    return MVE_OK;
+}
+
+int mve_loftr_plan(void* handle, int phase, int N, int H, int W, size_t* workspace_bytes, int* n_ops, double* flops) {
+    MVE_CHECK(handle, MVE_ERR_ARG, "loftr_plan: null handle");
+    Unet* u = (Unet*)handle;
+    MVE_CHECK(u->cfg.loftr, MVE_ERR_ARG, "loftr_plan: handle is not a LoFTR model");
+    int rc = loftr_check_shape("loftr_plan", phase, N, H, W);
+    if (rc) return rc;
+    rc = ensure_plan(*u, N, H, W, phase, 0, u->cfg.dtype, 0, 0);
+    if (rc) return rc;
+    if (workspace_bytes) *workspace_bytes = u->cur->ws_bytes;
+    if (n_ops) *n_ops = (int)u->cur->ops.size();
+    if (flops) for (int i = 0; i < OC_COUNT; ++i) flops[i] = u->cur->flops[i];
+    return MVE_OK;
+}
+
+static int loftr_run(Unet* u, const char* who, int phase, int N, int H, int W, const void* d_images, const float* d_pos, int M, float thr, int border, void* const* d_io,
+                     void* const* d_taps, int n_taps, void* d_workspace, size_t workspace_bytes, float* op_ms, void* stream) {
+    {
+        char first[256];
+        const int miss = mve_unet_missing_params(u, first, sizeof(first));
+        MVE_CHECK(miss == 0, MVE_ERR_STATE, "%s: %d parameters not loaded (first: %s)", who, miss, first);
+    }
+    MVE_CHECK(d_io, MVE_ERR_ARG, "%s: null pointer (d_io)", who);
+    for (int i = 0; i < LOFTR_IO; ++i) {
+        const bool used = phase == 1 ? i <= 10 : (i <= 1 || (i >= 4 && i <= 6) || i == 9 || i >= 11);
+        MVE_CHECK(!used || (d_io[i] && ((uintptr_t)d_io[i] & 15) == 0), MVE_ERR_ARG, "%s: d_io[%d] is null or not 16-byte aligned", who, i);
+    }
+    int rc = ensure_plan(*u, N, H, W, phase, 0, u->cfg.dtype, 0, 0);
+    if (rc) return rc;
+    const Plan& pl = *u->cur;
+    MVE_CHECK(d_workspace && workspace_bytes >= pl.ws_bytes, MVE_ERR_NOMEM, "%s: workspace %zu < required %zu", who, workspace_bytes, pl.ws_bytes);
+    std::vector<void*> ptrs(LOFTR_IO + LOFTR_TAPS_COARSE, nullptr);
+    for (int i = 0; i < LOFTR_IO; ++i) ptrs[i] = d_io[i];
+    if (d_taps)
+        for (int i = 0; i < n_taps; ++i) ptrs[LOFTR_IO + i] = d_taps[i];      // a null entry: that tap is not wanted
+    Run r;
+    r.ws = (unsigned char*)d_workspace; r.wt = u->slab;
+    r.sample = d_images; r.timesteps = nullptr; r.ctx = d_pos; r.out = nullptr;
+    r.down_res = nullptr; r.mid_res = nullptr; r.ref_store = nullptr;
+    r.cn_out = ptrs.data();
+    r.loftr_M = M; r.loftr_thr = thr; r.loftr_border = border;
+    r.stream = (hipStream_t)stream;
+    return run_plan_ops(pl, r, op_ms);
+}
+
+int mve_loftr_forward_coarse(void* handle, const void* d_images, const float* d_pos, int N, int H, int W, float thr, int border, void* const* d_io, void* const* d_taps,
+                             void* d_workspace, size_t workspace_bytes, float* op_ms, void* stream) {
+    MVE_CHECK(handle, MVE_ERR_ARG, "loftr_forward_coarse: null handle");
+    Unet* u = (Unet*)handle;
+    MVE_CHECK(u->cfg.loftr, MVE_ERR_ARG, "loftr_forward_coarse: handle is not a LoFTR model");
+    const int rc = loftr_check_shape("loftr_forward_coarse", 1, N, H, W);
+    if (rc) return rc;
+    MVE_CHECK(d_images && d_pos && ((uintptr_t)d_images & 15) == 0 && ((uintptr_t)d_pos & 15) == 0, MVE_ERR_ARG, "loftr_forward_coarse: d_images / d_pos null or not 16-byte aligned");
+    return loftr_run(u, "loftr_forward_coarse", 1, N, H, W, d_images, d_pos, 0, thr, border, d_io, d_taps, LOFTR_TAPS_COARSE, d_workspace, workspace_bytes, op_ms, stream);
+}
+
+int mve_loftr_forward_fine(void* handle, int N, int H, int W, int M, void* const* d_io, void* const* d_taps, void* d_workspace, size_t workspace_bytes, float* op_ms,
+                           void* stream) {
+    MVE_CHECK(handle, MVE_ERR_ARG, "loftr_forward_fine: null handle");
+    Unet* u = (Unet*)handle;
+    MVE_CHECK(u->cfg.loftr, MVE_ERR_ARG, "loftr_forward_fine: handle is not a LoFTR model");
+    const int rc = loftr_check_shape("loftr_forward_fine", 2, N, H, W);
+    if (rc) return rc;
+    MVE_CHECK(M >= 1 && (long long)M <= (long long)N * (H / 8) * (W / 8), MVE_ERR_ARG, "loftr_forward_fine: M %d must be in [1, N * L = %lld] (no fine call for an empty match set)", M,
+              (long long)N * (H / 8) * (W / 8));
+    return loftr_run(u, "loftr_forward_fine", 2, N, H, W, nullptr, nullptr, M, 0.f, 0, d_io, d_taps, LOFTR_TAPS_FINE, d_workspace, workspace_bytes, op_ms, stream);
+}
+
+int mve_loftr_destroy(void* handle) { return mve_unet_destroy(handle); }
+
 int mve_lpips_create(void** handle, int dtype, int normalize_inputs) {
     MVE_CHECK(handle, MVE_ERR_ARG, "lpips_create: null handle");
     MVE_CHECK(dtype == MVE_F16 || dtype == MVE_BF16, MVE_ERR_ARG, "lpips_create: dtype must be f16 or bf16");
@@ -754,8 +846,8 @@ int mve_unet_forward(void* handle, int phase, const void* d_sample, int io_dtype
                      float* op_ms /* optional host array [n_ops]: per-op milliseconds (synchronises) */, void* stream) {
     MVE_CHECK(handle, MVE_ERR_ARG, "unet_forward: null handle");
     Unet* u = (Unet*)handle;
-    MVE_CHECK(!u->cfg.controlnet && !u->cfg.vae && !u->cfg.sr && !u->cfg.lpips && !u->cfg.clip && !u->cfg.clipv && !u->cfg.resampler && !u->cfg.dpt, MVE_ERR_ARG,
-              "unet_forward: handle is a ControlNet / VAE / SRVGG / CLIP text or vision tower / Resampler / DPT (use their own forward calls)");
+    MVE_CHECK(!u->cfg.controlnet && !u->cfg.vae && !u->cfg.sr && !u->cfg.lpips && !u->cfg.clip && !u->cfg.clipv && !u->cfg.resampler && !u->cfg.dpt && !u->cfg.loftr, MVE_ERR_ARG,
+              "unet_forward: handle is a ControlNet / VAE / SRVGG / CLIP text or vision tower / Resampler / DPT / LoFTR (use their own forward calls)");
     {
         char first[256];
         const int miss = mve_unet_missing_params(handle, first, sizeof(first));
@@ -872,7 +964,7 @@ int mve_unet_set_attention(void* handle, int ip_tokens, float ip_scale, int ref_
 int mve_unet_set_residual_mode(void* handle, int pair) {
     MVE_CHECK(handle, MVE_ERR_ARG, "unet_set_residual_mode: null handle");
     Unet* u = (Unet*)handle;
-    MVE_CHECK(!u->cfg.vae && !u->cfg.sr && !u->cfg.lpips && !u->cfg.clip && !u->cfg.clipv && !u->cfg.resampler && !u->cfg.dpt, MVE_ERR_ARG, "unet_set_residual_mode: a UNet / ControlNet handle is needed");
+    MVE_CHECK(!u->cfg.vae && !u->cfg.sr && !u->cfg.lpips && !u->cfg.clip && !u->cfg.clipv && !u->cfg.resampler && !u->cfg.dpt && !u->cfg.loftr, MVE_ERR_ARG, "unet_set_residual_mode: a UNet / ControlNet handle is needed");
     const int old = u->ao.residual_pair;
     if (pair >= 0) u->ao.residual_pair = pair ? 1 : 0;     // part of the plan key: plans of either mode stay cached side by side
     return old;
@@ -901,7 +993,7 @@ int mve_unet_set_addition_embed(void* handle, int addition_type, int addition_ti
     MVE_CHECK(handle, MVE_ERR_ARG, "unet_set_addition_embed: null handle");
     Unet* u = (Unet*)handle;
     Config& c = u->cfg;
-    MVE_CHECK(!c.vae && !c.sr && !c.lpips && !c.clip && !c.clipv && !c.resampler && !c.dpt, MVE_ERR_ARG, "unet_set_addition_embed: a UNet / ControlNet handle is needed");
+    MVE_CHECK(!c.vae && !c.sr && !c.lpips && !c.clip && !c.clipv && !c.resampler && !c.dpt && !c.loftr, MVE_ERR_ARG, "unet_set_addition_embed: a UNet / ControlNet handle is needed");
     MVE_CHECK(addition_type == 0 || addition_type == 1, MVE_ERR_ARG, "unet_set_addition_embed: addition type %d (0 = none, 1 = text_time)", addition_type);
     MVE_CHECK(!u->slab && u->loaded.empty(), MVE_ERR_STATE, "unet_set_addition_embed: parameters are already loaded; declare the embedding right after create");
     MVE_CHECK(!c.add_type, MVE_ERR_STATE, "unet_set_addition_embed: the handle already has an addition embedding");

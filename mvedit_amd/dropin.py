@@ -37,7 +37,8 @@ Not part of `install()`: `swap_text_encoder(pipe)` puts native CLIP text towers 
 `pipe.text_encoder_2` of ONE pipeline object, on request; `swap_image_encoder(obj)` puts the native CLIP vision tower
 (mvedit_amd/vision_encoder.py) behind `image_encoder` / `vision_encoder` and the native image projection (mvedit_amd/ip_adapter.py) behind
 `image_proj_model` of ONE object (an `IPAdapter`, a `Zero123PlusPipeline`, a `Zero123Pipeline`), on request; `swap_normal_model(pipe)` puts the
-native DPT-hybrid normal predictor (mvedit_amd/normal_model.py) behind `pipe.normal_model`, on request.
+native DPT-hybrid normal predictor (mvedit_amd/normal_model.py) behind `pipe.normal_model`, on request; `swap_matcher(runner)` puts the native
+LoFTR matcher (mvedit_amd/matcher.py) behind a loaded `runner.matcher`, on request.
 
 Nothing here computes: every replacement is one of the engines / mirrors INTEGRATION.md documents seam by seam, and a conversion that fails
 raises -- there is no fallback to the torch module.  `uninstall()` restores everything (tests).
@@ -255,6 +256,32 @@ def swap_normal_model(pipe):
         object.__setattr__(m, '_mve_engine', cached)
     object.__setattr__(pipe, 'normal_model', cached[1])
     return pipe
+
+
+def make_matcher(m):
+    """The reference's `LoFTR(config=default_cfg)` (`init_matcher`, lib/core/utils/pose_estimation.py; held as `runner.matcher`,
+    lib/apis/adapter3d.py:411-415)."""
+    from .matcher import LoFTREngine
+    dtype, device = _module_dtype_device(m)
+    return LoFTREngine.from_module(m, dtype=dtype, device=device)
+
+
+def swap_matcher(obj):
+    """Opt-in (install() / swap_engines leave `matcher` alone): replaces a loaded `obj.matcher` by a native engine built from that module.
+    `matcher=None` (the runner before `load_matcher`, or after `unload_matcher`) stays `None`.  Idempotent; the engine is cached on the source
+    module like the other seams'."""
+    m = getattr(obj, 'matcher', None)
+    if m is None or getattr(m, '_mve_is_engine', False) or not hasattr(m, 'state_dict'):
+        return obj
+    fp = _fingerprint(m)
+    cached = getattr(m, '_mve_engine', None)
+    if cached is None or cached[0] != fp:
+        eng = make_matcher(m)
+        object.__setattr__(eng, '_mve_is_engine', True)
+        cached = (fp, eng)
+        object.__setattr__(m, '_mve_engine', cached)
+    object.__setattr__(obj, 'matcher', cached[1])
+    return obj
 
 
 MAKERS = dict(unet=make_unet, controlnet=make_controlnet, vae=make_vae, image_enhancer=make_image_enhancer, segmentation=make_segmentation,
