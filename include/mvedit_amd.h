@@ -752,7 +752,8 @@ MVE_API int mve_unet_load_param(void* handle, const char* name, const void* d_sr
 MVE_API int mve_unet_missing_params(void* handle, char* buf, int buf_len);
 
 /* (No reference counterpart: executor introspection.)  Builds (and caches) the static op list for this problem size.
- * flops[5] = analytic 2*MAC counts per class {conv3x3, linear/1x1, attention, norm, other}; SURVEY.md section 8(d) quotes their sum. */
+ * flops[5] = analytic 2*MAC counts per class {conv3x3, linear/1x1, attention, norm, other}; SURVEY.md section 8(d) quotes their sum.
+ * For UNet and ControlNet handles; a handle of another kind is MVE_ERR_ARG (the other engines have their own *_plan). */
 MVE_API int mve_unet_plan(void* handle, int B, int H, int W, int ctx_len, int num_cross_attn_imgs, int has_residuals,
                           int io_dtype, int residuals_nhwc, size_t* workspace_bytes, int* n_ops, double* flops);
 
@@ -792,7 +793,7 @@ MVE_API int mve_controlnet_set_cond_repeat(void* handle, int repeat);
  * of every item's d_ctx: the cross-attention K/V GEMM reads the first ctx_len - n rows of each item (one strided device copy inside the plan, no
  * caller-side copy), bit-identical to passing those rows as a dense [B, ctx_len - n, D] context.  n >= ctx_len is MVE_ERR_ARG at plan time, as is
  * the combination with ip_tokens > 0 (mve_unet_set_attention).  Part of the plan key, and with it of the hipGraph key.  Returns the previous
- * value (rows < 0: query). */
+ * value (rows < 0: query).  A handle that is neither a UNet nor a ControlNet is MVE_ERR_ARG. */
 MVE_API int mve_unet_set_context_tail(void* handle, int rows);
 MVE_API int mve_controlnet_forward(void* handle, const void* d_sample, int io_dtype, const float* d_timesteps, const void* d_ctx,
                                    const void* d_cond, int B, int H, int W, int ctx_len, float conditioning_scale, int accumulate,
@@ -1014,7 +1015,7 @@ MVE_API int mve_unet_set_residual_mode(void* handle, int pair);
  * outlive the prefix to the second.  The launches are the full-batch problem's either way (same tiles, same K slices), so the output is bit-identical
  * to the switch-off output for ANY input; nothing is decided on the host and a graph replay re-evaluates the flag.  Planned when B is even,
  * (B / 2) % num_cross_attn_imgs == 0 and reference attention is off; ControlNet handles are not covered.  on < 0: query.  Returns the previous value;
- * the switch is part of the plan key. */
+ * the switch is part of the plan key.  A handle of any kind but a UNet is MVE_ERR_ARG. */
 MVE_API int mve_unet_tune_cfg_prefix(void* handle, int on);
 /* Diagnostics (tests / tools): synchronises the stream of the last mve_unet_forward that ran a prologue and returns its flag -- 1: the halves were
  * identical and the prefix ran once, 0: they differed, -1: that plan had no prefix.  Errors are MVE_ERR_HIP, or MVE_ERR_STATE for a null handle (-1 is taken). */

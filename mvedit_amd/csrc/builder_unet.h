@@ -136,7 +136,7 @@ int Builder::build(int B_, int H, int W, int n_img, int has_res, int io_dtype, i
     struct Skip { Ref r; int C, H, W; };
     std::vector<Skip> skips;
     Ref x = ws_stream((size_t)M0 * c.ch[0] * e);
-    if (c.controlnet) {
+    if (c.kind == Kind::ControlNet) {
         // controlnet_cond_embedding on the 8H x 8W conditioning image, added to conv_in(sample)
         const int Hc = 8 * H, Wc = 8 * W, cc = c.cond_ch;
         // cn_cond_repeat = R: Bc = Bb / R conditioning images, item b of the batch uses image b mod Bc (the two halves of a CFG batch share them)
@@ -181,7 +181,7 @@ int Builder::build(int B_, int H, int W, int n_img, int has_res, int io_dtype, i
     // CFG prefix (executor_builder.h): planned for a UNet batch of two equal halves whose cross-image groups do not straddle the middle.  Reference
     // attention exempts the CFG-first item (ref_skip), so its halves differ; ControlNet engines are the follow-up.  conv_in stays outside: its output
     // is a skip the last up-block reads at full batch, and it costs less than broadcasting it would.
-    if (!c.controlnet && pl.ao.cfg_prefix && Bb % 2 == 0 && (Bb / 2) % n_img == 0 && pl.ao.ref_mode == 0)
+    if (c.kind != Kind::ControlNet && pl.ao.cfg_prefix && Bb % 2 == 0 && (Bb / 2) % n_img == 0 && pl.ao.ref_mode == 0)
         begin_prefix((size_t)(Bb / 2) * c.in_ch * H * W * esz(io_dtype), (size_t)(Bb / 2) * ld_temb * 4);
     skips.push_back({x, c.ch[0], H, W});
     int h = H, w = W, cin = c.ch[0];
@@ -209,7 +209,7 @@ int Builder::build(int B_, int H, int W, int n_img, int has_res, int io_dtype, i
     }
     end_prefix();          // (a network without cross-attention in its down path: the prefix does not reach into unet_dec)
     pl.enc_end = pl.ops.size();
-    if (c.controlnet) {
+    if (c.kind == Kind::ControlNet) {
         const int C = c.ch[n - 1];
         for (size_t i = 0; i < skips.size(); ++i)
             zero_conv(skips[i].r, skips[i].C, Bb * skips[i].H * skips[i].W, skips[i].H * skips[i].W, "controlnet_down_blocks." + std::to_string(i), (int)i);

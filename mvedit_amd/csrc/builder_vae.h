@@ -51,9 +51,9 @@ int Builder::build_vae(int B_, int H, int W, int io_dtype) {
     ld_temb = 0; ld_kv = 0;
     const int f = 1 << (n - 1);
     MVE_CHECK((H * W) % 8 == 0, MVE_ERR_ARG, "vae: input size %dx%d must have a multiple of 8 pixels", H, W);
-    if (c.vae == 2) MVE_CHECK(H % f == 0 && W % f == 0 && ((H / f) * (W / f)) % 8 == 0, MVE_ERR_ARG, "vae: image size %dx%d must be divisible by %d", H, W, f);
+    if (c.kind == Kind::VaeEncoder) MVE_CHECK(H % f == 0 && W % f == 0 && ((H / f) * (W / f)) % 8 == 0, MVE_ERR_ARG, "vae: image size %dx%d must be divisible by %d", H, W, f);
     const int wide = n > 1 && c.ch[1] > c.ch[0] ? c.ch[1] : c.ch[0];      // widest tensor at image resolution
-    MVE_CHECK((size_t)Bb * H * W * (c.vae == 1 ? (size_t)f * f : 1) * wide < ((size_t)1 << 31), MVE_ERR_ARG,
+    MVE_CHECK((size_t)Bb * H * W * (c.kind == Kind::VaeDecoder ? (size_t)f * f : 1) * wide < ((size_t)1 << 31), MVE_ERR_ARG,
               "vae: batch %d at this size overflows 32-bit activation indexing; decode / encode in smaller batches", Bb);
     const int M0 = Bb * H * W;
     Ref x_in = ws((size_t)M0 * 8 * e);
@@ -65,7 +65,7 @@ int Builder::build_vae(int B_, int H, int W, int io_dtype) {
     rows_img = H * W;
     int h = H, w = W;
     Ref x;
-    if (c.vae == 1) {
+    if (c.kind == Kind::VaeDecoder) {
         Ref z = ws((size_t)M0 * 8 * e);
         gemm(x_in, 8, wt("pq_conv.w"), 8, z, 8, M0, 8, 8, wt("pq_conv.b"), Ref(), 0, 0, Ref(), 0, 0, "post_quant_conv");
         rel(x_in);
@@ -103,7 +103,7 @@ int Builder::build_vae(int B_, int H, int W, int io_dtype) {
         rel(z);
     }
     int cur = Cm;
-    if (c.vae == 1) {
+    if (c.kind == Kind::VaeDecoder) {
         for (int i = 0; i < n; ++i) {
             const int cout = c.ch[n - 1 - i];
             for (int j = 0; j < L + 1; ++j) {
@@ -129,7 +129,7 @@ int Builder::build_vae(int B_, int H, int W, int io_dtype) {
     gn(x, cur, Ref(), 0, Bb, h * w, c.eps, wt("norm_out.g"), wt("norm_out.b"), 1, hn, "conv_norm_out+silu");
     rel(x);
     Ref o8 = ws((size_t)Mo * 8 * 4);
-    if (c.vae == 1) {
+    if (c.kind == Kind::VaeDecoder) {
         conv(hn, cur, Bb, h, w, 1, 0, wt("conv_out.w"), 8, o8, wt("conv_out.b"), Ref(), 0, Ref(), MVE_GEMM_OUT_F32, "conv_out");
         rel(hn);
     } else {

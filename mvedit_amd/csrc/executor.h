@@ -143,28 +143,50 @@ __global__ void k_group_mean(const typename Tag::T* __restrict__ x, typename Tag
 // ---------------------------------------------------------------------------------------------------
 constexpr int CN_EMB[4] = {16, 32, 96, 256};      // diffusers ControlNetModel conditioning_embedding_out_channels (default)
 
+// which network a handle runs: one executor, one plan builder per kind (builder_*.h)
+enum class Kind { UNet, ControlNet, VaeDecoder, VaeEncoder, Srvgg, Lpips, ClipText, ClipVision, Resampler, Dpt, Loftr };
+
+// the noun of "handle is ..., not ..." messages
+const char* kind_name(Kind k) {
+    switch (k) {
+        case Kind::UNet: return "a UNet";
+        case Kind::ControlNet: return "a ControlNet";
+        case Kind::VaeDecoder: case Kind::VaeEncoder: return "a VAE half";
+        case Kind::Srvgg: return "an SRVGGNetCompact";
+        case Kind::Lpips: return "an LPIPS engine";
+        case Kind::ClipText: return "a CLIP text tower";
+        case Kind::ClipVision: return "a CLIP vision tower";
+        case Kind::Resampler: return "a Resampler";
+        case Kind::Dpt: return "a DPT model";
+        case Kind::Loftr: return "a LoFTR model";
+    }
+    return "an unknown engine";
+}
+
 struct Config {
-    int controlnet = 0, cond_ch = 3;   // ControlNetModel: encoder + mid of the UNet, conditioning embedding, zero convolutions
-    int lpips = 0, lpips_normalize = 1; // LPIPS(net='vgg') forward + backward w.r.t. the prediction (lib/models/losses/lpips_loss.py)
-    int sr = 0, sr_scale = 4;          // SRVGGNetCompact (lib/models/decoders/image_space_ss.py): ch[0] = num_feat, layers_per_block = num_conv
-    int vae = 0;                       // AutoencoderKL half: 1 = post_quant_conv + Decoder, 2 = Encoder + quant_conv (no time embedding,
-                                       // no transformers; in_ch / out_ch are the half's own input / output channels, both <= 8)
+    Kind kind = Kind::UNet;
+    bool is_denoiser() const { return kind == Kind::UNet || kind == Kind::ControlNet; }
+    bool is_vae() const { return kind == Kind::VaeDecoder || kind == Kind::VaeEncoder; }
+    int cond_ch = 3;                   // ControlNetModel: encoder + mid of the UNet, conditioning embedding, zero convolutions
+    int lpips_normalize = 1;           // LPIPS(net='vgg') forward + backward w.r.t. the prediction (lib/models/losses/lpips_loss.py)
+    int sr_scale = 4;                  // SRVGGNetCompact (lib/models/decoders/image_space_ss.py): ch[0] = num_feat, layers_per_block = num_conv
+    // AutoencoderKL halves: VaeDecoder = post_quant_conv + Decoder, VaeEncoder = Encoder + quant_conv (no time embedding, no transformers;
+    // in_ch / out_ch are the half's own input / output channels, both <= 8)
     // CLIPTextModel(WithProjection) (transformers models/clip/modeling_clip.py): ch[0] = hidden_size, heads[0] = num_attention_heads,
     // layers_per_block = num_hidden_layers, eps = layer_norm_eps; clip_proj = projection_dim (0: no text_projection)
-    int clip = 0, clip_vocab = 0, clip_max_pos = 0, clip_inter = 0, clip_act = 0, clip_proj = 0;
+    int clip_vocab = 0, clip_max_pos = 0, clip_inter = 0, clip_act = 0, clip_proj = 0;
     // CLIPVisionModel(WithProjection): ch[0] / heads[0] / layers_per_block / eps / clip_inter / clip_act / clip_proj as for the text tower;
     // cv_image = image_size, cv_patch = patch_size (builder_clip_vision.h)
-    int clipv = 0, cv_image = 0, cv_patch = 0;
+    int cv_image = 0, cv_patch = 0;
     // IP-Adapter Resampler (lib/models/architecture/ip_adapter/resampler.py): ch[0] = dim, heads[0] = heads (dim_head 64), layers_per_block = depth,
     // rs_queries = num_queries, rs_embed = embedding_dim, rs_out = output_dim, rs_inner = int(dim * ff_mult)
-    int resampler = 0, rs_queries = 0, rs_embed = 0, rs_out = 0, rs_inner = 0;
+    int rs_queries = 0, rs_embed = 0, rs_out = 0, rs_inner = 0;
     // DPT-hybrid (omnidata_modules/midas/dpt_depth.py DPTDepthModel over vit_base_resnet50_384; builder_dpt.h): ch[0] = ViT width, heads[0],
     // layers_per_block = ViT depth, eps = LayerNorm eps, groups = GroupNorm groups of the ResNetV2, out_ch = num_channels; dp_image = image size,
     // dp_stem = stem width, dp_stage / dp_depth = the three stages' widths / depths, dp_tap = the two tapped ViT blocks (hooks[2], hooks[3]),
     // dp_inter = MLP width, dp_neck = channels of act_postprocess3 / 4, dp_features = decoder width
-    int dpt = 0, dp_image = 0, dp_stem = 0, dp_stage[3] = {0, 0, 0}, dp_depth[3] = {0, 0, 0}, dp_tap[2] = {0, 0}, dp_inter = 0, dp_neck[2] = {0, 0}, dp_features = 0;
+    int dp_image = 0, dp_stem = 0, dp_stage[3] = {0, 0, 0}, dp_depth[3] = {0, 0, 0}, dp_tap[2] = {0, 0}, dp_inter = 0, dp_neck[2] = {0, 0}, dp_features = 0;
     // LoFTR matcher (loftr/loftr.py with default_cfg; builder_loftr.h): a fixed topology, nothing to configure but the dtype
-    int loftr = 0;
     int dtype, in_ch, out_ch, n_levels, layers_per_block, ctx_dim, groups, linear_proj;
     // UNet2DConditionModel / ControlNetModel addition_embed_type (mve_unet_set_addition_embed): 0 none, 1 'text_time' (SDXL);
     // add_time_dim = addition_time_embed_dim, add_P = projection_class_embeddings_input_dim (in_features of add_embedding.linear_1)
@@ -190,10 +212,10 @@ struct Ref {
 };
 
 struct Run {
-    unsigned char* ws; unsigned char* wt;
-    const void* sample; const float* timesteps; const void* ctx; void* out;
-    const void* const* down_res; const void* mid_res;
-    unsigned char* ref_store;
+    unsigned char* ws = nullptr; unsigned char* wt = nullptr;
+    const void* sample = nullptr; const float* timesteps = nullptr; const void* ctx = nullptr; void* out = nullptr;
+    const void* const* down_res = nullptr; const void* mid_res = nullptr;
+    unsigned char* ref_store = nullptr;
     const void* cn_cond = nullptr;            // ControlNet: conditioning image [B, cond_ch, 8H, 8W] NCHW (io dtype)
     void* const* cn_out = nullptr;            // ControlNet: n_skips + 1 output tensors (NHWC, engine dtype)
     float cn_scale = 1.0f;                    // conditioning_scale
@@ -204,7 +226,7 @@ struct Run {
     int clip_eos = 0;                         // CLIP text tower: eos_token_id of this forward (pooling rule of mve_clip_pool)
     int loftr_M = 0, loftr_border = 2;        // LoFTR: match count of the fine call (host value), border / threshold of the coarse selection
     float loftr_thr = 0.2f;
-    hipStream_t stream;
+    hipStream_t stream = nullptr;
     void* p(const Ref& r) const {
         switch (r.kind) {
             case Ref::WS: return ws + r.off;
@@ -370,10 +392,13 @@ struct XfDesc { std::string name; int c, heads, layers; };
 
 void enumerate(const Config& c, std::vector<ResnetDesc>& rs, std::vector<XfDesc>& xs) {
     const int n = c.n_levels, L = c.layers_per_block;
-    if (c.sr || c.lpips || c.clip || c.clipv || c.resampler || c.dpt || c.loftr) return;     // plain conv stacks / the CLIP towers, the Resampler (builder_clip*.h), DPT (builder_dpt.h), LoFTR (builder_loftr.h)
-    if (c.vae) {      // diffusers Encoder / Decoder (autoencoders/vae.py): resnets only, one attention in the mid block
+    switch (c.kind) {
+        case Kind::UNet: case Kind::ControlNet: case Kind::VaeDecoder: case Kind::VaeEncoder: break;      // resnets and transformers, listed below
+        default: return;     // plain conv stacks / the CLIP towers, the Resampler (builder_clip*.h), DPT (builder_dpt.h), LoFTR (builder_loftr.h)
+    }
+    if (c.is_vae()) {      // diffusers Encoder / Decoder (autoencoders/vae.py): resnets only, one attention in the mid block
         const int Cm = c.ch[n - 1];
-        if (c.vae == 2) {
+        if (c.kind == Kind::VaeEncoder) {
             int cin = c.ch[0];
             for (int i = 0; i < n; ++i) {
                 for (int j = 0; j < L; ++j)
@@ -383,7 +408,7 @@ void enumerate(const Config& c, std::vector<ResnetDesc>& rs, std::vector<XfDesc>
         }
         rs.push_back({"mid_block.resnets.0", Cm, Cm});
         rs.push_back({"mid_block.resnets.1", Cm, Cm});
-        if (c.vae == 1) {
+        if (c.kind == Kind::VaeDecoder) {
             int cin = Cm;
             for (int i = 0; i < n; ++i) {
                 const int cout = c.ch[n - 1 - i];
@@ -405,7 +430,7 @@ void enumerate(const Config& c, std::vector<ResnetDesc>& rs, std::vector<XfDesc>
     rs.push_back({"mid_block.resnets.0", c.ch[n - 1], c.ch[n - 1]});
     xs.push_back({"mid_block.attentions.0", c.ch[n - 1], c.heads[n - 1], c.tlayers[n - 1]});
     rs.push_back({"mid_block.resnets.1", c.ch[n - 1], c.ch[n - 1]});
-    if (c.controlnet) return;
+    if (c.kind == Kind::ControlNet) return;
     int prev = c.ch[n - 1];
     for (int i = 0; i < n; ++i) {
         const int lvl = n - 1 - i, cout = c.ch[lvl];

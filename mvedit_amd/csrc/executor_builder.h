@@ -337,7 +337,7 @@ struct Builder {
         Ref h0 = ws((size_t)M * Cin * e);
         gn(x, C1, skip, C2, B, H * W, c.eps, wt(name + ".norm1.g"), wt(name + ".norm1.b"), 1, h0, "resnet.norm1+silu");
         Ref h1 = ws((size_t)M * Cout * e);
-        Ref tv = c.vae ? Ref() : at(tproj, (size_t)u.temb_off[name] * 4);      // the VAE's resnets have no time embedding
+        Ref tv = c.is_vae() ? Ref() : at(tproj, (size_t)u.temb_off[name] * 4);      // the VAE's resnets have no time embedding
         conv(h0, Cin, B, H, W, 1, 0, wt(name + ".conv1.w"), Cout, h1, wt(name + ".conv1.b"), tv, ld_temb, Ref(), 0, "resnet.conv1");
         rel(h0);
         Ref h2 = ws((size_t)M * Cout * e);

@@ -30,7 +30,8 @@ void layout_params(Unet& u) {
     u.fuse_sc = g_fuse_shortcut != 0;
     for (int i = 0; i < c.n_levels; ++i) u.fuse_sc = u.fuse_sc && (c.ch[i] % 64 == 0);
     auto need = [&](const std::string& n) { u.expected.push_back(n); };
-    if (c.lpips) {
+    switch (c.kind) {
+    case Kind::Lpips: {
         // every VGG conv twice: forward packing and the transposed / flipped packing that turns the same kernel into its dgrad
         for (int i = 0; i < 13; ++i) {
             const std::string n = vgg_name(i), e = "vgg." + std::to_string(i);
@@ -46,7 +47,7 @@ void layout_params(Unet& u) {
         u.slab_bytes = sb.top;
         return;
     }
-    if (c.clip) {
+    case Kind::ClipText: {
         // transformers' names; q_proj / k_proj / v_proj share one [3C, C] matrix and one [3C] bias (one GEMM per layer)
         const size_t C = c.ch[0], I = c.clip_inter;
         const std::string em = "text_model.embeddings.";
@@ -76,7 +77,7 @@ void layout_params(Unet& u) {
         u.slab_bytes = sb.top;
         return;
     }
-    if (c.clipv) {
+    case Kind::ClipVision: {
         // transformers' names, packed as for the text tower; the patch convolution's weight is [C][Kp]: (channel, ky, kx) columns, zero-padded
         // from 3 * P * P to a multiple of 8 (mve_clip_patchify lays out the matching operand rows)
         const size_t C = c.ch[0], I = c.clip_inter, Kp = (3 * (size_t)c.cv_patch * c.cv_patch + 7) / 8 * 8, G = c.cv_image / c.cv_patch;
@@ -109,7 +110,7 @@ void layout_params(Unet& u) {
         u.slab_bytes = sb.top;
         return;
     }
-    if (c.loftr) {
+    case Kind::Loftr: {
         // Engine-side slot names (mvedit_amd/matcher.py maps the checkpoint's keys onto them: BatchNorm folded into the convolution in front of it,
         // the 196-wide stage padded to 200 channels with zeros, k | v concatenated, conv K order): the loader converts a tensor of the slot's size.
         auto w16 = [&](const std::string& n, size_t elems) { sb.add(n, elems, false); need(n); };
@@ -143,7 +144,7 @@ void layout_params(Unet& u) {
         u.slab_bytes = sb.top;
         return;
     }
-    if (c.dpt) {
+    case Kind::Dpt: {
         // Engine-side slot names: the Python side (mvedit_amd/normal_model.py) maps the checkpoint's keys onto them and does every transformation
         // that is more than a copy -- weight standardisation, q|k|v concatenation, the readout's token / class halves, the conv K order, padding --
         // so the loader below only converts a tensor of the slot's size (16-bit slots in the engine dtype, fp32 slots as they are).
@@ -198,7 +199,7 @@ void layout_params(Unet& u) {
         u.slab_bytes = sb.top;
         return;
     }
-    if (c.resampler) {
+    case Kind::Resampler: {
         // the reference's state_dict() names; Linear weights as they come ([out][in]), LayerNorm affine parameters and biases in fp32
         const size_t D = c.ch[0], inner = (size_t)c.heads[0] * 64, F = c.rs_inner, E = c.rs_embed, O = c.rs_out, Q = c.rs_queries;
         sb.add("latents", Q * D, false); need("latents");
@@ -225,7 +226,7 @@ void layout_params(Unet& u) {
         u.slab_bytes = sb.top;
         return;
     }
-    if (c.sr) {
+    case Kind::Srvgg: {
         // body.0: conv in_ch -> F; body.(2k), k = 1..num_conv: conv F -> F; body.(2k+1): PReLU slopes; last: conv F -> out_ch * r * r
         const size_t F = c.ch[0];
         const int last = 2 * (c.layers_per_block + 1), opad = (c.out_ch * c.sr_scale * c.sr_scale + 7) & ~7;
@@ -239,9 +240,10 @@ void layout_params(Unet& u) {
         u.slab_bytes = sb.top;
         return;
     }
-    if (c.vae) {
+    case Kind::VaeDecoder: case Kind::VaeEncoder: {
         // names are the half's own (mve_unet_load_param strips `decoder.` / `encoder.`; (post_)quant_conv is `pq_conv`)
-        const int n = c.n_levels, Cm = c.ch[n - 1], Cin0 = c.vae == 1 ? Cm : c.ch[0], Cout0 = c.vae == 1 ? c.ch[0] : Cm;
+        const bool dec = c.kind == Kind::VaeDecoder;
+        const int n = c.n_levels, Cm = c.ch[n - 1], Cin0 = dec ? Cm : c.ch[0], Cout0 = dec ? c.ch[0] : Cm;
         sb.add("pq_conv.w", 8 * 8, false); need("pq_conv.weight");
         sb.add("pq_conv.b", 8, true); need("pq_conv.bias");
         sb.add("conv_in.w", (size_t)Cin0 * 9 * 8, false); need("conv_in.weight");
@@ -274,10 +276,10 @@ void layout_params(Unet& u) {
         sb.add(a + ".o.w", C * C, false); need(a + ".to_out.0.weight");
         sb.add(a + ".o.b", C, true); need(a + ".to_out.0.bias");
         for (int i = 0; i + 1 < n; ++i) {
-            const size_t Cs = c.vae == 1 ? c.ch[n - 1 - i] : c.ch[i];
-            const std::string sn = (c.vae == 1 ? "up_blocks." + std::to_string(i) + ".upsamplers" : "down_blocks." + std::to_string(i) + ".downsamplers") + ".0.conv";
+            const size_t Cs = dec ? c.ch[n - 1 - i] : c.ch[i];
+            const std::string sn = (dec ? "up_blocks." + std::to_string(i) + ".upsamplers" : "down_blocks." + std::to_string(i) + ".downsamplers") + ".0.conv";
             sb.add(sn + ".w", Cs * 9 * Cs, false); need(sn + ".weight");
-            if (c.vae == 1 && Cs % 64 == 0) sb.add(sn + ".w4", Cs * 16 * Cs, false);      // the upsampler's summed taps (mve_upsample_conv_phases)
+            if (dec && Cs % 64 == 0) sb.add(sn + ".w4", Cs * 16 * Cs, false);      // the upsampler's summed taps (mve_upsample_conv_phases)
             sb.add(sn + ".b", Cs, true); need(sn + ".bias");
         }
         sb.add("norm_out.g", Cout0, true); need("conv_norm_out.weight");
@@ -287,6 +289,9 @@ void layout_params(Unet& u) {
         u.slab_bytes = sb.top;
         return;
     }
+    case Kind::UNet: case Kind::ControlNet: break;
+    }
+    const bool controlnet = c.kind == Kind::ControlNet;
     sb.add("conv_in.w", (size_t)c.ch[0] * 9 * 8, false); need("conv_in.weight");
     sb.add("conv_in.b", c.ch[0], true); need("conv_in.bias");
     sb.add("time.w1", (size_t)T * c.ch[0], false); need("time_embedding.linear_1.weight");
@@ -359,14 +364,14 @@ void layout_params(Unet& u) {
         const std::string d = "down_blocks." + std::to_string(i) + ".downsamplers.0.conv";
         sb.add(d + ".w", C * 9 * C, false); need(d + ".weight");
         sb.add(d + ".b", C, true); need(d + ".bias");
-        if (c.controlnet) continue;
+        if (controlnet) continue;
         const size_t Cu = c.ch[c.n_levels - 1 - i];
         const std::string up = "up_blocks." + std::to_string(i) + ".upsamplers.0.conv";
         sb.add(up + ".w", Cu * 9 * Cu, false); need(up + ".weight");
         if (Cu % 64 == 0) sb.add(up + ".w4", Cu * 16 * Cu, false);      // the summed taps of the four 2 x 2 phase convs (mve_upsample_conv_phases)
         sb.add(up + ".b", Cu, true); need(up + ".bias");
     }
-    if (!c.controlnet) {
+    if (!controlnet) {
         sb.add("norm_out.g", c.ch[0], true); need("conv_norm_out.weight");
         sb.add("norm_out.b", c.ch[0], true); need("conv_norm_out.bias");
         sb.add("conv_out.w", (size_t)8 * 9 * c.ch[0], false); need("conv_out.weight");
@@ -470,13 +475,17 @@ int load_param(Unet& u, const std::string& name, const void* src, int src_dtype,
     int rc = MVE_ERR_ARG;
     const int T = c.temb_dim();
     const int Cm_ = c.ch[c.n_levels - 1];
-    const int vin = c.vae == 1 ? Cm_ : c.ch[0], vout = c.vae == 1 ? c.ch[0] : Cm_;     // widths after conv_in / before conv_out
+    const bool vae = c.is_vae(), dec = c.kind == Kind::VaeDecoder;
+    const int vin = dec ? Cm_ : c.ch[0], vout = dec ? c.ch[0] : Cm_;     // widths after conv_in / before conv_out
     const std::string va = "mid_block.attentions.0";
-    if (c.dpt || c.loftr) {
+    switch (c.kind) {
+    case Kind::Dpt: case Kind::Loftr: {
         Param* p = P(name);
-        MVE_CHECK(p, MVE_ERR_ARG, "load_param: %s is not a slot of this %s model", name.c_str(), c.dpt ? "DPT" : "LoFTR");
+        MVE_CHECK(p, MVE_ERR_ARG, "load_param: %s is not a slot of this %s model", name.c_str(), c.kind == Kind::Dpt ? "DPT" : "LoFTR");
         rc = vec(p, 0, (long long)(p->bytes / (p->f32 ? 4 : 2)), 1);
-    } else if (c.clipv) {
+        break;
+    }
+    case Kind::ClipVision: {
         const long long C = c.ch[0], I = c.clip_inter, PP3 = 3ll * c.cv_patch * c.cv_patch, Kp = (PP3 + 7) / 8 * 8, G = c.cv_image / c.cv_patch;
         const std::string em = "vision_model.embeddings.";
         int which = -1;
@@ -505,7 +514,9 @@ int load_param(Unet& u, const std::string& name, const void* src, int src_dtype,
             mve_set_error("load_param: %s is not a parameter of this CLIP vision model", name.c_str());
             return MVE_ERR_ARG;
         }
-    } else if (c.resampler) {
+        break;
+    }
+    case Kind::Resampler: {
         const long long D = c.ch[0], inner = (long long)c.heads[0] * 64, F = c.rs_inner, E = c.rs_embed, O = c.rs_out, Q = c.rs_queries;
         if (name == "latents") rc = mat(P("latents"), 0, Q, D, D);
         else if (name == "proj_in.weight") rc = mat(P("proj_in.w"), 0, D, E, E);
@@ -525,7 +536,9 @@ int load_param(Unet& u, const std::string& name, const void* src, int src_dtype,
             mve_set_error("load_param: %s is not a parameter of this Resampler", name.c_str());
             return MVE_ERR_ARG;
         }
-    } else if (c.clip) {
+        break;
+    }
+    case Kind::ClipText: {
         const long long C = c.ch[0], I = c.clip_inter;
         const std::string em = "text_model.embeddings.";
         int which = -1;
@@ -548,7 +561,9 @@ int load_param(Unet& u, const std::string& name, const void* src, int src_dtype,
             mve_set_error("load_param: %s is not a parameter of this CLIP text model", name.c_str());
             return MVE_ERR_ARG;
         }
-    } else if (c.lpips) {
+        break;
+    }
+    case Kind::Lpips: {
         int li = -1;
         for (int i = 0; i < 13; ++i) if (name.compare(0, vgg_name(i).size() + 1, vgg_name(i) + ".") == 0) li = i;
         if (li >= 0 && ends_with(name, ".weight")) {
@@ -579,7 +594,9 @@ int load_param(Unet& u, const std::string& name, const void* src, int src_dtype,
             mve_set_error("load_param: %s is not a parameter of LPIPS(net='vgg')", name.c_str());
             return MVE_ERR_ARG;
         }
-    } else if (c.sr) {
+        break;
+    }
+    case Kind::Srvgg: {
         MVE_CHECK(name.compare(0, 5, "body.") == 0, MVE_ERR_ARG, "load_param: %s is not a parameter of SRVGGNetCompact", name.c_str());
         const int idx = atoi(name.c_str() + 5), last = 2 * (c.layers_per_block + 1);
         const long long F = c.ch[0], nout = (long long)c.out_ch * c.sr_scale * c.sr_scale;
@@ -601,30 +618,33 @@ int load_param(Unet& u, const std::string& name, const void* src, int src_dtype,
             mve_set_error("load_param: %s is not a parameter of SRVGGNetCompact", name.c_str());
             return MVE_ERR_ARG;
         }
-    } else if (c.vae && name == "conv_in.weight") {
+        break;
+    }
+    default:      // the VAE halves first, then what they share with the UNet / ControlNet
+    if (vae && name == "conv_in.weight") {
         MVE_HIP(hipMemsetAsync(dstp(P("conv_in.w"), 0), 0, P("conv_in.w")->bytes, s));
         rc = conv(P("conv_in.w"), vin, c.in_ch, vin, 8);
-    } else if (c.vae && name == "conv_in.bias") rc = vec(P("conv_in.b"), 0, vin, 1);
-    else if (c.vae && name == "conv_norm_out.weight") rc = vec(P("norm_out.g"), 0, vout, 1);
-    else if (c.vae && name == "conv_norm_out.bias") rc = vec(P("norm_out.b"), 0, vout, 1);
-    else if (c.vae && name == "conv_out.weight") {
+    } else if (vae && name == "conv_in.bias") rc = vec(P("conv_in.b"), 0, vin, 1);
+    else if (vae && name == "conv_norm_out.weight") rc = vec(P("norm_out.g"), 0, vout, 1);
+    else if (vae && name == "conv_norm_out.bias") rc = vec(P("norm_out.b"), 0, vout, 1);
+    else if (vae && name == "conv_out.weight") {
         MVE_HIP(hipMemsetAsync(dstp(P("conv_out.w"), 0), 0, P("conv_out.w")->bytes, s));
         rc = conv(P("conv_out.w"), c.out_ch, vout, 8, vout);
-    } else if (c.vae && name == "pq_conv.weight") {      // (post_)quant_conv: 1x1 over <= 8 channels, zero-padded to 8 x 8
-        const int nq = c.vae == 1 ? c.in_ch : c.out_ch;
+    } else if (vae && name == "pq_conv.weight") {      // (post_)quant_conv: 1x1 over <= 8 channels, zero-padded to 8 x 8
+        const int nq = dec ? c.in_ch : c.out_ch;
         MVE_HIP(hipMemsetAsync(dstp(P("pq_conv.w"), 0), 0, P("pq_conv.w")->bytes, s));
         rc = mat(P("pq_conv.w"), 0, nq, nq, 8);
-    } else if (c.vae && name == "pq_conv.bias") {
+    } else if (vae && name == "pq_conv.bias") {
         MVE_HIP(hipMemsetAsync(dstp(P("pq_conv.b"), 0), 0, P("pq_conv.b")->bytes, s));
-        rc = vec(P("pq_conv.b"), 0, c.vae == 1 ? c.in_ch : c.out_ch, 1);
-    } else if (c.vae && (name == va + ".to_q.weight" || name == va + ".to_k.weight"))
+        rc = vec(P("pq_conv.b"), 0, dec ? c.in_ch : c.out_ch, 1);
+    } else if (vae && (name == va + ".to_q.weight" || name == va + ".to_k.weight"))
         rc = mat(P(va + ".qk.w"), name[va.size() + 4] == 'q' ? 0 : (size_t)Cm_ * Cm_, Cm_, Cm_, Cm_);
-    else if (c.vae && (name == va + ".to_q.bias" || name == va + ".to_k.bias"))
+    else if (vae && (name == va + ".to_q.bias" || name == va + ".to_k.bias"))
         rc = vec(P(va + ".qk.b"), name[va.size() + 4] == 'q' ? 0 : Cm_, Cm_, 1);
-    else if (c.vae && name == va + ".to_v.weight") rc = mat(P(va + ".v.w"), 0, Cm_, Cm_, Cm_);
-    else if (c.vae && name == va + ".to_v.bias") rc = vec(P(va + ".v.b"), 0, Cm_, 1);
-    else if (c.vae && name == va + ".to_out.0.weight") rc = mat(P(va + ".o.w"), 0, Cm_, Cm_, Cm_);
-    else if (c.vae && name == va + ".to_out.0.bias") rc = vec(P(va + ".o.b"), 0, Cm_, 1);
+    else if (vae && name == va + ".to_v.weight") rc = mat(P(va + ".v.w"), 0, Cm_, Cm_, Cm_);
+    else if (vae && name == va + ".to_v.bias") rc = vec(P(va + ".v.b"), 0, Cm_, 1);
+    else if (vae && name == va + ".to_out.0.weight") rc = mat(P(va + ".o.w"), 0, Cm_, Cm_, Cm_);
+    else if (vae && name == va + ".to_out.0.bias") rc = vec(P(va + ".o.b"), 0, Cm_, 1);
     else if (name == "conv_in.weight") {
         MVE_HIP(hipMemsetAsync(dstp(P("conv_in.w"), 0), 0, P("conv_in.w")->bytes, s));
         rc = conv(P("conv_in.w"), c.ch[0], c.in_ch, c.ch[0], 8);
@@ -745,6 +765,7 @@ int load_param(Unet& u, const std::string& name, const void* src, int src_dtype,
     else {
         mve_set_error("load_param: %s is not a parameter of this UNet configuration", name.c_str());
         return MVE_ERR_ARG;
+    }
     }
     if (rc == MVE_OK) u.loaded[name] = true;
     return rc;

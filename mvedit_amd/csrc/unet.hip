@@ -30,12 +30,16 @@
 
 namespace {
 
-int ensure_plan(Unet& u, int B, int H, int W, int n_img, int has_res, int io_dtype, int res_nhwc, int ctx_len) {
+// what a plan is built for and cached under, next to the handle's own options (AttnOpts, add_type).  The networks without conditioning use the first
+// three and io_dtype; the CLIP text tower and the Resampler put their sequence length in H, LoFTR its phase in n_img.
+struct PlanKey { int B = 0, H = 0, W = 0, n_img = 1, has_res = 0, io_dtype = 0, res_nhwc = 0, ctx_len = 0; };
+
+int ensure_plan(Unet& u, const PlanKey& k) {
     ++u.tick;
     for (auto& pp : u.plans) {
         const Plan& p = *pp;
-        if (p.B == B && p.H == H && p.W == W && p.n_img == n_img && p.has_res == has_res && p.io_dtype == io_dtype &&
-            p.res_nhwc == res_nhwc && p.ctx_len == ctx_len && p.add_type == u.cfg.add_type && p.ao == u.ao) {
+        if (p.B == k.B && p.H == k.H && p.W == k.W && p.n_img == k.n_img && p.has_res == k.has_res && p.io_dtype == k.io_dtype &&
+            p.res_nhwc == k.res_nhwc && p.ctx_len == k.ctx_len && p.add_type == u.cfg.add_type && p.ao == u.ao) {
             pp->last_use = u.tick;
             u.cur = pp.get();
             return MVE_OK;
@@ -44,11 +48,22 @@ int ensure_plan(Unet& u, int B, int H, int W, int n_img, int has_res, int io_dty
     std::unique_ptr<Plan> np(new Plan());
     np->ao = u.ao;
     Builder b(u, *np);
-    b.ctx_rows_per_img = ctx_len;
+    b.ctx_rows_per_img = k.ctx_len;
     u.cur = nullptr;
-    const int rc = u.cfg.loftr ? b.build_loftr(B, H, W, n_img) : u.cfg.dpt ? b.build_dpt(B) : u.cfg.clipv ? b.build_clip_vision(B) : u.cfg.resampler ? b.build_resampler(B, H) : u.cfg.clip ? b.build_clip(B, H) : u.cfg.lpips ? b.build_lpips(B, H, W, io_dtype) : u.cfg.sr ? b.build_sr(B, H, W, io_dtype) : u.cfg.vae ? b.build_vae(B, H, W, io_dtype) : b.build(B, H, W, n_img, has_res, io_dtype, res_nhwc);
+    int rc = MVE_ERR_ARG;
+    switch (u.cfg.kind) {
+        case Kind::UNet: case Kind::ControlNet: rc = b.build(k.B, k.H, k.W, k.n_img, k.has_res, k.io_dtype, k.res_nhwc); break;
+        case Kind::VaeDecoder: case Kind::VaeEncoder: rc = b.build_vae(k.B, k.H, k.W, k.io_dtype); break;
+        case Kind::Srvgg: rc = b.build_sr(k.B, k.H, k.W, k.io_dtype); break;
+        case Kind::Lpips: rc = b.build_lpips(k.B, k.H, k.W, k.io_dtype); break;
+        case Kind::ClipText: rc = b.build_clip(k.B, k.H); break;
+        case Kind::ClipVision: rc = b.build_clip_vision(k.B); break;
+        case Kind::Resampler: rc = b.build_resampler(k.B, k.H); break;
+        case Kind::Dpt: rc = b.build_dpt(k.B); break;
+        case Kind::Loftr: rc = b.build_loftr(k.B, k.H, k.W, k.n_img); break;
+    }
     if (rc != MVE_OK) return rc;
-    np->ctx_len = ctx_len;
+    np->ctx_len = k.ctx_len;
     np->last_use = u.tick;
     np->uid = ++u.plan_counter;
     if (u.plans.size() >= 8) {
@@ -72,6 +87,110 @@ int take_added_cond(const Unet& u, int B, Run& r, const char* who) {
     return MVE_OK;
 }
 
+// the handle as an engine of one of the wanted kinds
+int as_engine(void* handle, const char* who, std::initializer_list<Kind> wanted, Unet*& u) {
+    MVE_CHECK(handle, MVE_ERR_ARG, "%s: null handle", who);
+    u = (Unet*)handle;
+    for (Kind k : wanted)
+        if (u->cfg.kind == k) return MVE_OK;
+    mve_set_error("%s: handle is %s, not %s", who, kind_name(u->cfg.kind), kind_name(*wanted.begin()));
+    return MVE_ERR_ARG;
+}
+
+// the three outputs of every *_plan call, from the current plan
+void report_plan(const Plan& pl, size_t* workspace_bytes, int* n_ops, double* flops) {
+    if (workspace_bytes) *workspace_bytes = pl.ws_bytes;
+    if (n_ops) *n_ops = (int)pl.ops.size();
+    if (flops) for (int i = 0; i < OC_COUNT; ++i) flops[i] = pl.flops[i];
+}
+
+int plan_and_report(Unet& u, const PlanKey& key, size_t* workspace_bytes, int* n_ops, double* flops) {
+    const int rc = ensure_plan(u, key);
+    if (rc) return rc;
+    report_plan(*u.cur, workspace_bytes, n_ops, flops);
+    return MVE_OK;
+}
+
+// The front of every forward call, in this order: null handle, kind, every parameter loaded, the call's own argument checks, plan, workspace size.
+// `args(u, key)` checks the arguments that are the call's own and fills the plan key (it may need the handle's configuration for either).
+template <class Args>
+int begin_forward(void* handle, const char* who, std::initializer_list<Kind> wanted, Args&& args, const void* d_workspace, size_t workspace_bytes, Unet*& u,
+                  const Plan*& pl) {
+    int rc = as_engine(handle, who, wanted, u);
+    if (rc) return rc;
+    char first[256];
+    const int miss = mve_unet_missing_params(handle, first, sizeof(first));
+    MVE_CHECK(miss == 0, MVE_ERR_STATE, "%s: %d parameters not loaded (first: %s)", who, miss, first);
+    PlanKey key;
+    rc = args(*u, key);
+    if (rc) return rc;
+    rc = ensure_plan(*u, key);
+    if (rc) return rc;
+    pl = u->cur;
+    MVE_CHECK(d_workspace && workspace_bytes >= pl->ws_bytes, MVE_ERR_NOMEM, "%s: workspace %zu < required %zu", who, workspace_bytes, pl->ws_bytes);
+    return MVE_OK;
+}
+
+// the events of a timed run: destroyed on every way out of it
+struct OpEvents {
+    std::vector<hipEvent_t> ev;
+    ~OpEvents() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    int create(size_t n) {
+        ev.assign(n, nullptr);
+        for (auto& e : ev) MVE_HIP(hipEventCreate(&e));
+        return MVE_OK;
+    }
+};
+
+// ops [lo, hi) of a plan on one stream; with op_ms (a host array indexed by the absolute op index) each op is timed and the stream is synchronised
+int run_plan_ops(const Plan& pl, const Run& r, size_t lo, size_t hi, float* op_ms) {
+    OpEvents t;
+    if (op_ms) {
+        const int rc = t.create(hi - lo + 1);
+        if (rc) return rc;
+        MVE_HIP(hipEventRecord(t.ev[0], r.stream));
+    }
+    for (size_t i = lo; i < hi; ++i) {
+        const int rc = pl.ops[i].fn(r);
+        if (rc) return rc;
+        if (op_ms) MVE_HIP(hipEventRecord(t.ev[i - lo + 1], r.stream));
+    }
+    if (op_ms) {
+        MVE_HIP(hipStreamSynchronize(r.stream));
+        for (size_t i = lo; i < hi; ++i) MVE_HIP(hipEventElapsedTime(&op_ms[i], t.ev[i - lo], t.ev[i - lo + 1]));
+    }
+    return MVE_OK;
+}
+
+Run new_run(const Unet& u, void* d_workspace, void* stream) {
+    Run r;
+    r.ws = (unsigned char*)d_workspace; r.wt = u.slab; r.stream = (hipStream_t)stream;
+    return r;
+}
+
+// mve_unet_create / mve_controlnet_create: the topology arguments the two share, checked and filled into a new handle
+int create_denoiser(void** handle, const char* who, Kind kind, int dtype, int in_channels, int out_channels, int n_levels, const int* block_out_channels,
+                    int layers_per_block, const int* down_attn, const int* num_heads, const int* transformer_layers, int cross_attention_dim,
+                    int norm_num_groups, float norm_eps, int use_linear_projection) {
+    MVE_CHECK(handle, MVE_ERR_ARG, "%s: null handle", who);
+    MVE_CHECK(dtype == MVE_F16 || dtype == MVE_BF16, MVE_ERR_ARG, "%s: dtype must be f16 or bf16", who);
+    MVE_CHECK(n_levels >= 1 && n_levels <= MAX_LEVELS && layers_per_block >= 1, MVE_ERR_ARG, "%s: bad topology", who);
+    MVE_CHECK(in_channels >= 1 && in_channels <= 8 && out_channels >= 1 && out_channels <= 8, MVE_ERR_ARG, "%s: in/out channels must be <= 8", who);
+    MVE_CHECK(cross_attention_dim % 8 == 0, MVE_ERR_ARG, "%s: cross_attention_dim must be a multiple of 8", who);
+    std::unique_ptr<Unet> u(new Unet());
+    Config& c = u->cfg;
+    c.kind = kind;
+    c.dtype = dtype; c.in_ch = in_channels; c.out_ch = out_channels; c.n_levels = n_levels; c.layers_per_block = layers_per_block;
+    c.ctx_dim = cross_attention_dim; c.groups = norm_num_groups; c.eps = norm_eps; c.linear_proj = use_linear_projection;
+    for (int i = 0; i < n_levels; ++i) {
+        c.ch[i] = block_out_channels[i]; c.attn[i] = down_attn[i]; c.heads[i] = num_heads[i]; c.tlayers[i] = transformer_layers[i];
+        MVE_CHECK(c.ch[i] % 32 == 0 && c.ch[i] % c.groups == 0 && (!c.attn[i] || c.ch[i] % c.heads[i] == 0), MVE_ERR_ARG,
+                  "%s: channel count %d incompatible with groups/heads", who, block_out_channels[i]);
+    }
+    *handle = u.release();
+    return MVE_OK;
+}
+
 }  // namespace
 
 // =====================================================================================================
@@ -82,33 +201,16 @@ extern "C" {
 int mve_unet_create(void** handle, int dtype, int in_channels, int out_channels, int n_levels, const int* block_out_channels,
                     int layers_per_block, const int* down_attn, const int* num_heads, const int* transformer_layers,
                     int cross_attention_dim, int norm_num_groups, float norm_eps, int use_linear_projection) {
-    MVE_CHECK(handle, MVE_ERR_ARG, "unet_create: null handle");
-    MVE_CHECK(dtype == MVE_F16 || dtype == MVE_BF16, MVE_ERR_ARG, "unet_create: dtype must be f16 or bf16");
-    MVE_CHECK(n_levels >= 1 && n_levels <= MAX_LEVELS && layers_per_block >= 1, MVE_ERR_ARG, "unet_create: bad topology");
-    MVE_CHECK(in_channels >= 1 && in_channels <= 8 && out_channels >= 1 && out_channels <= 8, MVE_ERR_ARG,
-              "unet_create: in/out channels must be <= 8");
-    MVE_CHECK(cross_attention_dim % 8 == 0, MVE_ERR_ARG, "unet_create: cross_attention_dim must be a multiple of 8");
-    Unet* u = new Unet();
-    Config& c = u->cfg;
-    c.dtype = dtype; c.in_ch = in_channels; c.out_ch = out_channels; c.n_levels = n_levels; c.layers_per_block = layers_per_block;
-    c.ctx_dim = cross_attention_dim; c.groups = norm_num_groups; c.eps = norm_eps; c.linear_proj = use_linear_projection;
-    for (int i = 0; i < n_levels; ++i) {
-        c.ch[i] = block_out_channels[i]; c.attn[i] = down_attn[i]; c.heads[i] = num_heads[i]; c.tlayers[i] = transformer_layers[i];
-        if (c.ch[i] % 32 != 0 || c.ch[i] % c.groups != 0 || (c.attn[i] && c.ch[i] % c.heads[i] != 0)) {
-            delete u;
-            mve_set_error("unet_create: channel count %d incompatible with groups/heads", block_out_channels[i]);
-            return MVE_ERR_ARG;
-        }
-    }
+    const int rc = create_denoiser(handle, "unet_create", Kind::UNet, dtype, in_channels, out_channels, n_levels, block_out_channels, layers_per_block, down_attn,
+                                   num_heads, transformer_layers, cross_attention_dim, norm_num_groups, norm_eps, use_linear_projection);
+    if (rc) return rc;
+    Unet* u = (Unet*)*handle;
     layout_params(*u);   // host-side only; device storage is allocated by the first mve_unet_load_param
     // Round 5: the UNet's residual stream is an unrounded (hi, lo) pair BY DEFAULT -- the mode whose end-to-end error against fp32 arithmetic is
     // inside north_star's 1e-3 (8.7e-4 at the benchmark shape; the reference's rounding points give 1.2e-3).  MVE_RESIDUAL_PAIR=0 or
     // mve_unet_set_residual_mode(handle, 0) restore the 16-bit stream.  ControlNet / VAE handles keep the 16-bit stream unless asked.
-    {
-        const char* e = getenv("MVE_RESIDUAL_PAIR");
-        u->ao.residual_pair = e ? (atoi(e) != 0) : 1;
-    }
-    *handle = u;
+    const char* e = getenv("MVE_RESIDUAL_PAIR");
+    u->ao.residual_pair = e ? (atoi(e) != 0) : 1;
     return MVE_OK;
 }
 
@@ -117,73 +219,34 @@ int mve_controlnet_create(void** handle, int dtype, int in_channels, int conditi
                           int cross_attention_dim, int norm_num_groups, float norm_eps, int use_linear_projection) {
     MVE_CHECK(conditioning_channels >= 1 && conditioning_channels <= 8, MVE_ERR_ARG, "controlnet_create: conditioning channels must be <= 8");
     // same topology arguments as the UNet; build the parameter table in ControlNet mode
-    MVE_CHECK(handle, MVE_ERR_ARG, "controlnet_create: null handle");
-    MVE_CHECK(dtype == MVE_F16 || dtype == MVE_BF16, MVE_ERR_ARG, "controlnet_create: dtype must be f16 or bf16");
-    MVE_CHECK(n_levels >= 1 && n_levels <= MAX_LEVELS && layers_per_block >= 1, MVE_ERR_ARG, "controlnet_create: bad topology");
-    MVE_CHECK(in_channels >= 1 && in_channels <= 8, MVE_ERR_ARG, "controlnet_create: in channels must be <= 8");
-    MVE_CHECK(cross_attention_dim % 8 == 0, MVE_ERR_ARG, "controlnet_create: cross_attention_dim must be a multiple of 8");
-    Unet* u = new Unet();
-    Config& c = u->cfg;
-    c.controlnet = 1; c.cond_ch = conditioning_channels;
-    c.dtype = dtype; c.in_ch = in_channels; c.out_ch = in_channels; c.n_levels = n_levels; c.layers_per_block = layers_per_block;
-    c.ctx_dim = cross_attention_dim; c.groups = norm_num_groups; c.eps = norm_eps; c.linear_proj = use_linear_projection;
-    for (int i = 0; i < n_levels; ++i) {
-        c.ch[i] = block_out_channels[i]; c.attn[i] = down_attn[i]; c.heads[i] = num_heads[i]; c.tlayers[i] = transformer_layers[i];
-        if (c.ch[i] % 32 != 0 || c.ch[i] % c.groups != 0 || (c.attn[i] && c.ch[i] % c.heads[i] != 0)) {
-            delete u;
-            mve_set_error("controlnet_create: channel count %d incompatible with groups/heads", block_out_channels[i]);
-            return MVE_ERR_ARG;
-        }
-    }
+    const int rc = create_denoiser(handle, "controlnet_create", Kind::ControlNet, dtype, in_channels, in_channels, n_levels, block_out_channels, layers_per_block,
+                                   down_attn, num_heads, transformer_layers, cross_attention_dim, norm_num_groups, norm_eps, use_linear_projection);
+    if (rc) return rc;
+    Unet* u = (Unet*)*handle;
+    u->cfg.cond_ch = conditioning_channels;
     layout_params(*u);
-    *handle = u;
     return MVE_OK;
 }
 
 int mve_controlnet_forward(void* handle, const void* d_sample, int io_dtype, const float* d_timesteps, const void* d_ctx, const void* d_cond,
                            int B, int H, int W, int ctx_len, float conditioning_scale, int accumulate, void* const* d_outputs,
                            void* d_workspace, size_t workspace_bytes, float* op_ms, void* stream) {
-    MVE_CHECK(handle, MVE_ERR_ARG, "controlnet_forward: null handle");
-    Unet* u = (Unet*)handle;
-    MVE_CHECK(u->cfg.controlnet, MVE_ERR_ARG, "controlnet_forward: handle is a UNet, not a ControlNet");
-    {
-        char first[256];
-        const int miss = mve_unet_missing_params(handle, first, sizeof(first));
-        MVE_CHECK(miss == 0, MVE_ERR_STATE, "controlnet_forward: %d parameters not loaded (first: %s)", miss, first);
-    }
-    MVE_CHECK(d_sample && d_timesteps && d_ctx && d_cond && d_outputs, MVE_ERR_ARG, "controlnet_forward: null pointer");
-    int rc = ensure_plan(*u, B, H, W, 1, 0, io_dtype, 0, ctx_len);
+    Unet* u;
+    const Plan* pl;
+    int rc = begin_forward(handle, "controlnet_forward", {Kind::ControlNet}, [&](const Unet&, PlanKey& k) -> int {
+        MVE_CHECK(d_sample && d_timesteps && d_ctx && d_cond && d_outputs, MVE_ERR_ARG, "controlnet_forward: null pointer");
+        k.B = B; k.H = H; k.W = W; k.io_dtype = io_dtype; k.ctx_len = ctx_len;
+        return MVE_OK;
+    }, d_workspace, workspace_bytes, u, pl);
     if (rc) return rc;
-    const Plan& pl = *u->cur;
-    MVE_CHECK(d_workspace && workspace_bytes >= pl.ws_bytes, MVE_ERR_NOMEM, "controlnet_forward: workspace %zu < required %zu", workspace_bytes,
-              pl.ws_bytes);
     const int n_out = u->cfg.n_levels * (u->cfg.layers_per_block + 1) + 1;
     for (int i = 0; i < n_out; ++i) MVE_CHECK(d_outputs[i], MVE_ERR_ARG, "controlnet_forward: null output %d", i);
-    Run r;
-    r.ws = (unsigned char*)d_workspace; r.wt = u->slab;
-    r.sample = d_sample; r.timesteps = d_timesteps; r.ctx = d_ctx; r.out = nullptr;
-    r.down_res = nullptr; r.mid_res = nullptr; r.ref_store = nullptr;
+    Run r = new_run(*u, d_workspace, stream);
+    r.sample = d_sample; r.timesteps = d_timesteps; r.ctx = d_ctx;
     r.cn_cond = d_cond; r.cn_out = d_outputs; r.cn_scale = conditioning_scale; r.cn_accum = accumulate ? 1 : 0;
-    r.stream = (hipStream_t)stream;
     rc = take_added_cond(*u, B, r, "controlnet_forward");
     if (rc) return rc;
-    std::vector<hipEvent_t> ev;
-    if (op_ms) {
-        ev.resize(pl.ops.size() + 1);
-        for (auto& e : ev) MVE_HIP(hipEventCreate(&e));
-        MVE_HIP(hipEventRecord(ev[0], r.stream));
-    }
-    for (size_t i = 0; i < pl.ops.size(); ++i) {
-        rc = pl.ops[i].fn(r);
-        if (rc) return rc;
-        if (op_ms) MVE_HIP(hipEventRecord(ev[i + 1], r.stream));
-    }
-    if (op_ms) {
-        MVE_HIP(hipStreamSynchronize(r.stream));
-        for (size_t i = 0; i < pl.ops.size(); ++i) MVE_HIP(hipEventElapsedTime(&op_ms[i], ev[i], ev[i + 1]));
-        for (auto& e : ev) (void)hipEventDestroy(e);
-    }
-    return MVE_OK;
+    return run_plan_ops(*pl, r, 0, pl->ops.size(), op_ms);
 }
 
 int mve_vae_create(void** handle, int dtype, int half, int in_channels, int out_channels, int n_levels, const int* block_out_channels,
@@ -196,7 +259,7 @@ int mve_vae_create(void** handle, int dtype, int half, int in_channels, int out_
               "vae_create: in/out channels must be <= 8 (encoder: out_channels = 2 * latent_channels)");
     Unet* u = new Unet();
     Config& c = u->cfg;
-    c.vae = half;
+    c.kind = half == 1 ? Kind::VaeDecoder : Kind::VaeEncoder;
     c.dtype = dtype; c.in_ch = in_channels; c.out_ch = out_channels; c.n_levels = n_levels; c.layers_per_block = layers_per_block;
     c.ctx_dim = 8; c.groups = norm_num_groups; c.eps = norm_eps; c.linear_proj = 0;
     for (int i = 0; i < n_levels; ++i) {
@@ -213,64 +276,37 @@ int mve_vae_create(void** handle, int dtype, int half, int in_channels, int out_
 }
 
 // image networks (VAE halves, SRVGGNetCompact): one NCHW tensor in, one out, no conditioning
-static int imgnet_plan(void* handle, bool want_vae, int B, int H, int W, int io_dtype, size_t* workspace_bytes, int* n_ops, double* flops) {
+static int imgnet_plan(void* handle, std::initializer_list<Kind> wanted, int B, int H, int W, int io_dtype, size_t* workspace_bytes, int* n_ops, double* flops) {
     MVE_CHECK(handle && B > 0 && H > 0 && W > 0, MVE_ERR_ARG, "plan: bad arguments");
-    Unet* u = (Unet*)handle;
-    MVE_CHECK(want_vae ? u->cfg.vae != 0 : u->cfg.sr != 0, MVE_ERR_ARG, "plan: handle is not %s", want_vae ? "a VAE half" : "an SRVGGNetCompact");
-    int rc = ensure_plan(*u, B, H, W, 1, 0, io_dtype, 0, 0);
+    Unet* u;
+    const int rc = as_engine(handle, "plan", wanted, u);
     if (rc) return rc;
-    if (workspace_bytes) *workspace_bytes = u->cur->ws_bytes;
-    if (n_ops) *n_ops = (int)u->cur->ops.size();
-    if (flops) for (int i = 0; i < OC_COUNT; ++i) flops[i] = u->cur->flops[i];
-    return MVE_OK;
+    PlanKey k;
+    k.B = B; k.H = H; k.W = W; k.io_dtype = io_dtype;
+    return plan_and_report(*u, k, workspace_bytes, n_ops, flops);
 }
 
-static int imgnet_forward(void* handle, bool want_vae, const void* d_in, int io_dtype, int B, int H, int W, void* d_out, void* d_workspace,
+static int imgnet_forward(void* handle, std::initializer_list<Kind> wanted, const void* d_in, int io_dtype, int B, int H, int W, void* d_out, void* d_workspace,
                           size_t workspace_bytes, float* op_ms, void* stream) {
-    MVE_CHECK(handle, MVE_ERR_ARG, "forward: null handle");
-    Unet* u = (Unet*)handle;
-    MVE_CHECK(want_vae ? u->cfg.vae != 0 : u->cfg.sr != 0, MVE_ERR_ARG, "forward: handle is not %s", want_vae ? "a VAE half" : "an SRVGGNetCompact");
-    {
-        char first[256];
-        const int miss = mve_unet_missing_params(handle, first, sizeof(first));
-        MVE_CHECK(miss == 0, MVE_ERR_STATE, "forward: %d parameters not loaded (first: %s)", miss, first);
-    }
-    MVE_CHECK(d_in && d_out, MVE_ERR_ARG, "forward: null pointer");
-    int rc = ensure_plan(*u, B, H, W, 1, 0, io_dtype, 0, 0);
+    Unet* u;
+    const Plan* pl;
+    const int rc = begin_forward(handle, "forward", wanted, [&](const Unet&, PlanKey& k) -> int {
+        MVE_CHECK(d_in && d_out, MVE_ERR_ARG, "forward: null pointer");
+        k.B = B; k.H = H; k.W = W; k.io_dtype = io_dtype;
+        return MVE_OK;
+    }, d_workspace, workspace_bytes, u, pl);
     if (rc) return rc;
-    const Plan& pl = *u->cur;
-    MVE_CHECK(d_workspace && workspace_bytes >= pl.ws_bytes, MVE_ERR_NOMEM, "forward: workspace %zu < required %zu", workspace_bytes,
-              pl.ws_bytes);
-    Run r;
-    r.ws = (unsigned char*)d_workspace; r.wt = u->slab;
-    r.sample = d_in; r.timesteps = nullptr; r.ctx = nullptr; r.out = d_out;
-    r.down_res = nullptr; r.mid_res = nullptr; r.ref_store = nullptr;
-    r.stream = (hipStream_t)stream;
-    std::vector<hipEvent_t> ev;
-    if (op_ms) {
-        ev.resize(pl.ops.size() + 1);
-        for (auto& e : ev) MVE_HIP(hipEventCreate(&e));
-        MVE_HIP(hipEventRecord(ev[0], r.stream));
-    }
-    for (size_t i = 0; i < pl.ops.size(); ++i) {
-        rc = pl.ops[i].fn(r);
-        if (rc) return rc;
-        if (op_ms) MVE_HIP(hipEventRecord(ev[i + 1], r.stream));
-    }
-    if (op_ms) {
-        MVE_HIP(hipStreamSynchronize(r.stream));
-        for (size_t i = 0; i < pl.ops.size(); ++i) MVE_HIP(hipEventElapsedTime(&op_ms[i], ev[i], ev[i + 1]));
-        for (auto& e : ev) (void)hipEventDestroy(e);
-    }
-    return MVE_OK;
+    Run r = new_run(*u, d_workspace, stream);
+    r.sample = d_in; r.out = d_out;
+    return run_plan_ops(*pl, r, 0, pl->ops.size(), op_ms);
 }
 
 int mve_vae_plan(void* handle, int B, int H, int W, int io_dtype, size_t* workspace_bytes, int* n_ops, double* flops) {
-    return imgnet_plan(handle, true, B, H, W, io_dtype, workspace_bytes, n_ops, flops);
+    return imgnet_plan(handle, {Kind::VaeDecoder, Kind::VaeEncoder}, B, H, W, io_dtype, workspace_bytes, n_ops, flops);
 }
 int mve_vae_forward(void* handle, const void* d_in, int io_dtype, int B, int H, int W, void* d_out, void* d_workspace,
                     size_t workspace_bytes, float* op_ms, void* stream) {
-    return imgnet_forward(handle, true, d_in, io_dtype, B, H, W, d_out, d_workspace, workspace_bytes, op_ms, stream);
+    return imgnet_forward(handle, {Kind::VaeDecoder, Kind::VaeEncoder}, d_in, io_dtype, B, H, W, d_out, d_workspace, workspace_bytes, op_ms, stream);
 }
 
 int mve_srvgg_create(void** handle, int dtype, int num_in_ch, int num_out_ch, int num_feat, int num_conv, int upscale) {
@@ -281,7 +317,7 @@ int mve_srvgg_create(void** handle, int dtype, int num_in_ch, int num_out_ch, in
     MVE_CHECK(num_feat >= 8 && num_feat % 8 == 0 && num_conv >= 0 && upscale >= 1 && upscale <= 8, MVE_ERR_ARG, "srvgg_create: bad topology");
     Unet* u = new Unet();
     Config& c = u->cfg;
-    c.sr = 1; c.sr_scale = upscale;
+    c.kind = Kind::Srvgg; c.sr_scale = upscale;
     c.dtype = dtype; c.in_ch = num_in_ch; c.out_ch = num_out_ch; c.n_levels = 1; c.layers_per_block = num_conv;
     c.ctx_dim = 8; c.groups = 1; c.eps = 0.f; c.linear_proj = 0;
     c.ch[0] = num_feat; c.attn[0] = 0; c.heads[0] = 1; c.tlayers[0] = 0;
@@ -290,11 +326,11 @@ int mve_srvgg_create(void** handle, int dtype, int num_in_ch, int num_out_ch, in
     return MVE_OK;
 }
 int mve_srvgg_plan(void* handle, int B, int H, int W, int io_dtype, size_t* workspace_bytes, int* n_ops, double* flops) {
-    return imgnet_plan(handle, false, B, H, W, io_dtype, workspace_bytes, n_ops, flops);
+    return imgnet_plan(handle, {Kind::Srvgg}, B, H, W, io_dtype, workspace_bytes, n_ops, flops);
 }
 int mve_srvgg_forward(void* handle, const void* d_in, int io_dtype, int B, int H, int W, void* d_out, void* d_workspace,
                       size_t workspace_bytes, float* op_ms, void* stream) {
-    return imgnet_forward(handle, false, d_in, io_dtype, B, H, W, d_out, d_workspace, workspace_bytes, op_ms, stream);
+    return imgnet_forward(handle, {Kind::Srvgg}, d_in, io_dtype, B, H, W, d_out, d_workspace, workspace_bytes, op_ms, stream);
 }
 
 int mve_clip_text_create(void** handle, int dtype, int vocab_size, int max_position_embeddings, int hidden_size, int num_layers, int num_heads,
@@ -312,7 +348,7 @@ int mve_clip_text_create(void** handle, int dtype, int vocab_size, int max_posit
     MVE_CHECK(layer_norm_eps > 0.f, MVE_ERR_ARG, "clip_text_create: layer_norm_eps must be positive");
     Unet* u = new Unet();
     Config& c = u->cfg;
-    c.clip = 1; c.clip_vocab = vocab_size; c.clip_max_pos = max_position_embeddings; c.clip_inter = intermediate_size; c.clip_act = act;
+    c.kind = Kind::ClipText; c.clip_vocab = vocab_size; c.clip_max_pos = max_position_embeddings; c.clip_inter = intermediate_size; c.clip_act = act;
     c.clip_proj = projection_dim;
     c.dtype = dtype; c.in_ch = 1; c.out_ch = 1; c.n_levels = 1; c.layers_per_block = num_layers;
     c.ctx_dim = 8; c.groups = 1; c.eps = layer_norm_eps; c.linear_proj = 0;
@@ -322,89 +358,50 @@ int mve_clip_text_create(void** handle, int dtype, int vocab_size, int max_posit
     return MVE_OK;
 }
 
+// the CLIP towers' output table (Run::cn_out): last hidden state, pooled output, projected embeddings, then the optional hidden states
+static int clip_outputs(const char* who, const Unet& u, void* d_last, void* d_pooled, void* d_embeds, void* const* d_hidden_states, std::vector<void*>& outs) {
+    const int n_hidden = u.cfg.layers_per_block + 1;
+    outs.assign(CLIP_OUT_HIDDEN0 + n_hidden, nullptr);
+    outs[CLIP_OUT_LAST] = d_last; outs[CLIP_OUT_POOLED] = d_pooled; outs[CLIP_OUT_EMBEDS] = d_embeds;
+    if (d_hidden_states)
+        for (int i = 0; i < n_hidden; ++i) {
+            MVE_CHECK(d_hidden_states[i], MVE_ERR_ARG, "%s: null d_hidden_states[%d]", who, i);
+            outs[CLIP_OUT_HIDDEN0 + i] = d_hidden_states[i];
+        }
+    return MVE_OK;
+}
+
 int mve_clip_text_plan(void* handle, int B, int L, size_t* workspace_bytes, int* n_ops, double* flops) {
     MVE_CHECK(handle && B > 0 && L > 0, MVE_ERR_ARG, "clip_text_plan: bad arguments");
-    Unet* u = (Unet*)handle;
-    MVE_CHECK(u->cfg.clip, MVE_ERR_ARG, "clip_text_plan: handle is not a CLIP text tower");
-    int rc = ensure_plan(*u, B, L, 1, 1, 0, u->cfg.dtype, 0, 0);
+    Unet* u;
+    const int rc = as_engine(handle, "clip_text_plan", {Kind::ClipText}, u);
     if (rc) return rc;
-    if (workspace_bytes) *workspace_bytes = u->cur->ws_bytes;
-    if (n_ops) *n_ops = (int)u->cur->ops.size();
-    if (flops) for (int i = 0; i < OC_COUNT; ++i) flops[i] = u->cur->flops[i];
-    return MVE_OK;
+    PlanKey k;
+    k.B = B; k.H = L; k.W = 1; k.io_dtype = u->cfg.dtype;
+    return plan_and_report(*u, k, workspace_bytes, n_ops, flops);
 }
 
 int mve_clip_text_forward(void* handle, const int32_t* d_ids, int B, int L, int eos_token_id, void* d_last_hidden_state, void* d_pooler_output,
                           void* d_text_embeds, void* const* d_hidden_states, void* d_workspace, size_t workspace_bytes, float* op_ms, void* stream) {
-    MVE_CHECK(handle, MVE_ERR_ARG, "clip_text_forward: null handle");
-    Unet* u = (Unet*)handle;
-    MVE_CHECK(u->cfg.clip, MVE_ERR_ARG, "clip_text_forward: handle is not a CLIP text tower");
-    {
-        char first[256];
-        const int miss = mve_unet_missing_params(handle, first, sizeof(first));
-        MVE_CHECK(miss == 0, MVE_ERR_STATE, "clip_text_forward: %d parameters not loaded (first: %s)", miss, first);
-    }
-    MVE_CHECK(d_ids && d_last_hidden_state && d_pooler_output, MVE_ERR_ARG, "clip_text_forward: null pointer (d_ids / d_last_hidden_state / d_pooler_output)");
-    MVE_CHECK(u->cfg.clip_proj ? d_text_embeds != nullptr : d_text_embeds == nullptr, MVE_ERR_ARG,
-              "clip_text_forward: d_text_embeds must be given exactly when the handle has a text_projection (projection_dim %d)", u->cfg.clip_proj);
-    MVE_CHECK(B > 0 && L > 0, MVE_ERR_ARG, "clip_text_forward: bad B %d / L %d", B, L);
-    int rc = ensure_plan(*u, B, L, 1, 1, 0, u->cfg.dtype, 0, 0);
+    Unet* u;
+    const Plan* pl;
+    int rc = begin_forward(handle, "clip_text_forward", {Kind::ClipText}, [&](const Unet& e, PlanKey& k) -> int {
+        MVE_CHECK(d_ids && d_last_hidden_state && d_pooler_output, MVE_ERR_ARG, "clip_text_forward: null pointer (d_ids / d_last_hidden_state / d_pooler_output)");
+        MVE_CHECK(e.cfg.clip_proj ? d_text_embeds != nullptr : d_text_embeds == nullptr, MVE_ERR_ARG,
+                  "clip_text_forward: d_text_embeds must be given exactly when the handle has a text_projection (projection_dim %d)", e.cfg.clip_proj);
+        MVE_CHECK(B > 0 && L > 0, MVE_ERR_ARG, "clip_text_forward: bad B %d / L %d", B, L);
+        k.B = B; k.H = L; k.W = 1; k.io_dtype = e.cfg.dtype;
+        return MVE_OK;
+    }, d_workspace, workspace_bytes, u, pl);
     if (rc) return rc;
-    const Plan& pl = *u->cur;
-    MVE_CHECK(d_workspace && workspace_bytes >= pl.ws_bytes, MVE_ERR_NOMEM, "clip_text_forward: workspace %zu < required %zu", workspace_bytes, pl.ws_bytes);
-    const int n_hidden = u->cfg.layers_per_block + 1;
-    std::vector<void*> outs(CLIP_OUT_HIDDEN0 + n_hidden, nullptr);
-    outs[CLIP_OUT_LAST] = d_last_hidden_state; outs[CLIP_OUT_POOLED] = d_pooler_output; outs[CLIP_OUT_EMBEDS] = d_text_embeds;
-    if (d_hidden_states)
-        for (int i = 0; i < n_hidden; ++i) {
-            MVE_CHECK(d_hidden_states[i], MVE_ERR_ARG, "clip_text_forward: null d_hidden_states[%d]", i);
-            outs[CLIP_OUT_HIDDEN0 + i] = d_hidden_states[i];
-        }
-    Run r;
-    r.ws = (unsigned char*)d_workspace; r.wt = u->slab;
-    r.sample = d_ids; r.timesteps = nullptr; r.ctx = nullptr; r.out = nullptr;
-    r.down_res = nullptr; r.mid_res = nullptr; r.ref_store = nullptr;
+    std::vector<void*> outs;
+    rc = clip_outputs("clip_text_forward", *u, d_last_hidden_state, d_pooler_output, d_text_embeds, d_hidden_states, outs);
+    if (rc) return rc;
+    Run r = new_run(*u, d_workspace, stream);
+    r.sample = d_ids;
     r.cn_out = outs.data();
     r.clip_eos = eos_token_id;
-    r.stream = (hipStream_t)stream;
-    std::vector<hipEvent_t> ev;
-    if (op_ms) {
-        ev.resize(pl.ops.size() + 1);
-        for (auto& e : ev) MVE_HIP(hipEventCreate(&e));
-        MVE_HIP(hipEventRecord(ev[0], r.stream));
-    }
-    for (size_t i = 0; i < pl.ops.size(); ++i) {
-        rc = pl.ops[i].fn(r);
-        if (rc) return rc;
-        if (op_ms) MVE_HIP(hipEventRecord(ev[i + 1], r.stream));
-    }
-    if (op_ms) {
-        MVE_HIP(hipStreamSynchronize(r.stream));
-        for (size_t i = 0; i < pl.ops.size(); ++i) MVE_HIP(hipEventElapsedTime(&op_ms[i], ev[i], ev[i + 1]));
-        for (auto& e : ev) (void)hipEventDestroy(e);
-    }
-    return MVE_OK;
-}
-
-// the op list of the current plan on one stream, with optional per-op timing (CLIP vision tower, Resampler)
-static int run_plan_ops(const Plan& pl, const Run& r, float* op_ms) {
-    std::vector<hipEvent_t> ev;
-    if (op_ms) {
-        ev.resize(pl.ops.size() + 1);
-        for (auto& e : ev) MVE_HIP(hipEventCreate(&e));
-        MVE_HIP(hipEventRecord(ev[0], r.stream));
-    }
-    for (size_t i = 0; i < pl.ops.size(); ++i) {
-        const int rc = pl.ops[i].fn(r);
-        if (rc) return rc;
-        if (op_ms) MVE_HIP(hipEventRecord(ev[i + 1], r.stream));
-    }
-    if (op_ms) {
-        MVE_HIP(hipStreamSynchronize(r.stream));
-        for (size_t i = 0; i < pl.ops.size(); ++i) MVE_HIP(hipEventElapsedTime(&op_ms[i], ev[i], ev[i + 1]));
-        for (auto& e : ev) (void)hipEventDestroy(e);
-    }
-    return MVE_OK;
+    return run_plan_ops(*pl, r, 0, pl->ops.size(), op_ms);
 }
 
 int mve_clip_vision_create(void** handle, int dtype, int image_size, int patch_size, int hidden_size, int num_layers, int num_heads, int intermediate_size,
@@ -424,7 +421,7 @@ int mve_clip_vision_create(void** handle, int dtype, int image_size, int patch_s
     MVE_CHECK(layer_norm_eps > 0.f, MVE_ERR_ARG, "clip_vision_create: layer_norm_eps must be positive");
     Unet* u = new Unet();
     Config& c = u->cfg;
-    c.clipv = 1; c.cv_image = image_size; c.cv_patch = patch_size; c.clip_inter = intermediate_size; c.clip_act = act; c.clip_proj = projection_dim;
+    c.kind = Kind::ClipVision; c.cv_image = image_size; c.cv_patch = patch_size; c.clip_inter = intermediate_size; c.clip_act = act; c.clip_proj = projection_dim;
     c.dtype = dtype; c.in_ch = 3; c.out_ch = 1; c.n_levels = 1; c.layers_per_block = num_layers;
     c.ctx_dim = 8; c.groups = 1; c.eps = layer_norm_eps; c.linear_proj = 0;
     c.ch[0] = hidden_size; c.attn[0] = 0; c.heads[0] = num_heads; c.tlayers[0] = 0;
@@ -435,50 +432,35 @@ int mve_clip_vision_create(void** handle, int dtype, int image_size, int patch_s
 
 int mve_clip_vision_plan(void* handle, int B, size_t* workspace_bytes, int* n_ops, double* flops) {
     MVE_CHECK(handle && B > 0, MVE_ERR_ARG, "clip_vision_plan: bad arguments");
-    Unet* u = (Unet*)handle;
-    MVE_CHECK(u->cfg.clipv, MVE_ERR_ARG, "clip_vision_plan: handle is not a CLIP vision tower");
-    int rc = ensure_plan(*u, B, u->cfg.cv_image, u->cfg.cv_image, 1, 0, u->cfg.dtype, 0, 0);
+    Unet* u;
+    const int rc = as_engine(handle, "clip_vision_plan", {Kind::ClipVision}, u);
     if (rc) return rc;
-    if (workspace_bytes) *workspace_bytes = u->cur->ws_bytes;
-    if (n_ops) *n_ops = (int)u->cur->ops.size();
-    if (flops) for (int i = 0; i < OC_COUNT; ++i) flops[i] = u->cur->flops[i];
-    return MVE_OK;
+    PlanKey k;
+    k.B = B; k.H = k.W = u->cfg.cv_image; k.io_dtype = u->cfg.dtype;
+    return plan_and_report(*u, k, workspace_bytes, n_ops, flops);
 }
 
 int mve_clip_vision_forward(void* handle, const void* d_pixels, int B, void* d_last_hidden_state, void* d_pooler_output, void* d_image_embeds,
                             void* const* d_hidden_states, void* d_workspace, size_t workspace_bytes, float* op_ms, void* stream) {
-    MVE_CHECK(handle, MVE_ERR_ARG, "clip_vision_forward: null handle");
-    Unet* u = (Unet*)handle;
-    MVE_CHECK(u->cfg.clipv, MVE_ERR_ARG, "clip_vision_forward: handle is not a CLIP vision tower");
-    {
-        char first[256];
-        const int miss = mve_unet_missing_params(handle, first, sizeof(first));
-        MVE_CHECK(miss == 0, MVE_ERR_STATE, "clip_vision_forward: %d parameters not loaded (first: %s)", miss, first);
-    }
-    MVE_CHECK(d_pixels && d_last_hidden_state && d_pooler_output, MVE_ERR_ARG, "clip_vision_forward: null pointer (d_pixels / d_last_hidden_state / d_pooler_output)");
-    MVE_CHECK(u->cfg.clip_proj ? d_image_embeds != nullptr : d_image_embeds == nullptr, MVE_ERR_ARG,
-              "clip_vision_forward: d_image_embeds must be given exactly when the handle has a visual_projection (projection_dim %d)", u->cfg.clip_proj);
-    MVE_CHECK(B > 0, MVE_ERR_ARG, "clip_vision_forward: bad B %d", B);
-    MVE_CHECK(((uintptr_t)d_pixels & 15) == 0, MVE_ERR_ARG, "clip_vision_forward: d_pixels must be 16-byte aligned");
-    int rc = ensure_plan(*u, B, u->cfg.cv_image, u->cfg.cv_image, 1, 0, u->cfg.dtype, 0, 0);
+    Unet* u;
+    const Plan* pl;
+    int rc = begin_forward(handle, "clip_vision_forward", {Kind::ClipVision}, [&](const Unet& e, PlanKey& k) -> int {
+        MVE_CHECK(d_pixels && d_last_hidden_state && d_pooler_output, MVE_ERR_ARG, "clip_vision_forward: null pointer (d_pixels / d_last_hidden_state / d_pooler_output)");
+        MVE_CHECK(e.cfg.clip_proj ? d_image_embeds != nullptr : d_image_embeds == nullptr, MVE_ERR_ARG,
+                  "clip_vision_forward: d_image_embeds must be given exactly when the handle has a visual_projection (projection_dim %d)", e.cfg.clip_proj);
+        MVE_CHECK(B > 0, MVE_ERR_ARG, "clip_vision_forward: bad B %d", B);
+        MVE_CHECK(((uintptr_t)d_pixels & 15) == 0, MVE_ERR_ARG, "clip_vision_forward: d_pixels must be 16-byte aligned");
+        k.B = B; k.H = k.W = e.cfg.cv_image; k.io_dtype = e.cfg.dtype;
+        return MVE_OK;
+    }, d_workspace, workspace_bytes, u, pl);
     if (rc) return rc;
-    const Plan& pl = *u->cur;
-    MVE_CHECK(d_workspace && workspace_bytes >= pl.ws_bytes, MVE_ERR_NOMEM, "clip_vision_forward: workspace %zu < required %zu", workspace_bytes, pl.ws_bytes);
-    const int n_hidden = u->cfg.layers_per_block + 1;
-    std::vector<void*> outs(CLIP_OUT_HIDDEN0 + n_hidden, nullptr);
-    outs[CLIP_OUT_LAST] = d_last_hidden_state; outs[CLIP_OUT_POOLED] = d_pooler_output; outs[CLIP_OUT_EMBEDS] = d_image_embeds;
-    if (d_hidden_states)
-        for (int i = 0; i < n_hidden; ++i) {
-            MVE_CHECK(d_hidden_states[i], MVE_ERR_ARG, "clip_vision_forward: null d_hidden_states[%d]", i);
-            outs[CLIP_OUT_HIDDEN0 + i] = d_hidden_states[i];
-        }
-    Run r;
-    r.ws = (unsigned char*)d_workspace; r.wt = u->slab;
-    r.sample = d_pixels; r.timesteps = nullptr; r.ctx = nullptr; r.out = nullptr;
-    r.down_res = nullptr; r.mid_res = nullptr; r.ref_store = nullptr;
+    std::vector<void*> outs;
+    rc = clip_outputs("clip_vision_forward", *u, d_last_hidden_state, d_pooler_output, d_image_embeds, d_hidden_states, outs);
+    if (rc) return rc;
+    Run r = new_run(*u, d_workspace, stream);
+    r.sample = d_pixels;
     r.cn_out = outs.data();
-    r.stream = (hipStream_t)stream;
-    return run_plan_ops(pl, r, op_ms);
+    return run_plan_ops(*pl, r, 0, pl->ops.size(), op_ms);
 }
 
 int mve_ip_resampler_create(void** handle, int dtype, int dim, int depth, int heads, int num_queries, int embedding_dim, int output_dim, int ff_mult) {
@@ -493,7 +475,7 @@ int mve_ip_resampler_create(void** handle, int dtype, int dim, int depth, int he
     const int inner = dim * ff_mult;      // int(dim * mult), resampler.py:10
     Unet* u = new Unet();
     Config& c = u->cfg;
-    c.resampler = 1; c.rs_queries = num_queries; c.rs_embed = embedding_dim; c.rs_out = output_dim; c.rs_inner = inner;
+    c.kind = Kind::Resampler; c.rs_queries = num_queries; c.rs_embed = embedding_dim; c.rs_out = output_dim; c.rs_inner = inner;
     c.dtype = dtype; c.in_ch = 1; c.out_ch = 1; c.n_levels = 1; c.layers_per_block = depth;
     c.ctx_dim = 8; c.groups = 1; c.eps = 1e-5f; c.linear_proj = 0;
     c.ch[0] = dim; c.attn[0] = 0; c.heads[0] = heads; c.tlayers[0] = 0;
@@ -504,38 +486,28 @@ int mve_ip_resampler_create(void** handle, int dtype, int dim, int depth, int he
 
 int mve_ip_resampler_plan(void* handle, int B, int n1, size_t* workspace_bytes, int* n_ops, double* flops) {
     MVE_CHECK(handle && B > 0 && n1 > 0, MVE_ERR_ARG, "ip_resampler_plan: bad arguments");
-    Unet* u = (Unet*)handle;
-    MVE_CHECK(u->cfg.resampler, MVE_ERR_ARG, "ip_resampler_plan: handle is not a Resampler");
-    int rc = ensure_plan(*u, B, n1, 1, 1, 0, u->cfg.dtype, 0, 0);
+    Unet* u;
+    const int rc = as_engine(handle, "ip_resampler_plan", {Kind::Resampler}, u);
     if (rc) return rc;
-    if (workspace_bytes) *workspace_bytes = u->cur->ws_bytes;
-    if (n_ops) *n_ops = (int)u->cur->ops.size();
-    if (flops) for (int i = 0; i < OC_COUNT; ++i) flops[i] = u->cur->flops[i];
-    return MVE_OK;
+    PlanKey k;
+    k.B = B; k.H = n1; k.W = 1; k.io_dtype = u->cfg.dtype;
+    return plan_and_report(*u, k, workspace_bytes, n_ops, flops);
 }
 
 int mve_ip_resampler_forward(void* handle, const void* d_x, int B, int n1, void* d_out, void* d_workspace, size_t workspace_bytes, float* op_ms, void* stream) {
-    MVE_CHECK(handle, MVE_ERR_ARG, "ip_resampler_forward: null handle");
-    Unet* u = (Unet*)handle;
-    MVE_CHECK(u->cfg.resampler, MVE_ERR_ARG, "ip_resampler_forward: handle is not a Resampler");
-    {
-        char first[256];
-        const int miss = mve_unet_missing_params(handle, first, sizeof(first));
-        MVE_CHECK(miss == 0, MVE_ERR_STATE, "ip_resampler_forward: %d parameters not loaded (first: %s)", miss, first);
-    }
-    MVE_CHECK(d_x && d_out, MVE_ERR_ARG, "ip_resampler_forward: null pointer (d_x / d_out)");
-    MVE_CHECK(B > 0 && n1 > 0, MVE_ERR_ARG, "ip_resampler_forward: bad B %d / n1 %d", B, n1);
-    MVE_CHECK(((uintptr_t)d_x & 15) == 0 && ((uintptr_t)d_out & 15) == 0, MVE_ERR_ARG, "ip_resampler_forward: d_x / d_out must be 16-byte aligned");
-    int rc = ensure_plan(*u, B, n1, 1, 1, 0, u->cfg.dtype, 0, 0);
+    Unet* u;
+    const Plan* pl;
+    const int rc = begin_forward(handle, "ip_resampler_forward", {Kind::Resampler}, [&](const Unet& e, PlanKey& k) -> int {
+        MVE_CHECK(d_x && d_out, MVE_ERR_ARG, "ip_resampler_forward: null pointer (d_x / d_out)");
+        MVE_CHECK(B > 0 && n1 > 0, MVE_ERR_ARG, "ip_resampler_forward: bad B %d / n1 %d", B, n1);
+        MVE_CHECK(((uintptr_t)d_x & 15) == 0 && ((uintptr_t)d_out & 15) == 0, MVE_ERR_ARG, "ip_resampler_forward: d_x / d_out must be 16-byte aligned");
+        k.B = B; k.H = n1; k.W = 1; k.io_dtype = e.cfg.dtype;
+        return MVE_OK;
+    }, d_workspace, workspace_bytes, u, pl);
     if (rc) return rc;
-    const Plan& pl = *u->cur;
-    MVE_CHECK(d_workspace && workspace_bytes >= pl.ws_bytes, MVE_ERR_NOMEM, "ip_resampler_forward: workspace %zu < required %zu", workspace_bytes, pl.ws_bytes);
-    Run r;
-    r.ws = (unsigned char*)d_workspace; r.wt = u->slab;
-    r.sample = d_x; r.timesteps = nullptr; r.ctx = nullptr; r.out = d_out;
-    r.down_res = nullptr; r.mid_res = nullptr; r.ref_store = nullptr;
-    r.stream = (hipStream_t)stream;
-    return run_plan_ops(pl, r, op_ms);
+    Run r = new_run(*u, d_workspace, stream);
+    r.sample = d_x; r.out = d_out;
+    return run_plan_ops(*pl, r, 0, pl->ops.size(), op_ms);
 }
 
 int mve_dpt_create(void** handle, int dtype, int image_size, int stem_width, const int* stage_widths, const int* stage_depths, int num_groups, int hidden_size,
@@ -563,7 +535,7 @@ int mve_dpt_create(void** handle, int dtype, int image_size, int stem_width, con
     MVE_CHECK(layer_norm_eps > 0.f, MVE_ERR_ARG, "dpt_create: layer_norm_eps must be positive");
     Unet* u = new Unet();
     Config& c = u->cfg;
-    c.dpt = 1; c.dp_image = image_size; c.dp_stem = stem_width; c.dp_inter = intermediate_size; c.dp_features = features;
+    c.kind = Kind::Dpt; c.dp_image = image_size; c.dp_stem = stem_width; c.dp_inter = intermediate_size; c.dp_features = features;
     for (int s = 0; s < 3; ++s) { c.dp_stage[s] = stage_widths[s]; c.dp_depth[s] = stage_depths[s]; }
     for (int k = 0; k < 2; ++k) { c.dp_tap[k] = tap_layers[k]; c.dp_neck[k] = neck_channels[k]; }
     c.dtype = dtype; c.in_ch = 3; c.out_ch = num_channels; c.n_levels = 1; c.layers_per_block = num_layers;
@@ -576,43 +548,33 @@ int mve_dpt_create(void** handle, int dtype, int image_size, int stem_width, con
 
 int mve_dpt_plan(void* handle, int B, size_t* workspace_bytes, int* n_ops, double* flops) {
     MVE_CHECK(handle && B > 0, MVE_ERR_ARG, "dpt_plan: bad arguments");
-    Unet* u = (Unet*)handle;
-    MVE_CHECK(u->cfg.dpt, MVE_ERR_ARG, "dpt_plan: handle is not a DPT model");
-    int rc = ensure_plan(*u, B, u->cfg.dp_image, u->cfg.dp_image, 1, 0, u->cfg.dtype, 0, 0);
+    Unet* u;
+    const int rc = as_engine(handle, "dpt_plan", {Kind::Dpt}, u);
     if (rc) return rc;
-    if (workspace_bytes) *workspace_bytes = u->cur->ws_bytes;
-    if (n_ops) *n_ops = (int)u->cur->ops.size();
-    if (flops) for (int i = 0; i < OC_COUNT; ++i) flops[i] = u->cur->flops[i];
-    return MVE_OK;
+    PlanKey k;
+    k.B = B; k.H = k.W = u->cfg.dp_image; k.io_dtype = u->cfg.dtype;
+    return plan_and_report(*u, k, workspace_bytes, n_ops, flops);
 }
 
 int mve_dpt_forward(void* handle, const void* d_pixels, int B, void* d_out, void* const* d_taps, void* d_workspace, size_t workspace_bytes, float* op_ms,
                     void* stream) {
-    MVE_CHECK(handle, MVE_ERR_ARG, "dpt_forward: null handle");
-    Unet* u = (Unet*)handle;
-    MVE_CHECK(u->cfg.dpt, MVE_ERR_ARG, "dpt_forward: handle is not a DPT model");
-    {
-        char first[256];
-        const int miss = mve_unet_missing_params(handle, first, sizeof(first));
-        MVE_CHECK(miss == 0, MVE_ERR_STATE, "dpt_forward: %d parameters not loaded (first: %s)", miss, first);
-    }
-    MVE_CHECK(d_pixels && d_out, MVE_ERR_ARG, "dpt_forward: null pointer (d_pixels / d_out)");
-    MVE_CHECK(B > 0, MVE_ERR_ARG, "dpt_forward: bad B %d", B);
-    MVE_CHECK(((uintptr_t)d_pixels & 15) == 0 && ((uintptr_t)d_out & 15) == 0, MVE_ERR_ARG, "dpt_forward: d_pixels / d_out must be 16-byte aligned");
-    int rc = ensure_plan(*u, B, u->cfg.dp_image, u->cfg.dp_image, 1, 0, u->cfg.dtype, 0, 0);
+    Unet* u;
+    const Plan* pl;
+    const int rc = begin_forward(handle, "dpt_forward", {Kind::Dpt}, [&](const Unet& e, PlanKey& k) -> int {
+        MVE_CHECK(d_pixels && d_out, MVE_ERR_ARG, "dpt_forward: null pointer (d_pixels / d_out)");
+        MVE_CHECK(B > 0, MVE_ERR_ARG, "dpt_forward: bad B %d", B);
+        MVE_CHECK(((uintptr_t)d_pixels & 15) == 0 && ((uintptr_t)d_out & 15) == 0, MVE_ERR_ARG, "dpt_forward: d_pixels / d_out must be 16-byte aligned");
+        k.B = B; k.H = k.W = e.cfg.dp_image; k.io_dtype = e.cfg.dtype;
+        return MVE_OK;
+    }, d_workspace, workspace_bytes, u, pl);
     if (rc) return rc;
-    const Plan& pl = *u->cur;
-    MVE_CHECK(d_workspace && workspace_bytes >= pl.ws_bytes, MVE_ERR_NOMEM, "dpt_forward: workspace %zu < required %zu", workspace_bytes, pl.ws_bytes);
     std::vector<void*> taps(DPT_TAPS, nullptr);
     if (d_taps)
         for (int i = 0; i < DPT_TAPS; ++i) taps[i] = d_taps[i];      // a null entry: that tap is not wanted
-    Run r;
-    r.ws = (unsigned char*)d_workspace; r.wt = u->slab;
-    r.sample = d_pixels; r.timesteps = nullptr; r.ctx = nullptr; r.out = d_out;
-    r.down_res = nullptr; r.mid_res = nullptr; r.ref_store = nullptr;
+    Run r = new_run(*u, d_workspace, stream);
+    r.sample = d_pixels; r.out = d_out;
     r.cn_out = taps.data();
-    r.stream = (hipStream_t)stream;
-    return run_plan_ops(pl, r, op_ms);
+    return run_plan_ops(*pl, r, 0, pl->ops.size(), op_ms);
 }
 
 int mve_loftr_create(void** handle, int dtype) {
@@ -620,7 +582,7 @@ int mve_loftr_create(void** handle, int dtype) {
     MVE_CHECK(dtype == MVE_F16 || dtype == MVE_BF16, MVE_ERR_ARG, "loftr_create: dtype must be f16 or bf16");
     Unet* u = new Unet();
     Config& c = u->cfg;
-    c.loftr = 1;
+    c.kind = Kind::Loftr;
     c.dtype = dtype; c.in_ch = 1; c.out_ch = 1; c.n_levels = 1; c.layers_per_block = 8;
     c.ctx_dim = 8; c.groups = 1; c.eps = 1e-5f; c.linear_proj = 0;
     c.ch[0] = 256; c.attn[0] = 0; c.heads[0] = 8; c.tlayers[0] = 0;
@@ -638,70 +600,62 @@ static int loftr_check_shape(const char* who, int phase, int N, int H, int W) {
 }
 
 int mve_loftr_plan(void* handle, int phase, int N, int H, int W, size_t* workspace_bytes, int* n_ops, double* flops) {
-    MVE_CHECK(handle, MVE_ERR_ARG, "loftr_plan: null handle");
-    Unet* u = (Unet*)handle;
-    MVE_CHECK(u->cfg.loftr, MVE_ERR_ARG, "loftr_plan: handle is not a LoFTR model");
-    int rc = loftr_check_shape("loftr_plan", phase, N, H, W);
+    Unet* u;
+    int rc = as_engine(handle, "loftr_plan", {Kind::Loftr}, u);
     if (rc) return rc;
-    rc = ensure_plan(*u, N, H, W, phase, 0, u->cfg.dtype, 0, 0);
+    rc = loftr_check_shape("loftr_plan", phase, N, H, W);
     if (rc) return rc;
-    if (workspace_bytes) *workspace_bytes = u->cur->ws_bytes;
-    if (n_ops) *n_ops = (int)u->cur->ops.size();
-    if (flops) for (int i = 0; i < OC_COUNT; ++i) flops[i] = u->cur->flops[i];
-    return MVE_OK;
+    PlanKey k;
+    k.B = N; k.H = H; k.W = W; k.n_img = phase; k.io_dtype = u->cfg.dtype;
+    return plan_and_report(*u, k, workspace_bytes, n_ops, flops);
 }
 
-static int loftr_run(Unet* u, const char* who, int phase, int N, int H, int W, const void* d_images, const float* d_pos, int M, float thr, int border, void* const* d_io,
+static int loftr_run(void* handle, const char* who, int phase, int N, int H, int W, const void* d_images, const float* d_pos, int M, float thr, int border, void* const* d_io,
                      void* const* d_taps, int n_taps, void* d_workspace, size_t workspace_bytes, float* op_ms, void* stream) {
-    {
-        char first[256];
-        const int miss = mve_unet_missing_params(u, first, sizeof(first));
-        MVE_CHECK(miss == 0, MVE_ERR_STATE, "%s: %d parameters not loaded (first: %s)", who, miss, first);
-    }
-    MVE_CHECK(d_io, MVE_ERR_ARG, "%s: null pointer (d_io)", who);
-    for (int i = 0; i < LOFTR_IO; ++i) {
-        const bool used = phase == 1 ? i <= 10 : (i <= 1 || (i >= 4 && i <= 6) || i == 9 || i >= 11);
-        MVE_CHECK(!used || (d_io[i] && ((uintptr_t)d_io[i] & 15) == 0), MVE_ERR_ARG, "%s: d_io[%d] is null or not 16-byte aligned", who, i);
-    }
-    int rc = ensure_plan(*u, N, H, W, phase, 0, u->cfg.dtype, 0, 0);
+    Unet* u;
+    const Plan* pl;
+    const int rc = begin_forward(handle, who, {Kind::Loftr}, [&](const Unet& e, PlanKey& k) -> int {
+        MVE_CHECK(d_io, MVE_ERR_ARG, "%s: null pointer (d_io)", who);
+        for (int i = 0; i < LOFTR_IO; ++i) {
+            const bool used = phase == 1 ? i <= 10 : (i <= 1 || (i >= 4 && i <= 6) || i == 9 || i >= 11);
+            MVE_CHECK(!used || (d_io[i] && ((uintptr_t)d_io[i] & 15) == 0), MVE_ERR_ARG, "%s: d_io[%d] is null or not 16-byte aligned", who, i);
+        }
+        k.B = N; k.H = H; k.W = W; k.n_img = phase; k.io_dtype = e.cfg.dtype;
+        return MVE_OK;
+    }, d_workspace, workspace_bytes, u, pl);
     if (rc) return rc;
-    const Plan& pl = *u->cur;
-    MVE_CHECK(d_workspace && workspace_bytes >= pl.ws_bytes, MVE_ERR_NOMEM, "%s: workspace %zu < required %zu", who, workspace_bytes, pl.ws_bytes);
     std::vector<void*> ptrs(LOFTR_IO + LOFTR_TAPS_COARSE, nullptr);
     for (int i = 0; i < LOFTR_IO; ++i) ptrs[i] = d_io[i];
     if (d_taps)
         for (int i = 0; i < n_taps; ++i) ptrs[LOFTR_IO + i] = d_taps[i];      // a null entry: that tap is not wanted
-    Run r;
-    r.ws = (unsigned char*)d_workspace; r.wt = u->slab;
-    r.sample = d_images; r.timesteps = nullptr; r.ctx = d_pos; r.out = nullptr;
-    r.down_res = nullptr; r.mid_res = nullptr; r.ref_store = nullptr;
+    Run r = new_run(*u, d_workspace, stream);
+    r.sample = d_images; r.ctx = d_pos;
     r.cn_out = ptrs.data();
     r.loftr_M = M; r.loftr_thr = thr; r.loftr_border = border;
-    r.stream = (hipStream_t)stream;
-    return run_plan_ops(pl, r, op_ms);
+    return run_plan_ops(*pl, r, 0, pl->ops.size(), op_ms);
 }
 
 int mve_loftr_forward_coarse(void* handle, const void* d_images, const float* d_pos, int N, int H, int W, float thr, int border, void* const* d_io, void* const* d_taps,
                              void* d_workspace, size_t workspace_bytes, float* op_ms, void* stream) {
-    MVE_CHECK(handle, MVE_ERR_ARG, "loftr_forward_coarse: null handle");
-    Unet* u = (Unet*)handle;
-    MVE_CHECK(u->cfg.loftr, MVE_ERR_ARG, "loftr_forward_coarse: handle is not a LoFTR model");
-    const int rc = loftr_check_shape("loftr_forward_coarse", 1, N, H, W);
+    Unet* u;
+    int rc = as_engine(handle, "loftr_forward_coarse", {Kind::Loftr}, u);
+    if (rc) return rc;
+    rc = loftr_check_shape("loftr_forward_coarse", 1, N, H, W);
     if (rc) return rc;
     MVE_CHECK(d_images && d_pos && ((uintptr_t)d_images & 15) == 0 && ((uintptr_t)d_pos & 15) == 0, MVE_ERR_ARG, "loftr_forward_coarse: d_images / d_pos null or not 16-byte aligned");
-    return loftr_run(u, "loftr_forward_coarse", 1, N, H, W, d_images, d_pos, 0, thr, border, d_io, d_taps, LOFTR_TAPS_COARSE, d_workspace, workspace_bytes, op_ms, stream);
+    return loftr_run(handle, "loftr_forward_coarse", 1, N, H, W, d_images, d_pos, 0, thr, border, d_io, d_taps, LOFTR_TAPS_COARSE, d_workspace, workspace_bytes, op_ms, stream);
 }
 
 int mve_loftr_forward_fine(void* handle, int N, int H, int W, int M, void* const* d_io, void* const* d_taps, void* d_workspace, size_t workspace_bytes, float* op_ms,
                            void* stream) {
-    MVE_CHECK(handle, MVE_ERR_ARG, "loftr_forward_fine: null handle");
-    Unet* u = (Unet*)handle;
-    MVE_CHECK(u->cfg.loftr, MVE_ERR_ARG, "loftr_forward_fine: handle is not a LoFTR model");
-    const int rc = loftr_check_shape("loftr_forward_fine", 2, N, H, W);
+    Unet* u;
+    int rc = as_engine(handle, "loftr_forward_fine", {Kind::Loftr}, u);
+    if (rc) return rc;
+    rc = loftr_check_shape("loftr_forward_fine", 2, N, H, W);
     if (rc) return rc;
     MVE_CHECK(M >= 1 && (long long)M <= (long long)N * (H / 8) * (W / 8), MVE_ERR_ARG, "loftr_forward_fine: M %d must be in [1, N * L = %lld] (no fine call for an empty match set)", M,
               (long long)N * (H / 8) * (W / 8));
-    return loftr_run(u, "loftr_forward_fine", 2, N, H, W, nullptr, nullptr, M, 0.f, 0, d_io, d_taps, LOFTR_TAPS_FINE, d_workspace, workspace_bytes, op_ms, stream);
+    return loftr_run(handle, "loftr_forward_fine", 2, N, H, W, nullptr, nullptr, M, 0.f, 0, d_io, d_taps, LOFTR_TAPS_FINE, d_workspace, workspace_bytes, op_ms, stream);
 }
 
 int mve_loftr_destroy(void* handle) { return mve_unet_destroy(handle); }
@@ -711,7 +665,7 @@ int mve_lpips_create(void** handle, int dtype, int normalize_inputs) {
     MVE_CHECK(dtype == MVE_F16 || dtype == MVE_BF16, MVE_ERR_ARG, "lpips_create: dtype must be f16 or bf16");
     Unet* u = new Unet();
     Config& c = u->cfg;
-    c.lpips = 1; c.lpips_normalize = normalize_inputs ? 1 : 0;
+    c.kind = Kind::Lpips; c.lpips_normalize = normalize_inputs ? 1 : 0;
     c.dtype = dtype; c.in_ch = 3; c.out_ch = 3; c.n_levels = 1; c.layers_per_block = 1;
     c.ctx_dim = 8; c.groups = 1; c.eps = 0.f; c.linear_proj = 0;
     c.ch[0] = 64; c.attn[0] = 0; c.heads[0] = 1; c.tlayers[0] = 0;
@@ -722,14 +676,14 @@ int mve_lpips_create(void** handle, int dtype, int normalize_inputs) {
 
 int mve_lpips_plan(void* handle, int B, int H, int W, int io_dtype, size_t* workspace_bytes, int* n_ops, int* n_forward_ops, double* flops) {
     MVE_CHECK(handle && B > 0 && H > 0 && W > 0, MVE_ERR_ARG, "lpips_plan: bad arguments");
-    Unet* u = (Unet*)handle;
-    MVE_CHECK(u->cfg.lpips, MVE_ERR_ARG, "lpips_plan: handle is not an LPIPS engine");
-    int rc = ensure_plan(*u, B, H, W, 1, 0, io_dtype, 0, 0);
+    Unet* u;
+    int rc = as_engine(handle, "lpips_plan", {Kind::Lpips}, u);
     if (rc) return rc;
-    if (workspace_bytes) *workspace_bytes = u->cur->ws_bytes;
-    if (n_ops) *n_ops = (int)u->cur->ops.size();
+    PlanKey k;
+    k.B = B; k.H = H; k.W = W; k.io_dtype = io_dtype;
+    rc = plan_and_report(*u, k, workspace_bytes, n_ops, flops);
+    if (rc) return rc;
     if (n_forward_ops) *n_forward_ops = (int)u->cur->enc_end;
-    if (flops) for (int i = 0; i < OC_COUNT; ++i) flops[i] = u->cur->flops[i];
     return MVE_OK;
 }
 
@@ -737,30 +691,17 @@ int mve_lpips_plan(void* handle, int B, int H, int W, int io_dtype, size_t* work
 // activations phase 1 left in d_workspace: same workspace, same (B, H, W), no other call on it in between.
 static int lpips_run(void* handle, int phase, const void* d_pred, const void* d_target, const float* d_grad_loss, int io_dtype, int B, int H,
                      int W, void* d_out, void* d_workspace, size_t workspace_bytes, void* stream) {
-    MVE_CHECK(handle, MVE_ERR_ARG, "lpips: null handle");
-    Unet* u = (Unet*)handle;
-    MVE_CHECK(u->cfg.lpips, MVE_ERR_ARG, "lpips: handle is not an LPIPS engine");
-    {
-        char first[256];
-        const int miss = mve_unet_missing_params(handle, first, sizeof(first));
-        MVE_CHECK(miss == 0, MVE_ERR_STATE, "lpips: %d parameters not loaded (first: %s)", miss, first);
-    }
-    MVE_CHECK(d_out && (phase == 2 ? d_grad_loss != nullptr : (d_pred && d_target)), MVE_ERR_ARG, "lpips: null pointer");
-    int rc = ensure_plan(*u, B, H, W, 1, 0, io_dtype, 0, 0);
+    Unet* u;
+    const Plan* pl;
+    const int rc = begin_forward(handle, "lpips", {Kind::Lpips}, [&](const Unet&, PlanKey& k) -> int {
+        MVE_CHECK(d_out && (phase == 2 ? d_grad_loss != nullptr : (d_pred && d_target)), MVE_ERR_ARG, "lpips: null pointer");
+        k.B = B; k.H = H; k.W = W; k.io_dtype = io_dtype;
+        return MVE_OK;
+    }, d_workspace, workspace_bytes, u, pl);
     if (rc) return rc;
-    const Plan& pl = *u->cur;
-    MVE_CHECK(d_workspace && workspace_bytes >= pl.ws_bytes, MVE_ERR_NOMEM, "lpips: workspace %zu < required %zu", workspace_bytes, pl.ws_bytes);
-    Run r;
-    r.ws = (unsigned char*)d_workspace; r.wt = u->slab;
+    Run r = new_run(*u, d_workspace, stream);
     r.sample = d_pred; r.timesteps = d_grad_loss; r.ctx = d_target; r.out = d_out;
-    r.down_res = nullptr; r.mid_res = nullptr; r.ref_store = nullptr;
-    r.stream = (hipStream_t)stream;
-    const size_t lo = phase == 2 ? pl.enc_end : 0, hi = phase == 1 ? pl.enc_end : pl.ops.size();
-    for (size_t i = lo; i < hi; ++i) {
-        rc = pl.ops[i].fn(r);
-        if (rc) return rc;
-    }
-    return MVE_OK;
+    return run_plan_ops(*pl, r, phase == 2 ? pl->enc_end : 0, phase == 1 ? pl->enc_end : pl->ops.size(), nullptr);
 }
 
 int mve_lpips_forward(void* handle, const void* d_pred, const void* d_target, int io_dtype, int B, int H, int W, float* d_loss,
@@ -804,13 +745,14 @@ int mve_unet_load_param(void* handle, const char* name, const void* d_src, int s
         MVE_HIP(hipMemsetAsync(u->slab, 0, u->slab_bytes, (hipStream_t)stream));      // padding rows / optional weights start as zeros
     }
     std::string nm = name;
-    if (u->cfg.lpips && nm.compare(0, 5, "lins.") == 0) nm = "lin" + nm.substr(5);      // nn.ModuleList alias of lin0..lin4
-    if (u->cfg.vae) {     // AutoencoderKL state-dict names -> the half's own
-        const std::string own = u->cfg.vae == 1 ? "decoder." : "encoder.", pq = u->cfg.vae == 1 ? "post_quant_conv." : "quant_conv.";
+    if (u->cfg.kind == Kind::Lpips && nm.compare(0, 5, "lins.") == 0) nm = "lin" + nm.substr(5);      // nn.ModuleList alias of lin0..lin4
+    if (u->cfg.is_vae()) {     // AutoencoderKL state-dict names -> the half's own
+        const bool dec = u->cfg.kind == Kind::VaeDecoder;
+        const std::string own = dec ? "decoder." : "encoder.", pq = dec ? "post_quant_conv." : "quant_conv.";
         if (nm.compare(0, own.size(), own) == 0) nm = nm.substr(own.size());
         else if (nm.compare(0, pq.size(), pq) == 0) nm = "pq_conv." + nm.substr(pq.size());
         else {
-            mve_set_error("vae_load_param: %s does not belong to the %s", name, u->cfg.vae == 1 ? "decoder" : "encoder");
+            mve_set_error("vae_load_param: %s does not belong to the %s", name, dec ? "decoder" : "encoder");
             return MVE_ERR_ARG;
         }
     }
@@ -831,43 +773,34 @@ int mve_unet_missing_params(void* handle, char* buf, int buf_len) {
 int mve_unet_plan(void* handle, int B, int H, int W, int ctx_len, int num_cross_attn_imgs, int has_residuals, int io_dtype,
                   int residuals_nhwc, size_t* workspace_bytes, int* n_ops, double* flops /* [5]: conv, linear, attention, norm, other */) {
     MVE_CHECK(handle && B > 0 && H > 0 && W > 0 && ctx_len > 0 && num_cross_attn_imgs >= 1, MVE_ERR_ARG, "unet_plan: bad arguments");
-    Unet* u = (Unet*)handle;
-    int rc = ensure_plan(*u, B, H, W, num_cross_attn_imgs, has_residuals, io_dtype, residuals_nhwc, ctx_len);
+    Unet* u;
+    const int rc = as_engine(handle, "unet_plan", {Kind::UNet, Kind::ControlNet}, u);
     if (rc) return rc;
-    if (workspace_bytes) *workspace_bytes = u->cur->ws_bytes;
-    if (n_ops) *n_ops = (int)u->cur->ops.size();
-    if (flops) for (int i = 0; i < OC_COUNT; ++i) flops[i] = u->cur->flops[i];
-    return MVE_OK;
+    PlanKey k;
+    k.B = B; k.H = H; k.W = W; k.n_img = num_cross_attn_imgs; k.has_res = has_residuals; k.io_dtype = io_dtype; k.res_nhwc = residuals_nhwc; k.ctx_len = ctx_len;
+    return plan_and_report(*u, k, workspace_bytes, n_ops, flops);
 }
 
 int mve_unet_forward(void* handle, int phase, const void* d_sample, int io_dtype, const float* d_timesteps, const void* d_ctx,
                      int B, int H, int W, int ctx_len, int num_cross_attn_imgs, const void* const* down_residuals,
                      const void* d_mid_residual, int residuals_nhwc, void* d_out, void* d_workspace, size_t workspace_bytes,
                      float* op_ms /* optional host array [n_ops]: per-op milliseconds (synchronises) */, void* stream) {
-    MVE_CHECK(handle, MVE_ERR_ARG, "unet_forward: null handle");
-    Unet* u = (Unet*)handle;
-    MVE_CHECK(!u->cfg.controlnet && !u->cfg.vae && !u->cfg.sr && !u->cfg.lpips && !u->cfg.clip && !u->cfg.clipv && !u->cfg.resampler && !u->cfg.dpt && !u->cfg.loftr, MVE_ERR_ARG,
-              "unet_forward: handle is a ControlNet / VAE / SRVGG / CLIP text or vision tower / Resampler / DPT / LoFTR (use their own forward calls)");
-    {
-        char first[256];
-        const int miss = mve_unet_missing_params(handle, first, sizeof(first));
-        MVE_CHECK(miss == 0, MVE_ERR_STATE, "unet_forward: %d parameters not loaded (first: %s)", miss, first);
-    }
     const int has_res = (down_residuals && d_mid_residual) ? 1 : 0;
-    int rc = ensure_plan(*u, B, H, W, num_cross_attn_imgs, has_res, io_dtype, residuals_nhwc, ctx_len);
+    Unet* u;
+    const Plan* plan;
+    int rc = begin_forward(handle, "unet_forward", {Kind::UNet}, [&](const Unet&, PlanKey& k) -> int {
+        k.B = B; k.H = H; k.W = W; k.n_img = num_cross_attn_imgs; k.has_res = has_res; k.io_dtype = io_dtype; k.res_nhwc = residuals_nhwc; k.ctx_len = ctx_len;
+        return MVE_OK;
+    }, d_workspace, workspace_bytes, u, plan);
     if (rc) return rc;
-    const Plan& pl = *u->cur;
-    MVE_CHECK(d_workspace && workspace_bytes >= pl.ws_bytes, MVE_ERR_NOMEM, "unet_forward: workspace %zu < required %zu",
-              workspace_bytes, pl.ws_bytes);
+    const Plan& pl = *plan;
     MVE_CHECK(d_timesteps && d_ctx && (phase == 1 || d_out) && (phase == 2 || d_sample), MVE_ERR_ARG, "unet_forward: null pointer");
-    Run r;
-    r.ws = (unsigned char*)d_workspace; r.wt = u->slab;
+    Run r = new_run(*u, d_workspace, stream);
     r.sample = d_sample; r.timesteps = d_timesteps; r.ctx = d_ctx; r.out = d_out;
     r.down_res = down_residuals; r.mid_res = d_mid_residual;
     r.ref_store = u->ref_store;
     MVE_CHECK(pl.ref_store_bytes == 0 || (u->ref_store && u->ref_store_bytes >= pl.ref_store_bytes), MVE_ERR_NOMEM,
               "unet_forward: reference store %zu < required %zu bytes", u->ref_store_bytes, pl.ref_store_bytes);
-    r.stream = (hipStream_t)stream;
     if (phase != 2) {      // unet_dec reuses the emb of its unet_enc state
         rc = take_added_cond(*u, B, r, "unet_forward");
         if (rc) return rc;
@@ -895,7 +828,7 @@ int mve_unet_forward(void* handle, int phase, const void* d_sample, int io_dtype
         }
         if (ge) {           // second sighting: capture, instantiate, launch
             MVE_HIP(hipStreamBeginCapture(r.stream, hipStreamCaptureModeRelaxed));
-            for (size_t i = lo; i < hi && rc == MVE_OK; ++i) rc = pl.ops[i].fn(r);
+            rc = run_plan_ops(pl, r, lo, hi, nullptr);
             hipGraph_t graph = nullptr;
             const hipError_t ce = hipStreamEndCapture(r.stream, &graph);
             if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
@@ -917,23 +850,7 @@ int mve_unet_forward(void* handle, int phase, const void* d_sample, int io_dtype
         ne.plan_uid = pl.uid; ne.phase = phase; ne.seen = 1; ne.ptrs = key; ne.last_use = u->tick;
         u->graphs.push_back(ne);          // first sighting: run eagerly below (also performs any one-time kernel attribute set-up)
     }
-    std::vector<hipEvent_t> ev;
-    if (op_ms) {
-        ev.resize(hi - lo + 1);
-        for (auto& e : ev) MVE_HIP(hipEventCreate(&e));
-        MVE_HIP(hipEventRecord(ev[0], r.stream));
-    }
-    for (size_t i = lo; i < hi; ++i) {
-        rc = pl.ops[i].fn(r);
-        if (rc) return rc;
-        if (op_ms) MVE_HIP(hipEventRecord(ev[i - lo + 1], r.stream));
-    }
-    if (op_ms) {
-        MVE_HIP(hipStreamSynchronize(r.stream));
-        for (size_t i = lo; i < hi; ++i) MVE_HIP(hipEventElapsedTime(&op_ms[i], ev[i - lo], ev[i - lo + 1]));
-        for (auto& e : ev) (void)hipEventDestroy(e);
-    }
-    return MVE_OK;
+    return run_plan_ops(pl, r, lo, hi, op_ms);
 }
 
 int mve_unet_graph(void* handle, int enable) {
@@ -964,7 +881,7 @@ int mve_unet_set_attention(void* handle, int ip_tokens, float ip_scale, int ref_
 int mve_unet_set_residual_mode(void* handle, int pair) {
     MVE_CHECK(handle, MVE_ERR_ARG, "unet_set_residual_mode: null handle");
     Unet* u = (Unet*)handle;
-    MVE_CHECK(!u->cfg.vae && !u->cfg.sr && !u->cfg.lpips && !u->cfg.clip && !u->cfg.clipv && !u->cfg.resampler && !u->cfg.dpt && !u->cfg.loftr, MVE_ERR_ARG, "unet_set_residual_mode: a UNet / ControlNet handle is needed");
+    MVE_CHECK(u->cfg.is_denoiser(), MVE_ERR_ARG, "unet_set_residual_mode: a UNet / ControlNet handle is needed");
     const int old = u->ao.residual_pair;
     if (pair >= 0) u->ao.residual_pair = pair ? 1 : 0;     // part of the plan key: plans of either mode stay cached side by side
     return old;
@@ -973,7 +890,7 @@ int mve_unet_set_residual_mode(void* handle, int pair) {
 int mve_unet_tune_cfg_prefix(void* handle, int on) {
     MVE_CHECK(handle, MVE_ERR_ARG, "unet_tune_cfg_prefix: null handle");
     Unet* u = (Unet*)handle;
-    MVE_CHECK(!u->cfg.controlnet && !u->cfg.vae && !u->cfg.sr && !u->cfg.lpips, MVE_ERR_ARG, "unet_tune_cfg_prefix: a UNet handle is needed");
+    MVE_CHECK(u->cfg.kind == Kind::UNet, MVE_ERR_ARG, "unet_tune_cfg_prefix: a UNet handle is needed");
     const int old = u->ao.cfg_prefix;
     if (on >= 0) u->ao.cfg_prefix = on ? 1 : 0;            // part of the plan key, like the residual mode
     return old;
@@ -993,7 +910,7 @@ int mve_unet_set_addition_embed(void* handle, int addition_type, int addition_ti
     MVE_CHECK(handle, MVE_ERR_ARG, "unet_set_addition_embed: null handle");
     Unet* u = (Unet*)handle;
     Config& c = u->cfg;
-    MVE_CHECK(!c.vae && !c.sr && !c.lpips && !c.clip && !c.clipv && !c.resampler && !c.dpt && !c.loftr, MVE_ERR_ARG, "unet_set_addition_embed: a UNet / ControlNet handle is needed");
+    MVE_CHECK(c.is_denoiser(), MVE_ERR_ARG, "unet_set_addition_embed: a UNet / ControlNet handle is needed");
     MVE_CHECK(addition_type == 0 || addition_type == 1, MVE_ERR_ARG, "unet_set_addition_embed: addition type %d (0 = none, 1 = text_time)", addition_type);
     MVE_CHECK(!u->slab && u->loaded.empty(), MVE_ERR_STATE, "unet_set_addition_embed: parameters are already loaded; declare the embedding right after create");
     MVE_CHECK(!c.add_type, MVE_ERR_STATE, "unet_set_addition_embed: the handle already has an addition embedding");
@@ -1026,7 +943,7 @@ int mve_unet_bind_added_cond(void* handle, const void* d_text_embeds, int text_d
 int mve_controlnet_set_cond_repeat(void* handle, int repeat) {
     MVE_CHECK(handle, MVE_ERR_ARG, "controlnet_set_cond_repeat: null handle");
     Unet* u = (Unet*)handle;
-    MVE_CHECK(u->cfg.controlnet, MVE_ERR_ARG, "controlnet_set_cond_repeat: a ControlNet handle is needed");
+    MVE_CHECK(u->cfg.kind == Kind::ControlNet, MVE_ERR_ARG, "controlnet_set_cond_repeat: a ControlNet handle is needed");
     const int old = u->ao.cn_cond_repeat;
     if (repeat >= 1) u->ao.cn_cond_repeat = repeat;        // part of the plan key
     return old;
@@ -1035,7 +952,7 @@ int mve_controlnet_set_cond_repeat(void* handle, int repeat) {
 int mve_unet_set_context_tail(void* handle, int rows) {
     MVE_CHECK(handle, MVE_ERR_ARG, "unet_set_context_tail: null handle");
     Unet* u = (Unet*)handle;
-    MVE_CHECK(!u->cfg.vae && !u->cfg.sr && !u->cfg.lpips, MVE_ERR_ARG, "unet_set_context_tail: a UNet / ControlNet handle is needed");
+    MVE_CHECK(u->cfg.is_denoiser(), MVE_ERR_ARG, "unet_set_context_tail: a UNet / ControlNet handle is needed");
     const int old = u->ao.ctx_tail;
     if (rows >= 0) u->ao.ctx_tail = rows;                  // part of the plan key (and through the plan's uid of the graph key)
     return old;

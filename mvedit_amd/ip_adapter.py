@@ -15,37 +15,10 @@ import torch
 
 from . import _lib
 from .ops import dt as _dt
-from .module_surface import ModuleSurface
-from .text_encoder import OP_CLASSES
+from .module_surface import EngineHandle, InferenceSurface
 
 
-class _Surface(ModuleSurface):
-    def eval(self):
-        return self
-
-    def requires_grad_(self, requires_grad=False):
-        if requires_grad:
-            raise NotImplementedError(f'{type(self).__name__}.requires_grad_(True): the engine is inference only')
-        return self
-
-    def to(self, *args, **kwargs):
-        want_dev, want_dt = kwargs.get('device'), kwargs.get('dtype')
-        for a in args:
-            if isinstance(a, torch.dtype):
-                want_dt = a
-            elif a is not None:
-                want_dev = a
-        if want_dt is not None and want_dt != self.dtype:
-            raise NotImplementedError(f'{type(self).__name__}.to(dtype={want_dt}): the engine is packed in {self.dtype}; build a new one')
-        if want_dev is not None:
-            d = torch.device(want_dev)
-            same = d.type == self.device.type and (d.index is None or self.device.index is None or d.index == self.device.index)
-            if not same:
-                raise NotImplementedError(f'{type(self).__name__}.to(device={d}): the engine lives on {self.device}; build a new one')
-        return self
-
-
-class ResamplerEngine(_Surface):
+class ResamplerEngine(EngineHandle):
     """`Resampler(dim, depth, dim_head, heads, num_queries, embedding_dim, output_dim, ff_mult)` on the native executor."""
 
     def __init__(self, dim=1024, depth=8, dim_head=64, heads=16, num_queries=8, embedding_dim=768, output_dim=1024, ff_mult=4, dtype=torch.float16, device='cuda'):
@@ -61,15 +34,6 @@ class ResamplerEngine(_Surface):
         _lib.call('mve_ip_resampler_create', ctypes.byref(self._h), _dt(dtype), self.dim, self.depth, self.heads, self.num_queries, self.embedding_dim,
                   self.output_dim, self.ff_mult)
         self._ws = None
-
-    def __del__(self):
-        h = getattr(self, '_h', None)
-        if h:
-            try:
-                _lib.raw('mve_unet_destroy')(h)
-            except Exception:
-                pass
-            self._h = None
 
     @classmethod
     def from_module(cls, m, dtype=None, device=None):
@@ -106,30 +70,17 @@ class ResamplerEngine(_Surface):
             for name in own:
                 if name not in state_dict:
                     continue
-                t = state_dict[name].detach()
-                if t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-                    t = t.float()
-                t = t.to(self.device).contiguous()
-                shape = (ctypes.c_longlong * t.dim())(*t.shape)
-                _lib.call('mve_unet_load_param', self._h, name.encode(), _lib.ptr(t), _dt(t), t.dim(), shape, s)
+                self._push_param(name, state_dict[name], s)
             torch.cuda.current_stream(self.device).synchronize()
         return self
 
     def plan(self, B, n1):
         ws, n_ops, flops = ctypes.c_size_t(), ctypes.c_int(), (ctypes.c_double * 5)()
         _lib.call('mve_ip_resampler_plan', self._h, int(B), int(n1), ctypes.byref(ws), ctypes.byref(n_ops), flops)
-        return dict(workspace_bytes=ws.value, n_ops=n_ops.value, flops=dict(zip(OP_CLASSES, list(flops))))
+        return self._plan_result(ws, n_ops, flops)
 
     def op_table(self):
-        out, i = [], 0
-        cls, fl, lab = ctypes.c_int(), ctypes.c_double(), ctypes.create_string_buffer(96)
-        while True:
-            ph = _lib.raw('mve_unet_op_info')(self._h, i, ctypes.byref(cls), ctypes.byref(fl), lab, 96)
-            if ph < 0:
-                break
-            out.append((OP_CLASSES[cls.value], fl.value, lab.value.decode()))
-            i += 1
-        return out
+        return [row[1:] for row in self._op_rows()]
 
     def run(self, x, profile=False):
         if x.dim() != 3 or x.shape[-1] != self.embedding_dim or x.shape[0] == 0 or x.shape[1] == 0:
@@ -139,12 +90,10 @@ class ResamplerEngine(_Surface):
         x = x.to(device=dev, dtype=self.dtype).contiguous()
         with torch.cuda.device(dev):
             info = self.plan(B, n1)
-            if self._ws is None or self._ws.numel() < info['workspace_bytes']:
-                self._ws = None
-                self._ws = torch.empty(info['workspace_bytes'], dtype=torch.uint8, device=dev)
+            ws = self._workspace(info['workspace_bytes'])
             out = torch.empty(B, self.num_queries, self.output_dim, dtype=self.dtype, device=dev)
             op_ms = (ctypes.c_float * info['n_ops'])() if profile else None
-            _lib.call('mve_ip_resampler_forward', self._h, _lib.ptr(x), B, n1, _lib.ptr(out), _lib.ptr(self._ws), self._ws.numel(), op_ms, _lib.stream_ptr(dev))
+            _lib.call('mve_ip_resampler_forward', self._h, _lib.ptr(x), B, n1, _lib.ptr(out), _lib.ptr(ws), ws.numel(), op_ms, _lib.stream_ptr(dev))
         return (out, list(op_ms)) if profile else out
 
     def __call__(self, x):
@@ -153,7 +102,7 @@ class ResamplerEngine(_Surface):
     forward = __call__
 
 
-class ImageProjEngine(_Surface):
+class ImageProjEngine(InferenceSurface):
     """`ImageProjModel(cross_attention_dim, clip_embeddings_dim, clip_extra_context_tokens)`: mve_gemm (bias fused) + mve_layernorm."""
 
     def __init__(self, cross_attention_dim=1024, clip_embeddings_dim=1024, clip_extra_context_tokens=4, dtype=torch.float16, device='cuda'):

@@ -9,6 +9,7 @@ import ctypes
 import torch
 
 from . import _lib
+from .module_surface import EngineHandle
 from .ops import dt as _dt
 
 
@@ -45,21 +46,12 @@ class _LPIPSFn(torch.autograd.Function):
         return out.to(ctx.in_dtype), None, None
 
 
-class LPIPSEngine:
+class LPIPSEngine(EngineHandle):
     def __init__(self, dtype=torch.bfloat16, device='cuda', normalize_inputs=True):
         assert dtype in (torch.float16, torch.bfloat16)       # the reference runs the module in bf16 when the GPU has it (lpips_loss.py:31)
         self.dtype, self.device, self.normalize_inputs = dtype, torch.device(device), normalize_inputs
         self._h = ctypes.c_void_p()
         _lib.call('mve_lpips_create', ctypes.byref(self._h), _dt(dtype), int(normalize_inputs))
-
-    def __del__(self):
-        h = getattr(self, '_h', None)
-        if h:
-            try:
-                _lib.raw('mve_unet_destroy')(h)
-            except Exception:
-                pass
-            self._h = None
 
     @classmethod
     def from_state_dict(cls, state_dict, dtype=torch.bfloat16, device='cuda', normalize_inputs=True):
@@ -71,17 +63,11 @@ class LPIPSEngine:
             for name, t in state_dict.items():
                 if not name.startswith(('net.', 'lin', 'scaling_layer.')):
                     continue
-                t = t.detach()
-                if t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-                    t = t.float()
-                t = t.to(self.device).contiguous()
-                shape = (ctypes.c_longlong * t.dim())(*t.shape)
-                _lib.call('mve_unet_load_param', self._h, name.encode(), _lib.ptr(t), _dt(t), t.dim(), shape, s)
+                self._push_param(name, t, s)
             torch.cuda.current_stream(self.device).synchronize()
-        buf = ctypes.create_string_buffer(256)
-        missing = _lib.raw('mve_unet_missing_params')(self._h, buf, 256)
+        missing, first = self._missing_params()
         if strict and missing:
-            raise KeyError(f'{missing} LPIPS parameters missing from the state dict (first: {buf.value.decode()})')
+            raise KeyError(f'{missing} LPIPS parameters missing from the state dict (first: {first})')
         return self
 
     def plan(self, B, H, W, io_dtype=torch.float32):

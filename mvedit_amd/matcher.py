@@ -20,7 +20,7 @@ import math
 import torch
 
 from . import _lib
-from .module_surface import ModuleSurface
+from .module_surface import EngineHandle
 
 _DT = {torch.float16: 1, torch.bfloat16: 2}
 WINDOW = 5          # the fine window the kernels are written for (FINE_WINDOW_SIZE)
@@ -220,7 +220,6 @@ DEFAULT_CONFIG = dict(
     coarse=dict(d_model=256, d_ffn=256, nhead=8, layer_names=['self', 'cross'] * 4, attention='linear', temp_bug_fix=False),
     match_coarse=dict(thr=0.2, border_rm=2, match_type='dual_softmax', dsmax_temperature=0.1),
     fine=dict(d_model=128, d_ffn=128, nhead=8, layer_names=['self', 'cross'], attention='linear'))
-OP_CLASSES = ('conv', 'linear', 'attention', 'norm', 'other')
 COARSE_TAPS = ('stem', 'layer1', 'layer2', 'layer3', 'fpn_c', 'pos') + tuple(f'c{k}' for k in range(8))
 FINE_TAPS = ('unfold', 'merged', 'fine')
 _BLOCK_DIMS, _PADDED = (128, 196, 256), (128, 200, 256)      # the 196-wide stage runs as 200 channels, the last 4 zero
@@ -376,7 +375,7 @@ def pack_slots(params):
     return s
 
 
-class LoFTREngine(ModuleSurface):
+class LoFTREngine(EngineHandle):
     """`LoFTR(config=default_cfg)` (either `temp_bug_fix`) on the native executor: `engine(batch)` updates the reference's batch dict in place."""
 
     def __init__(self, config=None, dtype=torch.float16, device='cuda'):
@@ -390,15 +389,6 @@ class LoFTREngine(ModuleSurface):
         _lib.call('mve_loftr_create', ctypes.byref(self._h), _DT[dtype])
         self._ws, self._pos = None, {}
         self.training = False
-
-    def __del__(self):
-        h = getattr(self, '_h', None)
-        if h:
-            try:
-                _lib.raw('mve_loftr_destroy')(h)
-            except Exception:
-                pass
-            self._h = None
 
     @classmethod
     def from_module(cls, m, dtype=None, device=None):
@@ -426,58 +416,25 @@ class LoFTREngine(ModuleSurface):
                 shape = (ctypes.c_longlong * 1)(t.numel())
                 _lib.call('mve_unet_load_param', self._h, name.encode(), _lib.ptr(t), 0, 1, shape, s)
             torch.cuda.current_stream(self.device).synchronize()
-        buf = ctypes.create_string_buffer(256)
-        missing = _lib.raw('mve_unet_missing_params')(self._h, buf, 256)
+        missing, first = self._missing_params()
         if missing:
-            raise KeyError(f'{missing} LoFTR slots were not filled (first: {buf.value.decode()})')
+            raise KeyError(f'{missing} LoFTR slots were not filled (first: {first})')
         return self
 
     # ---- the nn.Module sliver the runner touches (`init_matcher().requires_grad_(False).to(device)`) ----------------------------------------------
-    def eval(self):
-        return self
-
     def train(self, mode=True):
         if mode:
             raise NotImplementedError('LoFTREngine.train(): the engine is inference only')
-        return self
-
-    def requires_grad_(self, requires_grad=False):
-        if requires_grad:
-            raise NotImplementedError('LoFTREngine.requires_grad_(True): the engine is inference only')
-        return self
-
-    def to(self, *args, **kwargs):
-        want_dev, want_dt = kwargs.get('device'), kwargs.get('dtype')
-        for a in args:
-            if isinstance(a, torch.dtype):
-                want_dt = a
-            elif a is not None:
-                want_dev = a
-        if want_dt is not None and want_dt != self.dtype:
-            raise NotImplementedError(f'LoFTREngine.to(dtype={want_dt}): the engine is packed in {self.dtype}; build a new one')
-        if want_dev is not None:
-            d = torch.device(want_dev)
-            same = d.type == self.device.type and (d.index is None or self.device.index is None or d.index == self.device.index)
-            if not same:
-                raise NotImplementedError(f'LoFTREngine.to(device={d}): the engine lives on {self.device}; build a new one')
         return self
 
     # ---- planning -------------------------------------------------------------------------------------------------------------------------------
     def plan(self, N, H, W, phase=1):
         ws, n_ops, flops = ctypes.c_size_t(), ctypes.c_int(), (ctypes.c_double * 5)()
         _lib.call('mve_loftr_plan', self._h, int(phase), int(N), int(H), int(W), ctypes.byref(ws), ctypes.byref(n_ops), flops)
-        return dict(workspace_bytes=ws.value, n_ops=n_ops.value, flops=dict(zip(OP_CLASSES, list(flops))))
+        return self._plan_result(ws, n_ops, flops)
 
     def op_table(self):
-        out, i = [], 0
-        cls, fl, lab = ctypes.c_int(), ctypes.c_double(), ctypes.create_string_buffer(96)
-        while True:
-            ph = _lib.raw('mve_unet_op_info')(self._h, i, ctypes.byref(cls), ctypes.byref(fl), lab, 96)
-            if ph < 0:
-                break
-            out.append((OP_CLASSES[cls.value], fl.value, lab.value.decode()))
-            i += 1
-        return out
+        return [row[1:] for row in self._op_rows()]
 
     # ---- forward ----------------------------------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -493,12 +450,6 @@ class LoFTREngine(ModuleSurface):
         if H // 8 > MAX_GRID or W // 8 > MAX_GRID:
             raise ValueError(f'a {H // 8} x {W // 8} coarse grid exceeds the {MAX_GRID} x {MAX_GRID} position table')
         return N, H, W
-
-    def _workspace(self, nbytes):
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = None
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        return self._ws
 
     def _table(self, hc, wc):
         if (hc, wc) not in self._pos:

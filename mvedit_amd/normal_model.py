@@ -21,8 +21,7 @@ import torch
 
 from . import _lib
 from .ops import dt as _dt
-from .module_surface import ModuleSurface
-from .text_encoder import OP_CLASSES
+from .module_surface import EngineHandle
 
 CONFIG_FIELDS = ('image_size', 'stem_width', 'stage_widths', 'stage_depths', 'num_groups', 'hidden_size', 'num_layers', 'num_heads', 'intermediate_size',
                  'tap_layers', 'neck_channels', 'features', 'num_channels', 'layer_norm_eps', 'readout', 'backbone')
@@ -258,7 +257,7 @@ def reference_module_config(m):
                 layer_norm_eps=float(vit.blocks[0].norm1.eps), readout='project', backbone='vitb_rn50_384')
 
 
-class DPTNormalEngine(ModuleSurface):
+class DPTNormalEngine(EngineHandle):
     """`DPTDepthModel(backbone='vitb_rn50_384', num_channels=N)` on the native executor: [B, 3, S, S] -> [B, N, S, S] (dimension 1 squeezed when N == 1)."""
 
     def __init__(self, config=None, dtype=torch.float16, device='cuda'):
@@ -281,15 +280,6 @@ class DPTNormalEngine(ModuleSurface):
                   i2(*c['neck_channels']), int(c['features']), int(c['num_channels']), float(c['layer_norm_eps']))
         self.num_tokens = (c['image_size'] // 16) ** 2 + 1
         self._ws = None
-
-    def __del__(self):
-        h = getattr(self, '_h', None)
-        if h:
-            try:
-                _lib.raw('mve_unet_destroy')(h)
-            except Exception:
-                pass
-            self._h = None
 
     @classmethod
     def from_module(cls, m, dtype=None, device=None):
@@ -318,58 +308,21 @@ class DPTNormalEngine(ModuleSurface):
             s = _lib.stream_ptr(self.device)
             keep = []
             for name, t in slots.items():
-                t = t.to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()      # a slot is a flat run of its size (a conv's K order has 5 axes)
-                keep.append(t)
-                shape = (ctypes.c_longlong * t.dim())(*t.shape)
-                _lib.call('mve_unet_load_param', self._h, name.encode(), _lib.ptr(t), _dt(t), t.dim(), shape, s)
+                keep.append(self._push_param(name, t.to(dtype=torch.float32).reshape(-1), s))      # a slot is a flat run of its size (a conv's K order has 5 axes)
             torch.cuda.current_stream(self.device).synchronize()
-        buf = ctypes.create_string_buffer(256)
-        missing = _lib.raw('mve_unet_missing_params')(self._h, buf, 256)
+        missing, first = self._missing_params()
         if missing:
-            raise KeyError(f'{missing} DPT slots were not filled (first: {buf.value.decode()})')
-        return self
-
-    # ---- the nn.Module sliver the pipelines touch ---------------------------------------------------------------------------------------
-    def eval(self):
-        return self
-
-    def requires_grad_(self, requires_grad=False):
-        if requires_grad:
-            raise NotImplementedError('DPTNormalEngine.requires_grad_(True): the engine is inference only')
-        return self
-
-    def to(self, *args, **kwargs):
-        want_dev, want_dt = kwargs.get('device'), kwargs.get('dtype')
-        for a in args:
-            if isinstance(a, torch.dtype):
-                want_dt = a
-            elif a is not None:
-                want_dev = a
-        if want_dt is not None and want_dt != self.dtype:
-            raise NotImplementedError(f'DPTNormalEngine.to(dtype={want_dt}): the engine is packed in {self.dtype}; build a new one')
-        if want_dev is not None:
-            d = torch.device(want_dev)
-            same = d.type == self.device.type and (d.index is None or self.device.index is None or d.index == self.device.index)
-            if not same:
-                raise NotImplementedError(f'DPTNormalEngine.to(device={d}): the engine lives on {self.device}; build a new one')
+            raise KeyError(f'{missing} DPT slots were not filled (first: {first})')
         return self
 
     # ---- planning / profiling -----------------------------------------------------------------------------------------------------------
     def plan(self, B):
         ws, n_ops, flops = ctypes.c_size_t(), ctypes.c_int(), (ctypes.c_double * 5)()
         _lib.call('mve_dpt_plan', self._h, int(B), ctypes.byref(ws), ctypes.byref(n_ops), flops)
-        return dict(workspace_bytes=ws.value, n_ops=n_ops.value, flops=dict(zip(OP_CLASSES, list(flops))))
+        return self._plan_result(ws, n_ops, flops)
 
     def op_table(self):
-        out, i = [], 0
-        cls, fl, lab = ctypes.c_int(), ctypes.c_double(), ctypes.create_string_buffer(96)
-        while True:
-            ph = _lib.raw('mve_unet_op_info')(self._h, i, ctypes.byref(cls), ctypes.byref(fl), lab, 96)
-            if ph < 0:
-                break
-            out.append((OP_CLASSES[cls.value], fl.value, lab.value.decode()))
-            i += 1
-        return out
+        return [row[1:] for row in self._op_rows()]
 
     # ---- forward ------------------------------------------------------------------------------------------------------------------------
     def _check_input(self, x):
@@ -400,14 +353,12 @@ class DPTNormalEngine(ModuleSurface):
         x = x.to(device=dev, dtype=self.dtype).contiguous()
         with torch.cuda.device(dev):
             info = self.plan(B)
-            if self._ws is None or self._ws.numel() < info['workspace_bytes']:
-                self._ws = None
-                self._ws = torch.empty(info['workspace_bytes'], dtype=torch.uint8, device=dev)
+            ws = self._workspace(info['workspace_bytes'])
             out = torch.empty(B, nc, S, S, dtype=self.dtype, device=dev)
             taps = [torch.empty(s, dtype=self.dtype, device=dev) for s in self._tap_shapes(B)] if output_features else None
             tp = (ctypes.c_void_p * len(TAP_NAMES))(*[t.data_ptr() for t in taps]) if taps else None
             op_ms = (ctypes.c_float * info['n_ops'])() if profile else None
-            _lib.call('mve_dpt_forward', self._h, _lib.ptr(x), B, _lib.ptr(out), tp, _lib.ptr(self._ws), self._ws.numel(), op_ms, _lib.stream_ptr(dev))
+            _lib.call('mve_dpt_forward', self._h, _lib.ptr(x), B, _lib.ptr(out), tp, _lib.ptr(ws), ws.numel(), op_ms, _lib.stream_ptr(dev))
         out = out.squeeze(1) if nc == 1 else out              # DPTDepthModel.forward: `.squeeze(dim=1)`
         res = out
         if output_features:

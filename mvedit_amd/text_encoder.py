@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from .ops import dt as _dt
-from .module_surface import ModuleSurface
+from .module_surface import EngineHandle
 
 OP_CLASSES = ('conv', 'linear', 'attention', 'norm', 'other')
 ACTS = {'quick_gelu': 0, 'gelu': 1}
@@ -92,7 +92,7 @@ class _FinalLayerNorm:
     forward = __call__
 
 
-class CLIPTextEngine(ModuleSurface):
+class CLIPTextEngine(EngineHandle):
     """`CLIPTextModel` (with_projection=False) or `CLIPTextModelWithProjection` (True) on the native executor."""
 
     def __init__(self, config, dtype=torch.float16, device='cuda', with_projection=False):
@@ -110,15 +110,6 @@ class CLIPTextEngine(ModuleSurface):
                   self.projection_dim)
         self._ws = None
         self.text_model = SimpleNamespace(final_layer_norm=_FinalLayerNorm(self), config=self.config)
-
-    def __del__(self):
-        h = getattr(self, '_h', None)
-        if h:
-            try:
-                _lib.raw('mve_unet_destroy')(h)
-            except Exception:
-                pass
-            self._h = None
 
     @classmethod
     def from_module(cls, m, dtype=None, device=None):
@@ -160,57 +151,23 @@ class CLIPTextEngine(ModuleSurface):
             for name, t in state_dict.items():
                 if name not in own:              # buffers (`text_model.embeddings.position_ids`), a projection the plain model does not use
                     continue
-                t = t.detach()
-                if t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-                    t = t.float()
-                t = t.to(self.device).contiguous()
-                shape = (ctypes.c_longlong * t.dim())(*t.shape)
-                _lib.call('mve_unet_load_param', self._h, name.encode(), _lib.ptr(t), _dt(t), t.dim(), shape, s)
+                t = self._push_param(name, t, s)
                 if name.startswith('text_model.final_layer_norm.'):
                     setattr(self.text_model.final_layer_norm, name.rsplit('.', 1)[1], t.float())
             torch.cuda.current_stream(self.device).synchronize()
-        buf = ctypes.create_string_buffer(256)
-        missing = _lib.raw('mve_unet_missing_params')(self._h, buf, 256)
+        missing, first = self._missing_params()
         if strict and missing:
-            raise KeyError(f'{missing} CLIP text parameters missing from the state dict (first: {buf.value.decode()})')
-        return self
-
-    # ---- the nn.Module sliver the pipelines touch ---------------------------------------------------------------------------------------
-    def eval(self):
-        return self
-
-    def to(self, *args, **kwargs):
-        want_dev, want_dt = kwargs.get('device'), kwargs.get('dtype')
-        for a in args:
-            if isinstance(a, torch.dtype):
-                want_dt = a
-            elif a is not None:
-                want_dev = a
-        if want_dt is not None and want_dt != self.dtype:
-            raise NotImplementedError(f'CLIPTextEngine.to(dtype={want_dt}): the engine is packed in {self.dtype}; build a new one')
-        if want_dev is not None:
-            d = torch.device(want_dev)
-            same = d.type == self.device.type and (d.index is None or self.device.index is None or d.index == self.device.index)
-            if not same:
-                raise NotImplementedError(f'CLIPTextEngine.to(device={d}): the engine lives on {self.device}; build a new one')
+            raise KeyError(f'{missing} CLIP text parameters missing from the state dict (first: {first})')
         return self
 
     # ---- planning / profiling -----------------------------------------------------------------------------------------------------------
     def plan(self, B, L):
         ws, n_ops, flops = ctypes.c_size_t(), ctypes.c_int(), (ctypes.c_double * 5)()
         _lib.call('mve_clip_text_plan', self._h, int(B), int(L), ctypes.byref(ws), ctypes.byref(n_ops), flops)
-        return dict(workspace_bytes=ws.value, n_ops=n_ops.value, flops=dict(zip(OP_CLASSES, list(flops))))
+        return self._plan_result(ws, n_ops, flops)
 
     def op_table(self):
-        out, i = [], 0
-        cls, fl, lab = ctypes.c_int(), ctypes.c_double(), ctypes.create_string_buffer(96)
-        while True:
-            ph = _lib.raw('mve_unet_op_info')(self._h, i, ctypes.byref(cls), ctypes.byref(fl), lab, 96)
-            if ph < 0:
-                break
-            out.append((OP_CLASSES[cls.value], fl.value, lab.value.decode()))
-            i += 1
-        return out
+        return [row[1:] for row in self._op_rows()]
 
     # ---- forward ------------------------------------------------------------------------------------------------------------------------
     def _check_ids(self, input_ids):
@@ -237,9 +194,7 @@ class CLIPTextEngine(ModuleSurface):
         ids32 = ids.to(device=dev, dtype=torch.int32).contiguous()
         with torch.cuda.device(dev):
             info = self.plan(B, L)
-            if self._ws is None or self._ws.numel() < info['workspace_bytes']:
-                self._ws = None
-                self._ws = torch.empty(info['workspace_bytes'], dtype=torch.uint8, device=dev)
+            ws = self._workspace(info['workspace_bytes'])
             last = torch.empty(B, L, C, dtype=self.dtype, device=dev)
             pooled = torch.empty(B, C, dtype=self.dtype, device=dev)
             embeds = torch.empty(B, self.projection_dim, dtype=self.dtype, device=dev) if self.projection_dim else None
@@ -247,7 +202,7 @@ class CLIPTextEngine(ModuleSurface):
             hs = (ctypes.c_void_p * n_hidden)(*[h.data_ptr() for h in hidden]) if hidden else None
             op_ms = (ctypes.c_float * info['n_ops'])() if profile else None
             _lib.call('mve_clip_text_forward', self._h, _lib.ptr(ids32), B, L, int(c['eos_token_id']), _lib.ptr(last), _lib.ptr(pooled), _lib.ptr(embeds), hs,
-                      _lib.ptr(self._ws), self._ws.numel(), op_ms, _lib.stream_ptr(dev))
+                      _lib.ptr(ws), ws.numel(), op_ms, _lib.stream_ptr(dev))
         res = (last, pooled, embeds, hidden)
         return res + (list(op_ms),) if profile else res
 

@@ -18,7 +18,7 @@ import torch
 
 from . import _lib
 from .attn_processors import AttnProcessorTable, attn_processor_names
-from .module_surface import ModuleSurface
+from .module_surface import EngineHandle
 from .ops import dt as _dt
 
 SD15_CONFIG = dict(
@@ -79,7 +79,9 @@ def config_from_diffusers(cfg):
                 norm_eps=g('norm_eps'), transformer_layers=tl, use_linear_projection=bool(g('use_linear_projection', False)), **extra)
 
 
-class UNet2DConditionEngine(AttnProcessorTable, ModuleSurface):
+class UNet2DConditionEngine(AttnProcessorTable, EngineHandle):
+    OP_CLASSES = OP_CLASSES
+
     def __init__(self, config=None, dtype=torch.float16, device='cuda'):
         self.cfg = dict(config or SD15_CONFIG)
         assert dtype in (torch.float16, torch.bfloat16)
@@ -144,15 +146,6 @@ class UNet2DConditionEngine(AttnProcessorTable, ModuleSurface):
         self._ack_keep = (text, ids)
         _lib.call('mve_unet_bind_added_cond', self._h, _lib.ptr(text), _dt(text), text.shape[1], _lib.ptr(ids), ids.shape[1], B)
 
-    def __del__(self):
-        h = getattr(self, '_h', None)
-        if h:
-            try:
-                _lib.raw('mve_unet_destroy')(h)
-            except Exception:
-                pass
-            self._h = None
-
     def set_residual_pair(self, flag=True):
         """Carry the residual stream (x + f(x) of ResnetBlock2D / BasicTransformerBlock / Transformer2DModel) as an unrounded pair -- the 16-bit tensor
         every matrix-core operand read sees plus an 8-bit E5M2 remainder (lo8, csrc/common.h) -- instead of rounding it after every block as the
@@ -200,18 +193,12 @@ class UNet2DConditionEngine(AttnProcessorTable, ModuleSurface):
         with torch.cuda.device(self.device):
             s = _lib.stream_ptr(self.device)
             for name, t in state_dict.items():
-                t = t.detach()
-                if t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-                    t = t.float()
-                t = t.to(self.device).contiguous()
-                shape = (ctypes.c_longlong * t.dim())(*t.shape)
-                _lib.call('mve_unet_load_param', self._h, name.encode(), _lib.ptr(t), _dt(t), t.dim(), shape, s)
+                self._push_param(name, t, s)
             torch.cuda.current_stream(self.device).synchronize()   # source tensors may die after return
         if strict:
-            buf = ctypes.create_string_buffer(256)
-            missing = _lib.raw('mve_unet_missing_params')(self._h, buf, 256)
+            missing, first = self._missing_params()
             if missing:
-                raise KeyError(f'{missing} UNet parameters missing from the state dict (first: {buf.value.decode()})')
+                raise KeyError(f'{missing} UNet parameters missing from the state dict (first: {first})')
         return self
 
     # ------------------------------------------------------------------ attention processors
@@ -229,13 +216,8 @@ class UNet2DConditionEngine(AttnProcessorTable, ModuleSurface):
 
     def _attn_push(self, name, tensor):
         """One to_k_ip / to_v_ip weight of an installed IPAttnProcessor into the executor (stream-ordered: no synchronisation)."""
-        t = tensor.detach()
-        if t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-            t = t.float()
-        t = t.to(self.device).contiguous()
-        shape = (ctypes.c_longlong * t.dim())(*t.shape)
         with torch.cuda.device(self.device):
-            _lib.call('mve_unet_load_param', self._h, name.encode(), _lib.ptr(t), _dt(t), t.dim(), shape, _lib.stream_ptr(self.device))
+            self._push_param(name, tensor, _lib.stream_ptr(self.device))
 
     def _set_attention(self, cak, B, H, W, ctx_len=None):
         """Translate the reference's cross_attention_kwargs (mode / ref_dict / is_cfg_guidance) into engine state.  The
@@ -282,27 +264,13 @@ class UNet2DConditionEngine(AttnProcessorTable, ModuleSurface):
         flops = (ctypes.c_double * 5)()
         _lib.call('mve_unet_plan', self._h, B, H, W, ctx_len, num_cross_attn_imgs, int(has_residuals),
                   _dt(io_dtype or self.dtype), int(residuals_nhwc), ctypes.byref(ws), ctypes.byref(n_ops), flops)
-        return dict(workspace_bytes=ws.value, n_ops=n_ops.value, flops=dict(zip(OP_CLASSES, list(flops))))
+        return self._plan_result(ws, n_ops, flops)
 
     def op_table(self):
         """[(phase, class, flops, label)] of the currently cached plan."""
-        out, i = [], 0
-        cls, fl, lab = ctypes.c_int(), ctypes.c_double(), ctypes.create_string_buffer(96)
-        while True:
-            ph = _lib.raw('mve_unet_op_info')(self._h, i, ctypes.byref(cls), ctypes.byref(fl), lab, 96)
-            if ph < 0:
-                break
-            out.append((ph, OP_CLASSES[cls.value], fl.value, lab.value.decode()))
-            i += 1
-        return out
+        return list(self._op_rows())
 
     # ------------------------------------------------------------------ execution
-    def _workspace(self, nbytes):
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = None
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        return self._ws
-
     def _run(self, phase, sample, timestep, ctx, n_img, down_res, mid_res, out, profile=False, workspace=None,
              residuals_nhwc=False, shape=None):
         B, _, H, W = shape if shape is not None else sample.shape

@@ -15,11 +15,10 @@ import torch
 
 from . import _lib
 from .ops import dt as _dt
-from .module_surface import ModuleSurface
+from .module_surface import EngineHandle, ModuleSurface
 
 SD_VAE_CONFIG = dict(in_channels=3, out_channels=3, latent_channels=4, block_out_channels=(128, 256, 512, 512), layers_per_block=2,
                      norm_num_groups=32, scaling_factor=0.18215)
-OP_CLASSES = ('conv', 'linear', 'attention', 'norm', 'other')
 
 
 class DiagonalGaussianDistribution:
@@ -40,7 +39,7 @@ class DiagonalGaussianDistribution:
         return self.mean
 
 
-class _Half:
+class _Half(EngineHandle):
     """One native engine: the decoder (+ post_quant_conv) or the encoder (+ quant_conv)."""
 
     def __init__(self, half, cfg, dtype, device):
@@ -54,15 +53,6 @@ class _Half:
                   int(cfg['layers_per_block']), int(cfg['norm_num_groups']), 1e-6)
         self._ws = None
 
-    def __del__(self):
-        h = getattr(self, '_h', None)
-        if h:
-            try:
-                _lib.raw('mve_unet_destroy')(h)
-            except Exception:
-                pass
-            self._h = None
-
     def load(self, state_dict):
         own = ('decoder.', 'post_quant_conv.') if self.half == 1 else ('encoder.', 'quant_conv.')
         with torch.cuda.device(self.device):
@@ -70,17 +60,11 @@ class _Half:
             for name, t in state_dict.items():
                 if not name.startswith(own):
                     continue
-                t = t.detach()
-                if t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-                    t = t.float()
-                t = t.to(self.device).contiguous()
-                shape = (ctypes.c_longlong * t.dim())(*t.shape)
-                _lib.call('mve_unet_load_param', self._h, name.encode(), _lib.ptr(t), _dt(t), t.dim(), shape, s)
+                self._push_param(name, t, s)
             torch.cuda.current_stream(self.device).synchronize()
-        buf = ctypes.create_string_buffer(256)
-        missing = _lib.raw('mve_unet_missing_params')(self._h, buf, 256)
+        missing, first = self._missing_params()
         if missing:
-            raise KeyError(f'{missing} VAE parameters missing from the state dict (first: {own[0]}{buf.value.decode()})')
+            raise KeyError(f'{missing} VAE parameters missing from the state dict (first: {own[0]}{first})')
 
     def max_batch(self, H, W):
         """Largest batch whose widest image-resolution activation stays below 2^31 elements (32-bit indexing in the conv kernels)."""
@@ -92,18 +76,10 @@ class _Half:
     def plan(self, B, H, W, io_dtype):
         ws, n_ops, flops = ctypes.c_size_t(), ctypes.c_int(), (ctypes.c_double * 5)()
         _lib.call('mve_vae_plan', self._h, B, H, W, _dt(io_dtype), ctypes.byref(ws), ctypes.byref(n_ops), flops)
-        return dict(workspace_bytes=ws.value, n_ops=n_ops.value, flops=dict(zip(OP_CLASSES, list(flops))))
+        return self._plan_result(ws, n_ops, flops)
 
     def op_table(self):
-        out, i = [], 0
-        cls, fl, lab = ctypes.c_int(), ctypes.c_double(), ctypes.create_string_buffer(96)
-        while True:
-            ph = _lib.raw('mve_unet_op_info')(self._h, i, ctypes.byref(cls), ctypes.byref(fl), lab, 96)
-            if ph < 0:
-                break
-            out.append((OP_CLASSES[cls.value], fl.value, lab.value.decode()))
-            i += 1
-        return out
+        return [row[1:] for row in self._op_rows()]
 
     def run(self, x, max_batch=None, profile=False):
         assert x.dim() == 4 and x.shape[1] == self.cin, (tuple(x.shape), self.cin)
@@ -122,12 +98,10 @@ class _Half:
             for b0 in range(0, B, step):       # the reference itself decodes `diff_bs` views at a time (mvedit_3d_pipeline.py:1259)
                 nb = min(step, B - b0)
                 info = self.plan(nb, H, W, io)
-                if self._ws is None or self._ws.numel() < info['workspace_bytes']:
-                    self._ws = None
-                    self._ws = torch.empty(info['workspace_bytes'], dtype=torch.uint8, device=self.device)
                 op_ms = (ctypes.c_float * info['n_ops'])() if profile else None
-                _lib.call('mve_vae_forward', self._h, _lib.ptr(x[b0:b0 + nb]), _dt(io), nb, H, W, _lib.ptr(out[b0:b0 + nb]), _lib.ptr(self._ws),
-                          self._ws.numel(), op_ms, _lib.stream_ptr(self.device))
+                ws = self._workspace(info['workspace_bytes'])
+                _lib.call('mve_vae_forward', self._h, _lib.ptr(x[b0:b0 + nb]), _dt(io), nb, H, W, _lib.ptr(out[b0:b0 + nb]), _lib.ptr(ws),
+                          ws.numel(), op_ms, _lib.stream_ptr(self.device))
                 if profile:
                     prof.append([(c, lab, fl, m) for (c, fl, lab), m in zip(self.op_table(), list(op_ms))])
         return (out, prof) if profile else out

@@ -16,8 +16,8 @@ import torch
 
 from . import _lib
 from .ops import dt as _dt
-from .module_surface import ModuleSurface
-from .text_encoder import ACTS, OP_CLASSES, CLIPTextOutput
+from .module_surface import EngineHandle
+from .text_encoder import ACTS, CLIPTextOutput
 
 CONFIG_FIELDS = ('hidden_size', 'intermediate_size', 'num_hidden_layers', 'num_attention_heads', 'image_size', 'patch_size', 'hidden_act', 'layer_norm_eps',
                  'projection_dim', 'num_channels')
@@ -42,7 +42,7 @@ def _config_dict(config):
     return cfg
 
 
-class CLIPVisionEngine(ModuleSurface):
+class CLIPVisionEngine(EngineHandle):
     """`CLIPVisionModelWithProjection` (with_projection=True) or `CLIPVisionModel` (False) on the native executor."""
 
     def __init__(self, config, dtype=torch.float16, device='cuda', with_projection=True):
@@ -62,15 +62,6 @@ class CLIPVisionEngine(ModuleSurface):
                   self.projection_dim)
         self.num_tokens = (int(c['image_size']) // int(c['patch_size'])) ** 2 + 1
         self._ws = None
-
-    def __del__(self):
-        h = getattr(self, '_h', None)
-        if h:
-            try:
-                _lib.raw('mve_unet_destroy')(h)
-            except Exception:
-                pass
-            self._h = None
 
     @classmethod
     def from_module(cls, m, dtype=None, device=None):
@@ -114,60 +105,21 @@ class CLIPVisionEngine(ModuleSurface):
             for name, t in state_dict.items():
                 if name not in own:              # buffers (`vision_model.embeddings.position_ids`), a projection the plain model does not use
                     continue
-                t = t.detach()
-                if t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-                    t = t.float()
-                t = t.to(self.device).contiguous()
-                shape = (ctypes.c_longlong * t.dim())(*t.shape)
-                _lib.call('mve_unet_load_param', self._h, name.encode(), _lib.ptr(t), _dt(t), t.dim(), shape, s)
+                self._push_param(name, t, s)
             torch.cuda.current_stream(self.device).synchronize()
-        buf = ctypes.create_string_buffer(256)
-        missing = _lib.raw('mve_unet_missing_params')(self._h, buf, 256)
+        missing, first = self._missing_params()
         if strict and missing:
-            raise KeyError(f'{missing} CLIP vision parameters missing from the state dict (first: {buf.value.decode()})')
-        return self
-
-    # ---- the nn.Module sliver the pipelines touch ---------------------------------------------------------------------------------------
-    def eval(self):
-        return self
-
-    def requires_grad_(self, requires_grad=False):
-        if requires_grad:
-            raise NotImplementedError('CLIPVisionEngine.requires_grad_(True): the engine is inference only')
-        return self
-
-    def to(self, *args, **kwargs):
-        want_dev, want_dt = kwargs.get('device'), kwargs.get('dtype')
-        for a in args:
-            if isinstance(a, torch.dtype):
-                want_dt = a
-            elif a is not None:
-                want_dev = a
-        if want_dt is not None and want_dt != self.dtype:
-            raise NotImplementedError(f'CLIPVisionEngine.to(dtype={want_dt}): the engine is packed in {self.dtype}; build a new one')
-        if want_dev is not None:
-            d = torch.device(want_dev)
-            same = d.type == self.device.type and (d.index is None or self.device.index is None or d.index == self.device.index)
-            if not same:
-                raise NotImplementedError(f'CLIPVisionEngine.to(device={d}): the engine lives on {self.device}; build a new one')
+            raise KeyError(f'{missing} CLIP vision parameters missing from the state dict (first: {first})')
         return self
 
     # ---- planning / profiling -----------------------------------------------------------------------------------------------------------
     def plan(self, B):
         ws, n_ops, flops = ctypes.c_size_t(), ctypes.c_int(), (ctypes.c_double * 5)()
         _lib.call('mve_clip_vision_plan', self._h, int(B), ctypes.byref(ws), ctypes.byref(n_ops), flops)
-        return dict(workspace_bytes=ws.value, n_ops=n_ops.value, flops=dict(zip(OP_CLASSES, list(flops))))
+        return self._plan_result(ws, n_ops, flops)
 
     def op_table(self):
-        out, i = [], 0
-        cls, fl, lab = ctypes.c_int(), ctypes.c_double(), ctypes.create_string_buffer(96)
-        while True:
-            ph = _lib.raw('mve_unet_op_info')(self._h, i, ctypes.byref(cls), ctypes.byref(fl), lab, 96)
-            if ph < 0:
-                break
-            out.append((OP_CLASSES[cls.value], fl.value, lab.value.decode()))
-            i += 1
-        return out
+        return [row[1:] for row in self._op_rows()]
 
     # ---- forward ------------------------------------------------------------------------------------------------------------------------
     def _check_pixels(self, pixel_values):
@@ -190,17 +142,15 @@ class CLIPVisionEngine(ModuleSurface):
         px = px.to(device=dev, dtype=self.dtype).contiguous()
         with torch.cuda.device(dev):
             info = self.plan(B)
-            if self._ws is None or self._ws.numel() < info['workspace_bytes']:
-                self._ws = None
-                self._ws = torch.empty(info['workspace_bytes'], dtype=torch.uint8, device=dev)
+            ws = self._workspace(info['workspace_bytes'])
             last = torch.empty(B, T, C, dtype=self.dtype, device=dev)
             pooled = torch.empty(B, C, dtype=self.dtype, device=dev)
             embeds = torch.empty(B, self.projection_dim, dtype=self.dtype, device=dev) if self.projection_dim else None
             hidden = tuple(torch.empty(B, T, C, dtype=self.dtype, device=dev) for _ in range(n_hidden)) if output_hidden_states else None
             hs = (ctypes.c_void_p * n_hidden)(*[h.data_ptr() for h in hidden]) if hidden else None
             op_ms = (ctypes.c_float * info['n_ops'])() if profile else None
-            _lib.call('mve_clip_vision_forward', self._h, _lib.ptr(px), B, _lib.ptr(last), _lib.ptr(pooled), _lib.ptr(embeds), hs, _lib.ptr(self._ws),
-                      self._ws.numel(), op_ms, _lib.stream_ptr(dev))
+            _lib.call('mve_clip_vision_forward', self._h, _lib.ptr(px), B, _lib.ptr(last), _lib.ptr(pooled), _lib.ptr(embeds), hs, _lib.ptr(ws),
+                      ws.numel(), op_ms, _lib.stream_ptr(dev))
         res = (last, pooled, embeds, hidden)
         return res + (list(op_ms),) if profile else res
 

@@ -54,9 +54,10 @@ def test_engine_call_checks(L):
     """Calls on a handle of the wrong kind, with parameters missing, or with a latent size the topology cannot take."""
     lib, p, _ = L
     arr = lambda *v: (ctypes.c_int * len(v))(*v)
-    vae, sr = ctypes.c_void_p(), ctypes.c_void_p()
+    vae, sr, clip = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
     lib.call('mve_vae_create', ctypes.byref(vae), 1, 1, 4, 3, 2, arr(64, 128), 1, 32, 1e-6)
     lib.call('mve_srvgg_create', ctypes.byref(sr), 1, 3, 3, 64, 2, 4)
+    lib.call('mve_clip_text_create', ctypes.byref(clip), 1, 512, 77, 128, 2, 2, 512, 0, ctypes.c_float(1e-5), 0)
     try:
         ws, n = ctypes.c_size_t(), ctypes.c_int()
         _bad(lib, 'mve_srvgg_plan', vae, 1, 8, 8, 1, ctypes.byref(ws), ctypes.byref(n), None, match='SRVGG')
@@ -65,9 +66,13 @@ def test_engine_call_checks(L):
         _bad(lib, 'mve_vae_plan', vae, 1, 3, 5, 1, ctypes.byref(ws), ctypes.byref(n), None, match='multiple of 8')
         _bad(lib, 'mve_unet_forward', vae, 0, p, 1, p, p, 1, 8, 8, 77, 1, None, None, 0, p, p, 1 << 20, None, None, match='VAE')
         _bad(lib, 'mve_controlnet_forward', vae, p, 1, p, p, p, 1, 8, 8, 77, 1.0, 0, None, p, 1 << 20, None, None, match='ControlNet')
+        _bad(lib, 'mve_unet_tune_cfg_prefix', clip, 1, match='a UNet handle is needed')                 # the denoisers' switches and plan: every other kind is refused
+        _bad(lib, 'mve_unet_set_context_tail', clip, 1, match='a UNet / ControlNet handle is needed')
+        _bad(lib, 'mve_unet_plan', vae, 1, 8, 8, 77, 1, 0, 1, 0, ctypes.byref(ws), ctypes.byref(n), None, match='VAE')
     finally:
         lib.raw('mve_unet_destroy')(vae)
         lib.raw('mve_unet_destroy')(sr)
+        lib.raw('mve_unet_destroy')(clip)
 
 
 def test_render_and_mesh_argument_checks(L):
