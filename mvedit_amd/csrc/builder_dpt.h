@@ -14,52 +14,23 @@ namespace {
 // it is a plain GEMM / conv here.  Dense GEMMs never split K (rows_img = 0).
 constexpr int DPT_TAPS = 10;
 
+// parameter names and labels of Builder::encoder_layer in the packed ViT scheme of mvedit_amd/normal_model.py
+constexpr Builder::EncoderNames DPT_ENCODER = {".n1", ".qkv", ".o", ".n2", ".fc1", ".fc2", "attn.qkv", "attn.proj+residual"};
+
 int Builder::build_dpt(int B_) {
-    B = B_; dt = c.dtype;
-    pl = Plan();
-    const int S = c.dp_image, e = 2, d = dt, Bn = B_, C = c.ch[0], heads = c.heads[0], hd = C / heads, I = c.dp_inter, F = c.dp_features;
+    const int S = c.dp_image, e = 2, Bn = B_, C = c.ch[0], I = c.dp_inter, F = c.dp_features;
     const int Gd = S / 16, G2 = Gd * Gd, T = G2 + 1, M = Bn * T, Cs = c.dp_stem, NC = c.out_ch;
-    pl.B = B_; pl.H = S; pl.W = S; pl.n_img = 1; pl.io_dtype = c.dtype;
-    const float eps = c.eps, gn_eps = 1e-5f /* BitGroupNormActivation's default */, scale = 1.0f / sqrtf((float)hd);
+    begin(B_, S, S, 1, c.dtype);
+    const int d = dt;
+    const float gn_eps = 1e-5f;      // BitGroupNormActivation's default
     MVE_CHECK((size_t)Bn * S * S * 32 < ((size_t)1 << 31) && (size_t)Bn * (S / 2) * (S / 2) * 152 < ((size_t)1 << 31) &&
                   (size_t)Bn * (S / 2) * (S / 2) * (size_t)(F > Cs ? F : Cs) < ((size_t)1 << 31) && (size_t)M * (size_t)(I > 3 * C ? I : 3 * C) < ((size_t)1 << 31),
               MVE_ERR_ARG, "dpt: batch %d overflows 32-bit activation indexing", Bn);
-    ld_temb = 0; ld_kv = 0;
-    rows_img = 0;
-    Ref px; px.kind = Ref::SAMPLE;
-    Ref out; out.kind = Ref::OUT;
-    auto tap = [&](Ref x, size_t bytes, int k, const char* what) {      // copied out only when the caller gave a tensor for it
-        live(x, what);
-        op(OC_OTHER, 0, what, [=](const Run& r) {
-            void* dst = r.cn_out ? r.cn_out[k] : nullptr;
-            if (!dst) return (int)MVE_OK;
-            return hipMemcpyAsync(dst, r.p(x), bytes, hipMemcpyDeviceToDevice, r.stream) == hipSuccess ? (int)MVE_OK : (int)MVE_ERR_HIP;
-        });
-    };
+    const Ref px = arg(Ref::SAMPLE);
     auto norm = [&](Ref x, int Cx, int HW, const std::string& n, int act, const char* what) {      // GroupNorm (+ ReLU: selector 2) -> new buffer
         Ref y = ws((size_t)Bn * HW * Cx * e);
         gn(x, Cx, Ref(), 0, Bn, HW, gn_eps, wt(n + ".g"), wt(n + ".b"), act, y, what);
         return y;
-    };
-    auto conv1 = [&](Ref x, int rows, int Cin, const std::string& w, Ref bias, int Cout, const char* what) {      // 1 x 1 convolution = GEMM -> new buffer
-        Ref y = ws((size_t)rows * Cout * e);
-        gemm(x, Cin, wt(w), Cin, y, Cout, rows, Cout, Cin, bias, Ref(), 0, 0, Ref(), 0, 0, what);
-        return y;
-    };
-    auto conv3 = [&](Ref x, int Cin, int H, int W, int stride, int flags, const std::string& w, Ref bias, int Cout, Ref res, const char* what) {
-        const int Ho = H / stride, Wo = W / stride;
-        Ref y = ws((size_t)Bn * Ho * Wo * Cout * e);
-        conv(x, Cin, Bn, H, W, stride, 0, wt(w), Cout, y, bias, Ref(), 0, res, flags, what);
-        return y;
-    };
-    auto add_relu = [&](Ref a, Ref b, Ref y, size_t nel, const char* what) {      // y = max(a + b, 0); b may be null
-        live(a, what); live(b, what); live(y, what);
-        op(OC_OTHER, 0, what, [=](const Run& r) { return mve_dpt_add_relu(d, r.p(a), r.p(b), r.p(y), nel, r.stream); });
-    };
-    auto layernorm = [&](Ref x, Ref y, const std::string& n) {
-        const Ref g = wt(n + ".g"), b = wt(n + ".b");
-        live(x, "layernorm"); live(y, "layernorm");
-        op(OC_NORM, 0, "layernorm", [=](const Run& r) { return mve_layernorm(d, r.p(x), C, r.p(y), C, M, C, (const float*)r.p(g), (const float*)r.p(b), eps, r.stream); });
     };
 
     // ---- stem: 7 x 7 / 2 "same" convolution as a GEMM over gathered rows, GroupNorm + ReLU, 3 x 3 / 2 "same" max-pool --------------------------
@@ -68,7 +39,7 @@ int Builder::build_dpt(int B_) {
     {
         Ref rows = ws((size_t)Bn * H * H * 152 * e);
         op(OC_OTHER, 0, "stem window rows", [=](const Run& r) { return mve_dpt_stem_rows(d, r.p(px), Bn, S, r.p(rows), 152, r.stream); });
-        Ref s0 = conv1(rows, Bn * H * H, 152, "stem.w", Ref(), Cs, "stem.conv 7x7/2");
+        Ref s0 = conv1x1(rows, Bn * H * H, 152, "stem.w", Ref(), Cs, "stem.conv 7x7/2");
         rel(rows);
         Ref s1 = norm(s0, Cs, H * H, "stem", 2, "stem.norm+relu");
         rel(s0);
@@ -78,7 +49,7 @@ int Builder::build_dpt(int B_) {
         op(OC_OTHER, 0, "stem.maxpool 3x3/2", [=](const Run& r) { return mve_dpt_maxpool(d, r.p(s1), Bn, Hs, Hs, Cs, r.p(x), r.stream); });
         rel(s1);
         H /= 2;
-        tap(x, (size_t)Bn * H * H * Cs * e, 0, "stem -> tap");
+        copy_out(x, (size_t)Bn * H * H * Cs * e, 0, "stem -> tap");
     }
 
     // ---- three stages of BitBottleneckLayer (non-pre-activation): the stride sits in the 3 x 3 convolution ("same": the extra row / column after =
@@ -91,27 +62,21 @@ int Builder::build_dpt(int B_) {
         for (int m = 0; m < c.dp_depth[s]; ++m) {
             const std::string b = "s" + std::to_string(s) + ".b" + std::to_string(m);
             const int stride = (m == 0 && s > 0) ? 2 : 1, Ho = H / stride;
-            Ref t1 = conv1(x, Bn * H * H, cin, b + ".c1.w", Ref(), mid, "bottleneck.conv1");
+            Ref t1 = conv1x1(x, Bn * H * H, cin, b + ".c1.w", Ref(), mid, "bottleneck.conv1");
             Ref t1n = norm(t1, mid, H * H, b + ".n1", 2, "bottleneck.norm1+relu");
             rel(t1);
-            Ref t2 = conv3(t1n, mid, H, H, stride, stride == 2 ? MVE_CONV_PAD_BR : 0, b + ".c2.w", Ref(), mid, Ref(), "bottleneck.conv2 3x3");
+            Ref t2 = conv3x3(t1n, mid, Bn, H, H, stride, b + ".c2.w", Ref(), mid, Ref(), stride == 2 ? MVE_CONV_PAD_BR : 0, "bottleneck.conv2 3x3");
             rel(t1n);
             Ref t2n = norm(t2, mid, Ho * Ho, b + ".n2", 2, "bottleneck.norm2+relu");
             rel(t2);
-            Ref t3 = conv1(t2n, Bn * Ho * Ho, mid, b + ".c3.w", Ref(), cout, "bottleneck.conv3");
+            Ref t3 = conv1x1(t2n, Bn * Ho * Ho, mid, b + ".c3.w", Ref(), cout, "bottleneck.conv3");
             rel(t2n);
             Ref t3n = norm(t3, cout, Ho * Ho, b + ".n3", 0, "bottleneck.norm3");
             rel(t3);
             Ref sc = x;
             if (m == 0) {
-                Ref xs = x;
-                if (stride == 2) {
-                    xs = ws((size_t)Bn * Ho * Ho * cin * e);
-                    const int Hi = H, ci = cin;
-                    live(x, "shortcut stride-2 gather"); live(xs, "shortcut stride-2 gather");
-                    op(OC_OTHER, 0, "shortcut stride-2 gather", [=](const Run& r) { return mve_dpt_gather_s2(d, r.p(x), Bn, Hi, Hi, ci, r.p(xs), r.stream); });
-                }
-                Ref ds = conv1(xs, Bn * Ho * Ho, cin, b + ".ds.w", Ref(), cout, "bottleneck.downsample.conv");
+                Ref xs = stride == 2 ? gather_s2(x, Bn, H, H, cin) : x;
+                Ref ds = conv1x1(xs, Bn * Ho * Ho, cin, b + ".ds.w", Ref(), cout, "bottleneck.downsample.conv");
                 if (stride == 2) rel(xs);
                 sc = norm(ds, cout, Ho * Ho, b + ".dn", 0, "bottleneck.downsample.norm");
                 rel(ds);
@@ -124,20 +89,20 @@ int Builder::build_dpt(int B_) {
             x = y; cin = cout; H = Ho;
         }
         stage_out[s] = x; stage_H[s] = H;
-        tap(x, (size_t)Bn * H * H * cout * e, 1 + s, "stage -> tap");
+        copy_out(x, (size_t)Bn * H * H * cout * e, 1 + s, "stage -> tap");
     }
 
     // ---- the decoder's inputs from the two feature maps: layer1_rn / layer2_rn --------------------------------------------------------------------
     Ref rn[4];
-    rn[0] = conv3(stage_out[0], c.dp_stage[0], stage_H[0], stage_H[0], 1, 0, "rn1.w", Ref(), F, Ref(), "layer1_rn");
+    rn[0] = conv3x3(stage_out[0], c.dp_stage[0], Bn, stage_H[0], stage_H[0], 1, "rn1.w", Ref(), F, Ref(), 0, "layer1_rn");
     rel(stage_out[0]);
-    rn[1] = conv3(stage_out[1], c.dp_stage[1], stage_H[1], stage_H[1], 1, 0, "rn2.w", Ref(), F, Ref(), "layer2_rn");
+    rn[1] = conv3x3(stage_out[1], c.dp_stage[1], Bn, stage_H[1], stage_H[1], 1, "rn2.w", Ref(), F, Ref(), 0, "layer2_rn");
     rel(stage_out[1]);
 
     // ---- tokens: 1 x 1 projection of stage 3, class token + position table, pre-norm ViT blocks ---------------------------------------------------
     MVE_CHECK(H == Gd, MVE_ERR_STATE, "dpt plan: stage 3 is %d x %d, the token grid %d x %d", H, H, Gd, Gd);
     {
-        Ref patch = conv1(x, Bn * G2, c.dp_stage[2], "proj.w", wt("proj.b"), C, "patch_embed.proj");
+        Ref patch = conv1x1(x, Bn * G2, c.dp_stage[2], "proj.w", wt("proj.b"), C, "patch_embed.proj");
         rel(x);
         x = ws((size_t)M * C * e);
         const Ref cls = wt("cls"), pos = wt("pos");
@@ -158,57 +123,23 @@ int Builder::build_dpt(int B_) {
         Ref ro = ws((size_t)Bn * G2 * C * e);
         gemm(tok, C, wt(r_ + ".wt"), C, ro, C, Bn * G2, C, C, Ref(), rv, C, G2, Ref(), 0, 0, "readout (token half + class row)");
         rel(tok); rel(rv);
-        {
-            const size_t nel = (size_t)Bn * G2 * C;
-            live(ro, "readout gelu");
-            op(OC_OTHER, 0, "readout gelu", [=](const Run& r) { return mve_act(d, MVE_ACT_GELU, r.p(ro), r.p(ro), nel, r.stream); });
-        }
-        Ref p = conv1(ro, Bn * G2, C, r_ + ".p.w", wt(r_ + ".p.b"), N, "act_postprocess conv1x1");
+        act(ro, (size_t)Bn * G2 * C, MVE_ACT_GELU, "readout gelu");
+        Ref p = conv1x1(ro, Bn * G2, C, r_ + ".p.w", wt(r_ + ".p.b"), N, "act_postprocess conv1x1");
         rel(ro);
         int Hp = Gd;
         if (which == 4) {
-            Ref z = conv3(p, N, Gd, Gd, 2, 0, "r4.z.w", wt("r4.z.b"), N, Ref(), "act_postprocess4 conv3x3/2");
+            Ref z = conv3x3(p, N, Bn, Gd, Gd, 2, "r4.z.w", wt("r4.z.b"), N, Ref(), 0, "act_postprocess4 conv3x3/2");
             rel(p); p = z; Hp = Gd / 2;
         }
-        Ref y = conv3(p, N, Hp, Hp, 1, 0, which == 3 ? "rn3.w" : "rn4.w", Ref(), F, Ref(), which == 3 ? "layer3_rn" : "layer4_rn");
+        Ref y = conv3x3(p, N, Bn, Hp, Hp, 1, which == 3 ? "rn3.w" : "rn4.w", Ref(), F, Ref(), 0, which == 3 ? "layer3_rn" : "layer4_rn");
         rel(p);
         return y;
     };
     for (int k = 0; k <= c.dp_tap[1]; ++k) {
-        const std::string b = "l" + std::to_string(k);
-        Ref n1 = ws((size_t)M * C * e);
-        layernorm(x, n1, b + ".n1");
-        Ref qkv = ws((size_t)M * 3 * C * e);
-        gemm(n1, C, wt(b + ".qkv.w"), C, qkv, 3 * C, M, 3 * C, C, wt(b + ".qkv.b"), Ref(), 0, 0, Ref(), 0, 0, "attn.qkv");
-        rel(n1);
-        Ref a = ws((size_t)M * C * e);
-        {
-            const Ref q = qkv, kk = at(qkv, (size_t)C * e), v = at(qkv, (size_t)2 * C * e);
-            live(qkv, "attention"); live(a, "attention");
-            op(OC_ATTN, 4.0 * Bn * heads * (double)T * T * hd, "attention", [=](const Run& r) {
-                return mve_attention(d, r.p(q), 3 * C, r.p(kk), 3 * C, r.p(v), 3 * C, nullptr, 0, nullptr, 0, r.p(a), C, Bn, T, T, 0, heads, hd, scale, r.stream);
-            });
-        }
-        rel(qkv);
-        Ref x2 = ws((size_t)M * C * e);
-        gemm(a, C, wt(b + ".o.w"), C, x2, C, M, C, C, wt(b + ".o.b"), Ref(), 0, 0, x, C, 0, "attn.proj+residual");
-        rel(a); rel(x); x = x2;
-        Ref n2 = ws((size_t)M * C * e);
-        layernorm(x, n2, b + ".n2");
-        Ref f = ws((size_t)M * I * e);
-        gemm(n2, C, wt(b + ".fc1.w"), C, f, I, M, I, C, wt(b + ".fc1.b"), Ref(), 0, 0, Ref(), 0, 0, "mlp.fc1");
-        rel(n2);
-        {
-            const size_t nel = (size_t)M * I;
-            live(f, "gelu");
-            op(OC_OTHER, 0, "gelu", [=](const Run& r) { return mve_act(d, MVE_ACT_GELU, r.p(f), r.p(f), nel, r.stream); });
-        }
-        Ref x3 = ws((size_t)M * C * e);
-        gemm(f, I, wt(b + ".fc2.w"), I, x3, C, M, C, I, wt(b + ".fc2.b"), Ref(), 0, 0, x, C, 0, "mlp.fc2+residual");
-        rel(f); rel(x); x = x3;
+        x = encoder_layer(DPT_ENCODER, "l" + std::to_string(k), x, M, C, I, MVE_ACT_GELU, false);
         // the taps are block outputs: the backbone's final LayerNorm never reaches the prediction
-        if (k == c.dp_tap[0]) { tap(x, (size_t)M * C * e, 4, "token tap 3 -> tap"); rn[2] = reassemble(x, 3); }
-        if (k == c.dp_tap[1]) { tap(x, (size_t)M * C * e, 5, "token tap 4 -> tap"); rn[3] = reassemble(x, 4); }
+        if (k == c.dp_tap[0]) { copy_out(x, (size_t)M * C * e, 4, "token tap 3 -> tap"); rn[2] = reassemble(x, 3); }
+        if (k == c.dp_tap[1]) { copy_out(x, (size_t)M * C * e, 5, "token tap 4 -> tap"); rn[3] = reassemble(x, 4); }
     }
     rel(x);
 
@@ -217,17 +148,11 @@ int Builder::build_dpt(int B_) {
         const size_t nel = (size_t)Bn * Hf * Hf * F;
         Ref r0 = ws(nel * e);
         add_relu(xin, Ref(), r0, nel, "relu");
-        Ref h = conv3(r0, F, Hf, Hf, 1, 0, n + ".c1.w", wt(n + ".c1.b"), F, Ref(), "resConfUnit.conv1");
+        Ref h = conv3x3(r0, F, Bn, Hf, Hf, 1, n + ".c1.w", wt(n + ".c1.b"), F, Ref(), 0, "resConfUnit.conv1");
         rel(r0);
-        add_relu(h, Ref(), h, nel, "relu");
-        Ref y = conv3(h, F, Hf, Hf, 1, 0, n + ".c2.w", wt(n + ".c2.b"), F, xin, "resConfUnit.conv2+residual");
+        relu(h, nel, "relu");
+        Ref y = conv3x3(h, F, Bn, Hf, Hf, 1, n + ".c2.w", wt(n + ".c2.b"), F, xin, 0, "resConfUnit.conv2+residual");
         rel(h);
-        return y;
-    };
-    auto upsample = [&](Ref xin, int Hf, int Cx, const char* what) {
-        Ref y = ws((size_t)Bn * 4 * Hf * Hf * Cx * e);
-        live(xin, what); live(y, what);
-        op(OC_OTHER, 0, what, [=](const Run& r) { return mve_dpt_upsample2x(d, r.p(xin), Bn, Hf, Hf, Cx, r.p(y), r.stream); });
         return y;
     };
     Ref path;
@@ -246,36 +171,32 @@ int Builder::build_dpt(int B_) {
         }
         Ref o = rcu(f + ".u2", s, Hf);
         rel(s);
-        Ref up = upsample(o, Hf, F, "fusion upsample x2 (align_corners)");
+        Ref up = upsample2x(o, Bn, Hf, Hf, F, "fusion upsample x2 (align_corners)");
         rel(o);
         Hf *= 2;
-        path = conv1(up, Bn * Hf * Hf, F, f + ".out.w", wt(f + ".out.b"), F, "fusion out_conv");
+        path = conv1x1(up, Bn * Hf * Hf, F, f + ".out.w", wt(f + ".out.b"), F, "fusion out_conv");
         rel(up);
-        tap(path, (size_t)Bn * Hf * Hf * F * e, 6 + (3 - k), "fusion -> tap");
+        copy_out(path, (size_t)Bn * Hf * Hf * F * e, 6 + (3 - k), "fusion -> tap");
     }
 
     // ---- head (dpt_depth.py:91-99): conv3x3, x2 bilinear, conv3x3, ReLU, conv1x1 (output channels padded to 8 for the GEMM), ReLU; NHWC -> NCHW ------
     MVE_CHECK(Hf == S / 2, MVE_ERR_STATE, "dpt plan: the decoder ends at %d, expected %d", Hf, S / 2);
     {
-        Ref h0 = conv3(path, F, Hf, Hf, 1, 0, "h0.w", wt("h0.b"), F / 2, Ref(), "head.conv0 3x3");
+        Ref h0 = conv3x3(path, F, Bn, Hf, Hf, 1, "h0.w", wt("h0.b"), F / 2, Ref(), 0, "head.conv0 3x3");
         rel(path);
-        Ref up = upsample(h0, Hf, F / 2, "head upsample x2 (align_corners)");
+        Ref up = upsample2x(h0, Bn, Hf, Hf, F / 2, "head upsample x2 (align_corners)");
         rel(h0);
-        Ref h2 = conv3(up, F / 2, S, S, 1, 0, "h2.w", wt("h2.b"), 32, Ref(), "head.conv2 3x3");
+        Ref h2 = conv3x3(up, F / 2, Bn, S, S, 1, "h2.w", wt("h2.b"), 32, Ref(), 0, "head.conv2 3x3");
         rel(up);
         const size_t npx = (size_t)Bn * S * S;
-        add_relu(h2, Ref(), h2, npx * 32, "relu");
-        Ref h4 = conv1(h2, (int)npx, 32, "h4.w", wt("h4.b"), 8, "head.conv4 1x1");
+        relu(h2, npx * 32, "relu");
+        Ref h4 = conv1x1(h2, (int)npx, 32, "h4.w", wt("h4.b"), 8, "head.conv4 1x1");
         rel(h2);
-        add_relu(h4, Ref(), h4, npx * 8, "relu");
-        live(h4, "NHWC -> NCHW");
-        op(OC_OTHER, 0, "NHWC -> NCHW", [=](const Run& r) { return mve_nhwc_to_nchw(d, d, r.p(h4), 8, Bn, NC, S, S, r.p(out), r.stream); });
+        relu(h4, npx * 8, "relu");
+        to_nchw(h4, d, 8, Bn, NC, S, S, "NHWC -> NCHW");
         rel(h4);
     }
-    pl.enc_end = pl.ops.size();
-    pl.ws_bytes = ar.peak + 256;
-    if (!u.err.empty()) { mve_set_error("dpt plan: %s", u.err.c_str()); u.err.clear(); return MVE_ERR_STATE; }
-    return MVE_OK;
+    return finish("dpt");
 }
 
 }  // namespace

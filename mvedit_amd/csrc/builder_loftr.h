@@ -18,16 +18,11 @@ namespace {
 constexpr int LOFTR_IO = 13, LOFTR_TAPS_COARSE = 14, LOFTR_TAPS_FINE = 3;
 
 int Builder::build_loftr(int N_, int H, int W, int phase) {
-    B = N_; dt = c.dtype;
-    pl = Plan();
+    begin(N_, H, W, phase, c.dtype);
     const int e = 2, d = dt, N = N_, Bn = 2 * N_, Hc = H / 8, Wc = W / 8, L = Hc * Wc, Sp = (L + 7) / 8 * 8, H2 = H / 2, W2 = W / 2, heads = 8;
-    pl.B = N_; pl.H = H; pl.W = W; pl.n_img = phase; pl.io_dtype = c.dtype;
     const long long cap = (long long)N * L;
     MVE_CHECK((long long)Bn * H2 * W2 * 256 < (1ll << 31) && cap * 25 * 2 * 256 < (1ll << 31) && (long long)L * Sp < (1ll << 31), MVE_ERR_ARG,
               "loftr: %d pairs of %d x %d overflow 32-bit activation indexing", N, H, W);
-    ld_temb = 0; ld_kv = 0;
-    rows_img = 0;
-    auto io = [](int k) { Ref r; r.kind = Ref::CNOUT; r.idx = k; return r; };
     const float ln_eps = 1e-5f, la_eps = 1e-6f;
     // copy `rows` rows of `width` bytes out of a pitched workspace tensor into call tensor / tap k (skipped when the caller gave no pointer)
     auto copy_out = [&](Ref x, size_t spitch, size_t width, int k, std::function<size_t(const Run&)> rows, const char* what) {
@@ -99,47 +94,24 @@ int Builder::build_loftr(int N_, int H, int W, int phase) {
     auto rel_bufs = [&](const LayerBufs& bf) { rel(bf.Q); rel(bf.KV); rel(bf.MS); rel(bf.kvf); rel(bf.law); };
 
     if (phase == 1) {
-        Ref px; px.kind = Ref::SAMPLE;
-        Ref pos; pos.kind = Ref::CTX;
+        const Ref px = arg(Ref::SAMPLE), pos = arg(Ref::CTX);
         auto tap = [&](Ref x, size_t bytes, int k, const char* what) { copy_out(x, bytes, bytes, LOFTR_IO + k, fixed(1), what); };
-        auto relu = [&](Ref x, size_t nel, const char* what) {
-            live(x, what);
-            op(OC_OTHER, 0, what, [=](const Run& r) { return mve_dpt_add_relu(d, r.p(x), nullptr, r.p(x), nel, r.stream); });
-        };
         auto leaky = [&](Ref x, size_t nel) {
             live(x, "leaky relu");
             op(OC_OTHER, 0, "leaky relu", [=](const Run& r) { return mve_loftr_leaky_relu(d, r.p(x), r.p(x), nel, 0.01f, r.stream); });
         };
-        auto conv1 = [&](Ref x, int rows, int Cin, const std::string& w, Ref bias, int Cout, Ref res, const char* what) {
-            Ref y = ws((size_t)rows * Cout * e);
-            gemm(x, Cin, wt(w), Cin, y, Cout, rows, Cout, Cin, bias, Ref(), 0, 0, res, Cout, 0, what);
-            return y;
-        };
-        auto conv3 = [&](Ref x, int Cin, int Hh, int Ww, int stride, const std::string& w, Ref bias, int Cout, Ref res, Ref y, const char* what) {
-            if (y.kind == Ref::NUL) y = ws((size_t)Bn * (Hh / stride) * (Ww / stride) * Cout * e);
-            conv(x, Cin, Bn, Hh, Ww, stride, 0, wt(w), Cout, y, bias, Ref(), 0, res, 0, what);
-            return y;
-        };
-        auto upsample = [&](Ref x, int Hh, int Ww, int Cx) {
-            Ref y = ws((size_t)Bn * 4 * Hh * Ww * Cx * e);
-            live(x, "upsample x2"); live(y, "upsample x2");
-            op(OC_OTHER, 0, "upsample x2 (align_corners)", [=](const Run& r) { return mve_dpt_upsample2x(d, r.p(x), Bn, Hh, Ww, Cx, r.p(y), r.stream); });
-            return y;
-        };
         // BasicBlock: relu(bn1(conv1)), bn2(conv2) + shortcut in the second convolution's epilogue, relu
         auto block = [&](Ref x, int cin, int co, int Hh, int Ww, int stride, const std::string& b) {
             const int Ho = Hh / stride, Wo = Ww / stride;
-            Ref y1 = conv3(x, cin, Hh, Ww, stride, b + ".c1.w", wt(b + ".c1.b"), co, Ref(), Ref(), "block.conv1+bn1");
+            Ref y1 = conv3x3(x, cin, Bn, Hh, Ww, stride, b + ".c1.w", wt(b + ".c1.b"), co, Ref(), 0, "block.conv1+bn1");
             relu(y1, (size_t)Bn * Ho * Wo * co, "relu");
             Ref sc = x;
             if (stride == 2) {
-                Ref xs = ws((size_t)Bn * Ho * Wo * cin * e);
-                live(x, "shortcut stride-2 gather");
-                op(OC_OTHER, 0, "shortcut stride-2 gather", [=](const Run& r) { return mve_dpt_gather_s2(d, r.p(x), Bn, Hh, Ww, cin, r.p(xs), r.stream); });
-                sc = conv1(xs, Bn * Ho * Wo, cin, b + ".ds.w", wt(b + ".ds.b"), co, Ref(), "block.downsample+bn");
+                Ref xs = gather_s2(x, Bn, Hh, Ww, cin);
+                sc = conv1x1(xs, Bn * Ho * Wo, cin, b + ".ds.w", wt(b + ".ds.b"), co, "block.downsample+bn");
                 rel(xs);
             }
-            Ref y = conv3(y1, co, Ho, Wo, 1, b + ".c2.w", wt(b + ".c2.b"), co, sc, Ref(), "block.conv2+bn2+shortcut");
+            Ref y = conv3x3(y1, co, Bn, Ho, Wo, 1, b + ".c2.w", wt(b + ".c2.b"), co, sc, 0, "block.conv2+bn2+shortcut");
             relu(y, (size_t)Bn * Ho * Wo * co, "relu");
             rel(y1);
             if (stride == 2) rel(sc);
@@ -151,7 +123,7 @@ int Builder::build_loftr(int N_, int H, int W, int phase) {
         {
             Ref rows = ws((size_t)Bn * H2 * W2 * 56 * e);
             op(OC_OTHER, 0, "stem window rows", [=](const Run& r) { return mve_loftr_stem_rows(d, r.p(px), Bn, H, W, r.p(rows), 56, r.stream); });
-            x0 = conv1(rows, Bn * H2 * W2, 56, "stem.w", wt("stem.b"), 128, Ref(), "stem.conv 7x7/2+bn");
+            x0 = conv1x1(rows, Bn * H2 * W2, 56, "stem.w", wt("stem.b"), 128, "stem.conv 7x7/2+bn");
             rel(rows);
             relu(x0, (size_t)Bn * H2 * W2 * 128, "relu");
             tap(x0, (size_t)Bn * H2 * W2 * 128 * e, 0, "stem -> tap");
@@ -172,25 +144,27 @@ int Builder::build_loftr(int N_, int H, int W, int phase) {
             tap(y, (size_t)Bn * Hh * Ww * Wd[s] * e, 1 + s, "stage -> tap");
         }
         const int H4 = H / 4, W4 = W / 4;
-        Ref x3o = conv1(xs[2], Bn * L, 256, "l3oc.w", Ref(), 256, Ref(), "layer3_outconv");
+        Ref x3o = conv1x1(xs[2], Bn * L, 256, "l3oc.w", Ref(), 256, "layer3_outconv");
         rel(xs[2]);
         tap(x3o, (size_t)Bn * L * 256 * e, 4, "coarse feature -> tap");
-        Ref u3 = upsample(x3o, Hc, Wc, 256);
-        Ref s2 = conv1(xs[1], Bn * H4 * W4, 200, "l2oc.w", Ref(), 256, u3, "layer2_outconv + upsampled");
+        Ref u3 = upsample2x(x3o, Bn, Hc, Wc, 256, "upsample x2 (align_corners)");
+        Ref s2 = ws((size_t)Bn * H4 * W4 * 256 * e);
+        dense(xs[1], wt("l2oc.w"), Ref(), s2, Bn * H4 * W4, 256, 200, u3, "layer2_outconv + upsampled");
         rel(u3); rel(xs[1]);
-        Ref t2 = conv3(s2, 256, H4, W4, 1, "l2oc2.0.w", wt("l2oc2.0.b"), 256, Ref(), Ref(), "layer2_outconv2.conv+bn");
+        Ref t2 = conv3x3(s2, 256, Bn, H4, W4, 1, "l2oc2.0.w", wt("l2oc2.0.b"), 256, Ref(), 0, "layer2_outconv2.conv+bn");
         rel(s2);
         leaky(t2, (size_t)Bn * H4 * W4 * 256);
-        Ref x2o = conv3(t2, 256, H4, W4, 1, "l2oc2.3.w", Ref(), 200, Ref(), Ref(), "layer2_outconv2.conv");
+        Ref x2o = conv3x3(t2, 256, Bn, H4, W4, 1, "l2oc2.3.w", Ref(), 200, Ref(), 0, "layer2_outconv2.conv");
         rel(t2);
-        Ref u2 = upsample(x2o, H4, W4, 200);
+        Ref u2 = upsample2x(x2o, Bn, H4, W4, 200, "upsample x2 (align_corners)");
         rel(x2o);
-        Ref s1 = conv1(xs[0], Bn * H2 * W2, 128, "l1oc.w", Ref(), 200, u2, "layer1_outconv + upsampled");
+        Ref s1 = ws((size_t)Bn * H2 * W2 * 200 * e);
+        dense(xs[0], wt("l1oc.w"), Ref(), s1, Bn * H2 * W2, 200, 128, u2, "layer1_outconv + upsampled");
         rel(u2); rel(xs[0]);
-        Ref t1 = conv3(s1, 200, H2, W2, 1, "l1oc2.0.w", wt("l1oc2.0.b"), 200, Ref(), Ref(), "layer1_outconv2.conv+bn");
+        Ref t1 = conv3x3(s1, 200, Bn, H2, W2, 1, "l1oc2.0.w", wt("l1oc2.0.b"), 200, Ref(), 0, "layer1_outconv2.conv+bn");
         rel(s1);
         leaky(t1, (size_t)Bn * H2 * W2 * 200);
-        conv3(t1, 200, H2, W2, 1, "l1oc2.3.w", Ref(), 128, Ref(), io(0), "layer1_outconv2.conv -> feat_f");
+        conv(t1, 200, Bn, H2, W2, 1, 0, wt("l1oc2.3.w"), 128, cn_out(0), Ref(), Ref(), 0, Ref(), 0, "layer1_outconv2.conv -> feat_f");
         rel(t1);
 
         // ---- tokens: position add, 8 encoder layers ----------------------------------------------------------------------------------------------
@@ -312,10 +286,7 @@ int Builder::build_loftr(int N_, int H, int W, int phase) {
         });
         rel(FY);
     }
-    pl.enc_end = pl.ops.size();
-    pl.ws_bytes = ar.peak + 256;
-    if (!u.err.empty()) { mve_set_error("loftr plan: %s", u.err.c_str()); u.err.clear(); return MVE_ERR_STATE; }
-    return MVE_OK;
+    return finish("loftr");
 }
 
 }  // namespace

@@ -1,4 +1,4 @@
-// Fragment of the executor's single translation unit (csrc/unet.hip includes it; not a stand-alone header): the plan builder -- workspace arena, op recording, and the blocks shared by all networks (GEMM / conv / norm / attention ops, ResnetBlock2D, Transformer2DModel).
+// Fragment of the executor's single translation unit (csrc/unet.hip includes it; not a stand-alone header): the plan builder -- workspace arena, op recording, and the blocks shared by the networks (GEMM / conv / norm / attention ops, the prologue / epilogue and small ops every builder uses, the pre-norm encoder layer, ResnetBlock2D, Transformer2DModel).
 #pragma once
 #include "executor_params.h"
 
@@ -313,6 +313,131 @@ struct Builder {
         });
     }
 
+    // ---- pieces shared by the network builders ----------------------------------------------------------------------------------------------------
+    // Every op below copies what its closure needs into locals first: the closures outlive the Builder and must not capture `this`.
+    // A plan starts with begin() and ends with `return finish(name)`.  finish() leaves alone an enc_end the builder has set itself (UNet, LPIPS).
+    void begin(int B_, int H, int W, int n_img, int io_dtype) {
+        B = B_; dt = c.dtype;
+        pl = Plan();
+        pl.B = B_; pl.H = H; pl.W = W; pl.n_img = n_img; pl.io_dtype = io_dtype;
+        ld_temb = 0; ld_kv = 0;
+        rows_img = 0;
+    }
+    int finish(const char* name) {
+        if (!pl.enc_end) pl.enc_end = pl.ops.size();
+        pl.ws_bytes = ar.peak + 256;
+        if (!u.err.empty()) { mve_set_error("%s plan: %s", name, u.err.c_str()); u.err.clear(); return MVE_ERR_STATE; }
+        return MVE_OK;
+    }
+    static Ref arg(Ref::Kind kind, int idx = 0) { Ref r; r.kind = kind; r.idx = idx; return r; }      // a tensor of the call (Run::p)
+    static Ref cn_out(int idx) { return arg(Ref::CNOUT, idx); }
+    // dense linear: out [rows, N] = A [rows, K] . W [N, K]^T (+ bias) (+ res [rows, N]); every leading dimension is the one K and N imply
+    void dense(Ref A, Ref W, Ref bias, Ref out, int rows, int N, int K, Ref res, const char* what, int flags = 0) {
+        gemm(A, K, W, K, out, N, rows, N, K, bias, Ref(), 0, 0, res, res.kind == Ref::NUL ? 0 : N, flags, what);
+    }
+    // LayerNorm of `rows` rows of x (pitch ldx) into dense rows of y, with the parameters slot.g / slot.b (plain stream; ln() above is the pair stream's)
+    void layernorm(Ref x, int ldx, Ref y, int rows, int C, const std::string& slot, float eps) {
+        const int d = dt;
+        const Ref g = wt(slot + ".g"), b = wt(slot + ".b");
+        live(x, "layernorm"); live(y, "layernorm");
+        op(OC_NORM, 0, "layernorm", [=](const Run& r) { return mve_layernorm(d, r.p(x), ldx, r.p(y), C, rows, C, (const float*)r.p(g), (const float*)r.p(b), eps, r.stream); });
+    }
+    // optional output: x is copied into Run::cn_out[slot] only when the caller gave a tensor for it
+    void copy_out(Ref x, size_t bytes, int slot, const char* what) {
+        live(x, what);
+        op(OC_OTHER, 0, what, [=](const Run& r) {
+            void* dst = r.cn_out ? r.cn_out[slot] : nullptr;
+            if (!dst) return (int)MVE_OK;
+            return hipMemcpyAsync(dst, r.p(x), bytes, hipMemcpyDeviceToDevice, r.stream) == hipSuccess ? (int)MVE_OK : (int)MVE_ERR_HIP;
+        });
+    }
+    void act(Ref x, size_t nel, int selector, const char* what) {      // in place; selector: MVE_ACT_*
+        const int d = dt;
+        live(x, what);
+        op(OC_OTHER, 0, what, [=](const Run& r) { return mve_act(d, selector, r.p(x), r.p(x), nel, r.stream); });
+    }
+    void add_relu(Ref a, Ref b, Ref y, size_t nel, const char* what) {      // y = max(a + b, 0); b may be null
+        const int d = dt;
+        live(a, what); live(b, what); live(y, what);
+        op(OC_OTHER, 0, what, [=](const Run& r) { return mve_dpt_add_relu(d, r.p(a), r.p(b), r.p(y), nel, r.stream); });
+    }
+    void relu(Ref x, size_t nel, const char* what) { add_relu(x, Ref(), x, nel, what); }
+    // NHWC convolutions into a new buffer: 1 x 1 (a GEMM over the pixels) and 3 x 3 (flags: MVE_CONV_*)
+    Ref conv1x1(Ref x, int rows, int Cin, const std::string& w, Ref bias, int Cout, const char* what) {
+        Ref y = ws((size_t)rows * Cout * 2);
+        dense(x, wt(w), bias, y, rows, Cout, Cin, Ref(), what);
+        return y;
+    }
+    Ref conv3x3(Ref x, int Cin, int Bn, int H, int W, int stride, const std::string& w, Ref bias, int Cout, Ref res, int flags, const char* what) {
+        Ref y = ws((size_t)Bn * (H / stride) * (W / stride) * Cout * 2);
+        conv(x, Cin, Bn, H, W, stride, 0, wt(w), Cout, y, bias, Ref(), 0, res, flags, what);
+        return y;
+    }
+    Ref upsample2x(Ref x, int Bn, int H, int W, int C, const char* what) {      // bilinear, align_corners -> new buffer
+        const int d = dt;
+        Ref y = ws((size_t)Bn * 4 * H * W * C * 2);
+        live(x, what); live(y, what);
+        op(OC_OTHER, 0, what, [=](const Run& r) { return mve_dpt_upsample2x(d, r.p(x), Bn, H, W, C, r.p(y), r.stream); });
+        return y;
+    }
+    Ref gather_s2(Ref x, int Bn, int H, int W, int C) {      // every second pixel of every second row (the input of a strided 1 x 1 shortcut) -> new buffer
+        const int d = dt;
+        Ref y = ws((size_t)Bn * (H / 2) * (W / 2) * C * 2);
+        live(x, "shortcut stride-2 gather"); live(y, "shortcut stride-2 gather");
+        op(OC_OTHER, 0, "shortcut stride-2 gather", [=](const Run& r) { return mve_dpt_gather_s2(d, r.p(x), Bn, H, W, C, r.p(y), r.stream); });
+        return y;
+    }
+    // layout ops at the ends of a network: a call tensor (NCHW, io_dtype) into NHWC rows of Cpad channels, and NHWC rows back into Run::out
+    void to_nhwc(Ref src, int Bn, int C, int H, int W, int Cpad, Ref dst, const char* what = "nchw->nhwc") {
+        const int d = dt, io = pl.io_dtype;
+        live(dst, what);
+        op(OC_OTHER, 0, what, [=](const Run& r) { return mve_nchw_to_nhwc(d, io, r.p(src), Bn, C, H, W, Cpad, r.p(dst), r.stream); });
+    }
+    void to_nchw(Ref x, int x_dtype, int ldx, int Bn, int C, int H, int W, const char* what = "nhwc->nchw") {
+        const int io = pl.io_dtype;
+        const Ref dst = arg(Ref::OUT);
+        live(x, what);
+        op(OC_OTHER, 0, what, [=](const Run& r) { return mve_nhwc_to_nchw(io, x_dtype, r.p(x), ldx, Bn, C, H, W, r.p(dst), r.stream); });
+    }
+
+    // One pre-norm transformer encoder layer over x [M = B * T, C] -> new buffer (x is released): x += out(attention(qkv(norm1(x)))), then
+    // x += fc2(act(fc1(norm2(x)))).  The callers differ in the parameter names and two labels (EncoderNames) and in the attention step: causal
+    // (CLIP text tower: head_dim 64, scale 1 / 8, mve_attention_causal) or full with head_dim^-1/2.
+    struct EncoderNames { const char *n1, *qkv, *o, *n2, *fc1, *fc2, *qkv_what, *o_what; };
+    Ref encoder_layer(const EncoderNames& nm, const std::string& p, Ref x, int M, int C, int I, int act_sel, bool causal) {
+        const int e = 2, d = dt, Bn = B, T = M / B, heads = c.heads[0], hd = causal ? 64 : C / heads;
+        const float eps = c.eps, scale = causal ? 0.125f : 1.0f / sqrtf((float)hd);
+        Ref n1 = ws((size_t)M * C * e);
+        layernorm(x, C, n1, M, C, p + nm.n1, eps);
+        Ref qkv = ws((size_t)M * 3 * C * e);
+        dense(n1, wt(p + nm.qkv + ".w"), wt(p + nm.qkv + ".b"), qkv, M, 3 * C, C, Ref(), nm.qkv_what);
+        rel(n1);
+        Ref a = ws((size_t)M * C * e);
+        {
+            const Ref q = qkv, kk = at(qkv, (size_t)C * e), v = at(qkv, (size_t)2 * C * e);
+            const char* what = causal ? "causal attention" : "attention";
+            live(qkv, what); live(a, what);
+            op(OC_ATTN, 4.0 * Bn * heads * (double)T * T * hd, what, [=](const Run& r) {
+                if (causal) return mve_attention_causal(d, r.p(q), 3 * C, r.p(kk), 3 * C, r.p(v), 3 * C, r.p(a), C, Bn, T, heads, hd, scale, r.stream);
+                return mve_attention(d, r.p(q), 3 * C, r.p(kk), 3 * C, r.p(v), 3 * C, nullptr, 0, nullptr, 0, r.p(a), C, Bn, T, T, 0, heads, hd, scale, r.stream);
+            });
+        }
+        rel(qkv);
+        Ref x2 = ws((size_t)M * C * e);
+        dense(a, wt(p + nm.o + ".w"), wt(p + nm.o + ".b"), x2, M, C, C, x, nm.o_what);
+        rel(a); rel(x);
+        Ref n2 = ws((size_t)M * C * e);
+        layernorm(x2, C, n2, M, C, p + nm.n2, eps);
+        Ref f = ws((size_t)M * I * e);
+        dense(n2, wt(p + nm.fc1 + ".w"), wt(p + nm.fc1 + ".b"), f, M, I, C, Ref(), "mlp.fc1");
+        rel(n2);
+        act(f, (size_t)M * I, act_sel, act_sel == MVE_ACT_GELU ? "gelu" : "quick_gelu");
+        Ref x3 = ws((size_t)M * C * e);
+        dense(f, wt(p + nm.fc2 + ".w"), wt(p + nm.fc2 + ".b"), x3, M, C, I, x2, "mlp.fc2+residual");
+        rel(f); rel(x2);
+        return x3;
+    }
+
     // ControlNet output k: out_k (+)= conditioning_scale * (W x + b), a 1x1 "zero convolution" (diffusers ControlNetModel
     // controlnet_down_blocks / controlnet_mid_block, then the `* conditioning_scale` and MultiControlNetModel's running sum)
     void zero_conv(Ref x, int C, int M, int hw, const std::string& name, int out_idx) {
@@ -391,7 +516,7 @@ struct Builder {
             gemm_ln(n0, C, wt(name + ".proj_in.w"), C, h, C, M, C, C, wt(name + ".proj_in.b"), Ref(), 0, n1_first, wt(b0 + ".norm1.g"), wt(b0 + ".norm1.b"),
                     "transformer.proj_in+norm1");
         } else {
-            gemm(n0, C, wt(name + ".proj_in.w"), C, h, C, M, C, C, wt(name + ".proj_in.b"), Ref(), 0, 0, Ref(), 0, 0, "transformer.proj_in");
+            dense(n0, wt(name + ".proj_in.w"), wt(name + ".proj_in.b"), h, M, C, C, Ref(), "transformer.proj_in");
         }
         rel(n0);
         for (int k = 0; k < layers; ++k) {
@@ -404,7 +529,7 @@ struct Builder {
                 ln(h, n1, M, C, wt(b + ".norm1.g"), wt(b + ".norm1.b"));
             }
             Ref qkv = ws((size_t)M * 3 * C * e);
-            gemm(n1, C, wt(b + ".qkv.w"), C, qkv, 3 * C, M, 3 * C, C, Ref(), Ref(), 0, 0, Ref(), 0, 0, "attn1.qkv");
+            dense(n1, wt(b + ".qkv.w"), Ref(), qkv, M, 3 * C, C, Ref(), "attn1.qkv");
             rel(n1);
             Ref a = ws((size_t)M * C * e);
             const AttnOpts& ao = pl.ao;
@@ -438,13 +563,13 @@ struct Builder {
                 gemm_ln(a, C, wt(b + ".o1.w"), C, h2, C, M, C, C, wt(b + ".o1.b"), h, C, n2, wt(b + ".norm2.g"), wt(b + ".norm2.b"), "attn1.to_out+residual+norm2");
                 rel(a); rel(h); h = h2;
             } else {
-                gemm(a, C, wt(b + ".o1.w"), C, h2, C, M, C, C, wt(b + ".o1.b"), Ref(), 0, 0, h, C, 0, "attn1.to_out+residual");
+                dense(a, wt(b + ".o1.w"), wt(b + ".o1.b"), h2, M, C, C, h, "attn1.to_out+residual");
                 rel(a); rel(h); h = h2;
                 // cross attention (K/V hoisted)
                 ln(h, n2, M, C, wt(b + ".norm2.g"), wt(b + ".norm2.b"));
             }
             Ref q = ws((size_t)M * C * e);
-            gemm(n2, C, wt(b + ".q2.w"), C, q, C, M, C, C, Ref(), Ref(), 0, 0, Ref(), 0, 0, "attn2.to_q");
+            dense(n2, wt(b + ".q2.w"), Ref(), q, M, C, C, Ref(), "attn2.to_q");
             rel(n2);
             end_prefix();          // the first cross-attention: from here on the halves of the batch differ
             Ref a2 = ws((size_t)M * C * e);
@@ -467,7 +592,7 @@ struct Builder {
                 gemm_ln(a2, C, wt(b + ".o2.w"), C, h3, C, M, C, C, wt(b + ".o2.b"), h, C, n3, wt(b + ".norm3.g"), wt(b + ".norm3.b"), "attn2.to_out+residual+norm3");
                 rel(a2); rel(h); h = h3;
             } else {
-                gemm(a2, C, wt(b + ".o2.w"), C, h3, C, M, C, C, wt(b + ".o2.b"), Ref(), 0, 0, h, C, 0, "attn2.to_out+residual");
+                dense(a2, wt(b + ".o2.w"), wt(b + ".o2.b"), h3, M, C, C, h, "attn2.to_out+residual");
                 rel(a2); rel(h); h = h3;
                 // feed forward (GEGLU fused in the first GEMM's epilogue)
                 ln(h, n3, M, C, wt(b + ".norm3.g"), wt(b + ".norm3.b"));
@@ -476,16 +601,20 @@ struct Builder {
             gemm(n3, C, wt(b + ".ff1.w"), C, f, 4 * C, M, 8 * C, C, wt(b + ".ff1.b"), Ref(), 0, 0, Ref(), 0, MVE_GEMM_GEGLU, "ff.geglu");
             rel(n3);
             Ref h4 = ws_stream((size_t)M * C * e);
-            gemm(f, 4 * C, wt(b + ".ff2.w"), 4 * C, h4, C, M, C, 4 * C, wt(b + ".ff2.b"), Ref(), 0, 0, h, C, 0, "ff.out+residual");
+            dense(f, wt(b + ".ff2.w"), wt(b + ".ff2.b"), h4, M, C, 4 * C, h, "ff.out+residual");
             rel(f); rel(h); h = h4;
         }
         Ref out = ws_stream((size_t)M * C * e);
-        gemm(h, C, wt(name + ".proj_out.w"), C, out, C, M, C, C, wt(name + ".proj_out.b"), Ref(), 0, 0, x, C, 0, "transformer.proj_out+residual");
+        dense(h, wt(name + ".proj_out.w"), wt(name + ".proj_out.b"), out, M, C, C, x, "transformer.proj_out+residual");
         rel(h);
         return out;
     }
 
-    // network-specific plan builders (builder_unet.h, builder_vae.h, builder_sr.h, builder_lpips.h, builder_clip.h, builder_clip_vision.h, builder_dpt.h, builder_loftr.h)
+    // network-specific plan builders: build, mid_block, add_residual (builder_unet.h); vae_attention, build_vae (builder_vae.h); build_sr (builder_sr.h);
+    // build_lpips (builder_lpips.h); build_clip (builder_clip.h); build_clip_vision, build_resampler (builder_clip_vision.h); build_dpt (builder_dpt.h);
+    // build_loftr (builder_loftr.h)
+    Ref mid_block(Ref x, int C, int h, int w);
+    Ref add_residual(Ref a, Ref src, int C, int h, int w, const char* label);
     Ref vae_attention(const std::string& name, Ref x, int C, int H, int W);
     int build_lpips(int B_, int H, int W, int io_dtype);
     int build_clip(int B_, int L);

@@ -17,7 +17,8 @@
 //   * per-op HIP-event profiling and analytic FLOP accounting are built in (bench.py's roofline).
 //
 // Source layout (one translation unit): executor.h (types) -> executor_params.h (parameter slab + loader) -> executor_builder.h (plan
-// builder, shared blocks) -> builder_{unet,vae,sr,lpips,clip,clip_vision,dpt,loftr}.h (one plan builder per network) -> this file (plan cache + C ABI).
+// builder: arena, op recording, and every block more than one network uses) -> builder_{unet,vae,sr,lpips,clip,clip_vision,dpt,loftr}.h (the plans:
+// UNet and ControlNet, the two VAE halves, SRVGG, LPIPS, CLIP text, CLIP vision and the Resampler, DPT, LoFTR) -> this file (plan cache + C ABI).
 #include "executor_builder.h"
 #include "builder_unet.h"
 #include "builder_vae.h"

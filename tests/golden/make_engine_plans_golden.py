@@ -94,12 +94,27 @@ def build_cases():
     vision = CLIPVisionEngine(SimpleNamespace(**GV.config_dict('A')), device='cpu', with_projection=GV.CASES['A']['with_projection'])
     cases['clip_vision'] = _entry(lib, vision, vision.plan(1))
     rs = ResamplerEngine(device='cpu', **GV.RESAMPLER)
-    cases['resampler'] = _entry(lib, rs, rs.plan(1, vision.num_tokens))
+    rs_tokens = vision.num_tokens
+    cases['resampler'] = _entry(lib, rs, rs.plan(1, rs_tokens))
     dpt = DPTNormalEngine(dict(GD.engine_config('A')), device='cpu')
     cases['dpt'] = _entry(lib, dpt, dpt.plan(1))
     loftr = LoFTREngine(None, f16, device='cpu')
     cases['loftr_coarse'] = _entry(lib, loftr, loftr.plan(1, 64, 64, 1))
     cases['loftr_fine'] = _entry(lib, loftr, loftr.plan(1, 64, 64, 2))
+
+    # branches of the plan builders that the cases above do not take (appended, so the entries above keep their place in the file)
+    text = CLIPTextEngine(SimpleNamespace(**GT.config_dict('B')), device='cpu', with_projection=GT.CASES['B']['with_projection'])
+    cases['clip_text_B'] = _entry(lib, text, text.plan(1, 77))
+    for k in ('B', 'C'):
+        vision = CLIPVisionEngine(SimpleNamespace(**GV.config_dict(k)), device='cpu', with_projection=GV.CASES[k]['with_projection'])
+        cases['clip_vision_' + k] = _entry(lib, vision, vision.plan(1))
+    cases['resampler_b2'] = _entry(lib, rs, rs.plan(2, rs_tokens))
+    dpt = DPTNormalEngine(dict(GD.engine_config('B')), device='cpu')
+    cases['dpt_B'] = _entry(lib, dpt, dpt.plan(2))
+    cases['vae_decoder_b2'] = _entry(lib, vae.decoder, vae.decoder.plan(2, 8, 8, f16))
+    cases['unet_sd15_residuals_nhwc'] = _entry(lib, unet, unet.plan(2, 16, 16, 77, has_residuals=True, residuals_nhwc=True))
+    cases['loftr_coarse_n2'] = _entry(lib, loftr, loftr.plan(2, 64, 64, 1))
+    cases['loftr_fine_n2'] = _entry(lib, loftr, loftr.plan(2, 64, 64, 2))
     return cases
 
 

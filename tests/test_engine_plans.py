@@ -11,7 +11,9 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CASES = ('unet_sd15', 'unet_sd15_residuals', 'unet_sd15_cross_imgs2', 'unet_sdxl', 'controlnet', 'controlnet_ctx93_tail4', 'vae_decoder', 'vae_encoder',
-         'srvgg', 'lpips', 'clip_text', 'clip_vision', 'resampler', 'dpt', 'loftr_coarse', 'loftr_fine')
+         'srvgg', 'lpips', 'clip_text', 'clip_vision', 'resampler', 'dpt', 'loftr_coarse', 'loftr_fine',
+         'clip_text_B', 'clip_vision_B', 'clip_vision_C', 'resampler_b2', 'dpt_B', 'vae_decoder_b2', 'unet_sd15_residuals_nhwc', 'loftr_coarse_n2',
+         'loftr_fine_n2')
 
 
 @pytest.fixture(scope='module')
