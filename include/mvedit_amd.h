@@ -738,7 +738,9 @@ MVE_API int mve_mesh_normals_backward(const float* d_verts, int V, const int32_t
  *    block_out_channels[i], down_attn[i] (CrossAttnDownBlock2D vs DownBlock2D), num_heads[i],
  *    transformer_layers[i].  Weights are engine-owned: mve_unet_load_param copies one tensor of
  *    the diffusers state dict (by its diffusers name, in its torch layout, any float dtype) into
- *    packed device storage; the caller's tensor is not retained.
+ *    packed device storage; the caller's tensor is not retained.  A name the configuration does
+ *    not have, an element count that differs from the parameter's, or a 3 x 3 convolution whose
+ *    shape is not exactly [O, I, 3, 3] is refused with MVE_ERR_ARG before the device is touched.
  * ========================================================================= */
 MVE_API int mve_unet_create(void** handle, int dtype, int in_channels, int out_channels, int n_levels,
                             const int* block_out_channels, int layers_per_block, const int* down_attn,

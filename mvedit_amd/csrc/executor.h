@@ -203,6 +203,23 @@ struct Param {   // one engine-owned packed tensor (or a slice view of one)
     float q_fold = 0.f;   // > 0: a to_q weight whose rows carry head_dim^-1/2 * log2(e) (the attention kernel then takes Q as it comes)
 };
 
+// One accepted state-dict tensor, as the layout describes it while it reserves the slot (executor_params.h): load_param looks the name up, checks
+// the tensor against `numel` / `conv`, and runs the steps.  Everything is resolved from Config at layout time.
+struct PackStep {
+    std::string slot;          // destination slot ...
+    size_t off = 0;            // ... and the element offset inside it
+    long long src_off = 0;     // element offset into the source tensor
+    PackDims d{};
+    bool phase4 = false;       // instead of `d`: the upsampler's summed taps (mve_pack_upsample_phase_weights over the source's [O, I, 3, 3])
+};
+struct Source {
+    long long numel = 0;               // required element count (any shape: [C, C] and [C, C, 1, 1] both load)
+    long long conv[2] = {0, 0};        // 3 x 3 convolutions: the exact shape [O, I, 3, 3] is required
+    bool zero = false;                 // the steps' slots are cleared first (padding rows / columns the tensor does not cover)
+    bool optional = false;             // not in `expected`: the IP-Adapter's to_k_ip / to_v_ip, counted in n_ip_loaded
+    std::vector<PackStep> steps;       // one, or two for a weight that is kept in two packings (LPIPS `.wt`, the upsamplers' `.w4`)
+};
+
 enum OpClass { OC_CONV = 0, OC_LINEAR = 1, OC_ATTN = 2, OC_NORM = 3, OC_OTHER = 4, OC_COUNT = 5 };
 
 struct Ref {
@@ -340,6 +357,7 @@ struct Arena {
 struct Unet {
     Config cfg;
     std::map<std::string, Param> params;     // packed tensors, by engine name
+    std::map<std::string, Source> sources;   // every accepted state-dict name -> where and how it is packed (written by the layout alone)
     std::map<std::string, bool> loaded;      // diffusers names seen
     std::vector<std::string> expected;       // diffusers names required
     unsigned char* slab = nullptr;
@@ -354,7 +372,6 @@ struct Unet {
     size_t ref_store_bytes = 0;
     int n_ip_loaded = 0, n_xf_layers = 0;
     bool fuse_sc = false;                       // conv_shortcut folded into conv2's K loop (all widths multiples of 64)
-    std::map<std::string, int> sc_cin;          // resnet prefix -> input width, for resnets with a shortcut
     std::string err;
     // added conditions of a 'text_time' handle, bound by mve_unet_bind_added_cond (caller-owned device memory)
     struct AddedCond { const void* text = nullptr; const float* ids = nullptr; int text_dtype = 0, text_dim = 0, n_ids = 0, B = 0; } added;

@@ -220,7 +220,7 @@ struct Builder {
         const int Hv = ups ? 2 * H : H, Wv = ups ? 2 * W : W;
         const int Ho = (Hv - 1) / stride + 1, Wo = (Wv - 1) / stride + 1;
         live(x, what); live(out, what); live(res, what); live(rowvec, what);
-        const int fl = flags | (C1 % 64 == 0 ? MVE_CONV_W_CHUNK64 : 0);   // must mirror load_param's packing rule
+        const int fl = flags | (C1 % 64 == 0 ? MVE_CONV_W_CHUNK64 : 0);   // must mirror the layout's packing rule (pack_conv)
         const size_t skb = mve_gemm_workspace_bytes(Bn * Ho * Wo, Cout, 9 * C1, Ho * Wo);
         Ref sk = skb ? ws(skb) : Ref();
         const Ref res_lo = lo(res), out_lo = (flags & MVE_GEMM_OUT_F32) ? Ref() : lo(out);

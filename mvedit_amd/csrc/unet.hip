@@ -736,15 +736,6 @@ int mve_unet_load_param(void* handle, const char* name, const void* d_src, int s
                         void* stream) {
     MVE_CHECK(handle && name && d_src && shape && ndim >= 1 && ndim <= 4, MVE_ERR_ARG, "unet_load_param: bad arguments");
     Unet* u = (Unet*)handle;
-    if (!u->slab) {
-        hipError_t e = hipMalloc((void**)&u->slab, u->slab_bytes);
-        if (e != hipSuccess) {
-            u->slab = nullptr;
-            mve_set_error("unet_load_param: hipMalloc(%zu) failed: %s", u->slab_bytes, hipGetErrorString(e));
-            return MVE_ERR_HIP;
-        }
-        MVE_HIP(hipMemsetAsync(u->slab, 0, u->slab_bytes, (hipStream_t)stream));      // padding rows / optional weights start as zeros
-    }
     std::string nm = name;
     if (u->cfg.kind == Kind::Lpips && nm.compare(0, 5, "lins.") == 0) nm = "lin" + nm.substr(5);      // nn.ModuleList alias of lin0..lin4
     if (u->cfg.is_vae()) {     // AutoencoderKL state-dict names -> the half's own

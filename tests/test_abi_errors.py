@@ -75,6 +75,51 @@ def test_engine_call_checks(L):
         lib.raw('mve_unet_destroy')(clip)
 
 
+def test_load_param_refuses_a_tensor_before_the_slab_exists(L):
+    """mve_unet_load_param looks the name up in the layout's table and checks the tensor against its entry before the slab is allocated: an
+    unknown name, a vector one element longer than its slot, a 3 x 3 convolution with O and I swapped (the element count still fits: only the exact
+    shape tells) and the time_emb_proj of a resnet the configuration does not have all answer MVE_ERR_ARG (-1) with the tensor's name."""
+    lib, p, _ = L
+    arr = lambda *v: (ctypes.c_int * len(v))(*v)
+    unet, vae, sr, clip = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+    lib.call('mve_unet_create', ctypes.byref(unet), 1, 4, 4, 2, arr(320, 640), 1, arr(1, 0), arr(8, 8), arr(1, 1), 768, 32, 1e-5, 0)
+    lib.call('mve_vae_create', ctypes.byref(vae), 1, 1, 4, 3, 2, arr(64, 128), 1, 32, 1e-6)          # the decoder half
+    lib.call('mve_srvgg_create', ctypes.byref(sr), 1, 3, 3, 64, 2, 4)
+    lib.call('mve_clip_text_create', ctypes.byref(clip), 1, 512, 77, 128, 2, 2, 512, 0, ctypes.c_float(1e-5), 0)
+
+    def refused(handle, name, *shape, names=None):
+        with pytest.raises(lib.MveError) as e:
+            lib.call('mve_unet_load_param', handle, name.encode(), p, 0, len(shape), (ctypes.c_longlong * len(shape))(*shape), None)
+        assert '(-1)' in str(e.value) and (names or name) in str(e.value), str(e.value)
+    try:
+        refused(unet, 'conv_nope.weight', 320)
+        refused(unet, 'conv_norm_out.weight', 321)
+        refused(unet, 'down_blocks.0.resnets.0.norm1.weight', 321)
+        refused(unet, 'down_blocks.1.resnets.0.conv1.weight', 320, 640, 3, 3)            # the layout has [640, 320, 3, 3]
+        refused(unet, 'down_blocks.7.resnets.0.time_emb_proj.weight', 320, 1280)
+        refused(unet, 'down_blocks.0.resnets.0.time_emb_proj.weight', 321, 1280)
+        refused(unet, 'down_blocks.0.attentions.0.transformer_blocks.0.attn1.to_q.weight', 320, 321)
+        # the VAE half: AutoencoderKL names, reported under the half's own
+        refused(vae, 'decoder.conv_nope.weight', 64, names='conv_nope.weight')
+        refused(vae, 'decoder.conv_norm_out.weight', 65, names='conv_norm_out.weight')
+        refused(vae, 'decoder.up_blocks.1.resnets.0.conv1.weight', 128, 64, 3, 3, names='up_blocks.1.resnets.0.conv1.weight')      # [64, 128, 3, 3]
+        refused(vae, 'decoder.mid_block.resnets.0.time_emb_proj.weight', 128, 512, names='mid_block.resnets.0.time_emb_proj.weight')
+        refused(clip, 'text_model.nope.weight', 128)
+        refused(clip, 'text_model.final_layer_norm.weight', 129)
+        refused(clip, 'text_model.encoder.layers.0.self_attn.q_proj.bias', 129)
+        refused(clip, 'text_model.encoder.layers.2.layer_norm1.weight', 128)                 # two layers: 0 and 1
+        refused(sr, 'body.99.weight', 64)
+        refused(sr, 'body.1.weight', 65)                                                       # PReLU slopes
+        refused(sr, 'body.0.weight', 3, 64, 3, 3)                                              # [64, 3, 3, 3]
+        refused(sr, 'body.2.time_emb_proj.weight', 64, 256)
+        buf = ctypes.create_string_buffer(256)
+        for h, n in ((unet, 'conv_in.weight'), (vae, 'pq_conv.weight'), (sr, 'body.0.weight'), (clip, 'text_model.embeddings.token_embedding.weight')):
+            assert lib.raw('mve_unet_missing_params')(h, buf, 256) > 0 and buf.value.decode() == n          # nothing counts as loaded
+    finally:
+        for h in (unet, vae, sr, clip):
+            lib.raw('mve_unet_destroy')(h)
+
+
 def test_render_and_mesh_argument_checks(L):
     lib, p, _ = L
     _bad(lib, 'mve_tonemap_lut', p, 16, p, p, 100, 0, 0, p, None, match='steps')

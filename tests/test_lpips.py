@@ -152,7 +152,7 @@ def test_lpips_building_blocks(lib):
 def test_dgrad_weight_packing_formula():
     """The loader packs every VGG weight a second time so that the FORWARD implicit-GEMM kernel computes the data gradient:
     W'[ci][co][ky][kx] = W[co][ci][2-ky][2-kx] in the slab-major layout [O'][I'/64][9][64].  This replays the loader's PackDims
-    (csrc/unet.hip, LPIPS branch of load_param: source offset 8 + o'*9 + slab*64*ci*9 - tap + c*ci*9) in numpy, reads the result back
+    (csrc/executor_params.h, the `.wt` step of the LPIPS case of layout_params: source offset 8 + o'*9 + slab*64*ci*9 - tap + c*ci*9) in numpy, reads the result back
     with the forward layout's meaning, and checks conv2d(g, W') against autograd's input gradient."""
     import numpy as np
     rng = np.random.default_rng(0)
