@@ -549,6 +549,33 @@ MVE_API int mve_loftr_gather_rows(int dtype, const void* d_feat, int N, int L, i
 MVE_API int mve_loftr_fine_match(int dtype, const void* d_feat0, const void* d_feat1, int M, int C, const float* d_mkpts1_c, float radius, float* d_expec_f,
                                  float* d_mkpts1_f, void* stream);
 
+/* ---- 2g. Segment Anything image encoder primitives (csrc/sam.hip): what segment_anything's `ImageEncoderViT` (the same arithmetic as
+ * transformers' SamVisionEncoder, models/sam/modeling_sam.py) has and the primitives above do not give.  The reference reaches it through
+ * `SamPredictor.set_image` (lib/apis/adapter3d.py:363-372, :723-734; lib/pipelines/utils.py:114-131).  `dtype` is f16 or bf16, C % 8 == 0,
+ * pointers are 16-byte aligned; every argument error returns MVE_ERR_ARG with a message that names the argument, before the device is touched. */
+
+/* Self-attention with MViTv2's decomposed relative-position bias over packed projections, laid out as mve_attention's: NS independent sequences
+ * of gh x gw tokens, row (s, i) at d_X + (s*gh*gw + i)*ldx, head h at column h*head_dim, token i at grid position (i / gw, i % gw).
+ *   O[q] = softmax_k( scale * Q[q].K[k] + Q[q].rel_h[qh - kh + gh - 1] + Q[q].rel_w[qw - kw + gw - 1] ) V[k]
+ * d_rel_h [2gh-1][head_dim] and d_rel_w [2gw-1][head_dim] in `dtype`, shared by every sequence and head; the UNSCALED Q multiplies them
+ * (SamVisionAttention.get_decomposed_rel_pos with equal query and key grids and tables of exactly 2n-1 rows: no interpolation).
+ * head_dim 64 or 80; 1 <= gh, gw <= 64 (the per-query products Q.rel_h^T, Q.rel_w^T are formed once per 64-query tile by MFMA and kept in LDS
+ * as fp32: 64 x 64 needs ~100 KB of the CU's 160 KB); ldq / ldk / ldv multiples of 8.  Logits, both bias terms, maximum, exp and sum in
+ * fp32 -- the bias is never rounded to 16 bit; the tail of the last 64-key tile is masked by a select (probability exactly 0, no infinity is
+ * formed); both products on the MFMA, fp32 accumulation, one rounding of O.  No atomics: two runs give the same bits, and a sequence's result
+ * does not depend on NS. */
+MVE_API int mve_attention_relpos(int dtype, const void* d_Q, int ldq, const void* d_K, int ldk, const void* d_V, int ldv, const void* d_rel_h,
+                                 const void* d_rel_w, void* d_O, int ldo, int NS, int gh, int gw, int heads, int head_dim, float scale, void* stream);
+/* SamVisionLayer.window_partition / window_unpartition: d_x [B][G][G][C] <-> d_win [B * nw * nw][window * window][C] with nw = ceil(G / window);
+ * window (b, wy, wx) holds the pixels (wy*window + ty, wx*window + tx).  Partition writes ZEROS for the rows of the padded map (bottom and right,
+ * up to nw * window) that have no source pixel; un-partition copies the kept rows back and never reads the padded ones.  1 <= window <= G.
+ * Pure data movement in 16-byte vectors, no arithmetic. */
+MVE_API int mve_sam_window_partition(int dtype, const void* d_x, int B, int G, int C, int window, void* d_win, void* stream);
+MVE_API int mve_sam_window_unpartition(int dtype, const void* d_win, int B, int G, int C, int window, void* d_x, void* stream);
+/* hidden_states + pos_embed: y[b, p, :] = round_once(float(x[b, p, :]) + float(pos[p, :])); d_x, d_y [B][HW][C], d_pos [HW][C], all in `dtype`.
+ * In place allowed (d_y == d_x). */
+MVE_API int mve_sam_pos_add(int dtype, const void* d_x, const void* d_pos, void* d_y, int B, int HW, int C, void* stream);
+
 /* GroupNorm over NHWC input (optionally the channel-concat of two tensors) with optional fused SiLU (`silu` = 1) or ReLU (`silu` = 2):
  *   out[B*HW][C1+C2] = act( (x - mean_g) * rstd_g * gamma + beta ), torch.nn.GroupNorm semantics.
  * gamma/beta: [C1+C2] f32.  d_workspace: >= mve_groupnorm_workspace_bytes(B,HW,C,G) bytes.
@@ -936,6 +963,32 @@ MVE_API int mve_loftr_forward_coarse(void* handle, const void* d_images, const f
 MVE_API int mve_loftr_forward_fine(void* handle, int N, int H, int W, int M, void* const* d_io, void* const* d_taps, void* d_workspace, size_t workspace_bytes,
                                    float* op_ms, void* stream);
 MVE_API int mve_loftr_destroy(void* handle);
+/* Segment Anything image encoder (segment_anything `ImageEncoderViT` = transformers `SamVisionEncoder`; the reference's
+ * `predictor.model.image_encoder`, run once per request by `SamPredictor.set_image`).  The prompt encoder, the mask decoder and the mask
+ * post-processing are NOT part of it.  An executor handle: parameters through mve_unet_load_param under transformers' names
+ * (`patch_embed.projection.*`, `pos_embed`, `layers.N.{layer_norm1,layer_norm2}.*`, `layers.N.attn.{qkv,proj}.*`,
+ * `layers.N.attn.{rel_pos_h,rel_pos_w}`, `layers.N.mlp.{lin1,lin2}.*`, `neck.{conv1,conv2}.weight`, `neck.{layer_norm1,layer_norm2}.*`;
+ * mvedit_amd/sam.py renames segment_anything's keys onto them).  A rel_pos table must have exactly 2n-1 rows (n = window_size, or the grid in
+ * a global block): another length would need the reference's linear interpolation and is refused by the loader.
+ * mve_unet_missing_params / mve_unet_op_info apply.
+ * Plan (csrc/builder_sam.h), G = image_size / patch_size: mve_clip_patchify, patch GEMM with bias, mve_sam_pos_add (hidden state 0); per block
+ * LayerNorm, [windowed: mve_sam_window_partition of the normalised map, zero-padded to a multiple of window_size], q|k|v GEMM,
+ * mve_attention_relpos (scale = head_dim^-1/2; NS = B * windows with n = window_size, or NS = B with n = G for the blocks in
+ * global_attn_indexes), [windowed: mve_sam_window_unpartition], proj GEMM + residual on the B G^2 kept rows, LayerNorm, lin1 GEMM,
+ * mve_act(GELU), lin2 GEMM + residual; the neck: 1 x 1 GEMM C -> output_channels without bias, mve_layernorm over the pixels' channels
+ * (LayerNorm2d, eps 1e-6), mve_conv3x3 without bias, mve_layernorm, NHWC -> NCHW.  GEMMs never split K: an item's result does not depend on B.
+ * Refused at create: head_dim (hidden / heads) not 64 or 80, hidden > 2048, image_size % patch_size != 0, a grid above 64 x 64, window_size
+ * larger than the grid, more than 64 blocks, mlp_dim or output_channels not a multiple of 8, output_channels > 2048, use_rel_pos = 0,
+ * use_abs_pos = 0.
+ * d_pixels [B,3,S,S] NCHW and d_out [B,output_channels,G,G] NCHW in the handle's dtype, 16-byte aligned.  d_hidden_states: NULL, or
+ * num_layers + 1 pointers to [B,G,G,C] tensors in the handle's dtype -- entry 0 is patch_embed + pos_embed, entry k + 1 the output of block k. */
+MVE_API int mve_sam_encoder_create(void** handle, int dtype, int image_size, int patch_size, int hidden_size, int num_layers, int num_heads, int mlp_dim,
+                                   int window_size, const int* global_attn_indexes, int n_global, int output_channels, float layer_norm_eps,
+                                   int use_rel_pos, int use_abs_pos);
+MVE_API int mve_sam_encoder_plan(void* handle, int B, size_t* workspace_bytes, int* n_ops, double* flops);
+MVE_API int mve_sam_encoder_forward(void* handle, const void* d_pixels, int B, void* d_out, void* const* d_hidden_states, void* d_workspace,
+                                    size_t workspace_bytes, float* op_ms, void* stream);
+MVE_API int mve_sam_encoder_destroy(void* handle);
 /* LPIPS(net='vgg') perceptual loss, forward and backward w.r.t. the prediction: the `patch_loss` of the reference's reconstruct step
  * (lib/models/losses/lpips_loss.py:8-42 -> lpips==0.1.4 `LPIPS.forward`; lib/models/autoencoders/base_nerf.py:337-344, 8 patches of
  * 128 x 128 per optimisation iteration).  An executor handle: parameters through mve_unet_load_param under lpips' own state-dict

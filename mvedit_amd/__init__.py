@@ -10,6 +10,7 @@ Host-side modules mirror the reference's operator interfaces for that path only:
     mvedit_amd.mesh_ops           <-> MeshRenderer, DMTet, Mesh.auto_normal, edge_dilation, the mesh regularisers
     mvedit_amd.recon_loss / lpips <-> the image-space losses of nerf_optim / mesh_optim, LPIPSLoss
     mvedit_amd.tonemapping / shencoder <-> Tonemapping, lib.ops.shencoder
+    mvedit_amd.sam                <-> segment_anything's ImageEncoderViT behind SamPredictor.set_image (image encoder only)
     mvedit_amd.parallel           view partitioning, the one all-gather of the multi-GPU design, the scene re-sync
 Arithmetic lives in mvedit_amd/csrc (hand-written HIP) behind the C ABI of include/mvedit_amd.h.
 """

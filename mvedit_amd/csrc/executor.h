@@ -79,6 +79,10 @@ int mve_loftr_unfold(int, const void*, int, int, int, int, const int64_t*, const
 int mve_loftr_ln_add(int, const void*, int, const void*, int, void*, int, int, int, const float*, const float*, float, void*);
 int mve_loftr_gather_rows(int, const void*, int, int, int, const int64_t*, const int64_t*, int, void*, void*);
 int mve_loftr_fine_match(int, const void*, const void*, int, int, const float*, float, float*, float*, void*);
+int mve_attention_relpos(int, const void*, int, const void*, int, const void*, int, const void*, const void*, void*, int, int, int, int, int, int, float, void*);
+int mve_sam_window_partition(int, const void*, int, int, int, int, void*, void*);
+int mve_sam_window_unpartition(int, const void*, int, int, int, int, void*, void*);
+int mve_sam_pos_add(int, const void*, const void*, void*, int, int, int, void*);
 }
 
 namespace {
@@ -144,7 +148,7 @@ __global__ void k_group_mean(const typename Tag::T* __restrict__ x, typename Tag
 constexpr int CN_EMB[4] = {16, 32, 96, 256};      // diffusers ControlNetModel conditioning_embedding_out_channels (default)
 
 // which network a handle runs: one executor, one plan builder per kind (builder_*.h)
-enum class Kind { UNet, ControlNet, VaeDecoder, VaeEncoder, Srvgg, Lpips, ClipText, ClipVision, Resampler, Dpt, Loftr };
+enum class Kind { UNet, ControlNet, VaeDecoder, VaeEncoder, Srvgg, Lpips, ClipText, ClipVision, Resampler, Dpt, Loftr, Sam };
 
 // the noun of "handle is ..., not ..." messages
 const char* kind_name(Kind k) {
@@ -159,6 +163,7 @@ const char* kind_name(Kind k) {
         case Kind::Resampler: return "a Resampler";
         case Kind::Dpt: return "a DPT model";
         case Kind::Loftr: return "a LoFTR model";
+        case Kind::Sam: return "a SAM image encoder";
     }
     return "an unknown engine";
 }
@@ -186,6 +191,11 @@ struct Config {
     // dp_stem = stem width, dp_stage / dp_depth = the three stages' widths / depths, dp_tap = the two tapped ViT blocks (hooks[2], hooks[3]),
     // dp_inter = MLP width, dp_neck = channels of act_postprocess3 / 4, dp_features = decoder width
     int dp_image = 0, dp_stem = 0, dp_stage[3] = {0, 0, 0}, dp_depth[3] = {0, 0, 0}, dp_tap[2] = {0, 0}, dp_inter = 0, dp_neck[2] = {0, 0}, dp_features = 0;
+    // SAM image encoder (segment_anything ImageEncoderViT = transformers SamVisionEncoder; builder_sam.h): ch[0] = hidden_size, heads[0],
+    // layers_per_block = num_hidden_layers, eps = layer_norm_eps, clip_inter = mlp_dim; sm_image = image_size, sm_patch = patch_size, sm_window =
+    // window_size, sm_out = output_channels (the neck's width), sm_global = bit k set: block k attends over the whole grid (global_attn_indexes)
+    int sm_image = 0, sm_patch = 0, sm_window = 0, sm_out = 0;
+    unsigned long long sm_global = 0;
     // LoFTR matcher (loftr/loftr.py with default_cfg; builder_loftr.h): a fixed topology, nothing to configure but the dtype
     int dtype, in_ch, out_ch, n_levels, layers_per_block, ctx_dim, groups, linear_proj;
     // UNet2DConditionModel / ControlNetModel addition_embed_type (mve_unet_set_addition_embed): 0 none, 1 'text_time' (SDXL);
@@ -411,7 +421,7 @@ void enumerate(const Config& c, std::vector<ResnetDesc>& rs, std::vector<XfDesc>
     const int n = c.n_levels, L = c.layers_per_block;
     switch (c.kind) {
         case Kind::UNet: case Kind::ControlNet: case Kind::VaeDecoder: case Kind::VaeEncoder: break;      // resnets and transformers, listed below
-        default: return;     // plain conv stacks / the CLIP towers, the Resampler (builder_clip*.h), DPT (builder_dpt.h), LoFTR (builder_loftr.h)
+        default: return;     // plain conv stacks / the CLIP towers, the Resampler (builder_clip*.h), DPT (builder_dpt.h), LoFTR (builder_loftr.h), SAM (builder_sam.h)
     }
     if (c.is_vae()) {      // diffusers Encoder / Decoder (autoencoders/vae.py): resnets only, one attention in the mid block
         const int Cm = c.ch[n - 1];

@@ -231,6 +231,36 @@ void layout_params(Unet& u) {
         if (c.clip_proj) sb.mat("visual_projection.w", "visual_projection.weight", c.clip_proj, C);
         break;
     }
+    case Kind::Sam: {
+        // transformers' SamVisionEncoder names (mvedit_amd/sam.py renames segment_anything's keys onto them).  The patch convolution's weight
+        // [C, 3, P, P] becomes [C][Kp] as for the CLIP tower; pos_embed and the relative-position tables stay in the engine dtype ([G*G][C],
+        // [2n-1][head_dim] with n = window_size, or the grid in a global block: a table of another length would need the reference's linear
+        // interpolation and fails the loader's element count); the neck's 3 x 3 weight in the conv's K order.
+        const size_t C = c.ch[0], I = c.clip_inter, O = c.sm_out, PP3 = 3 * (size_t)c.sm_patch * c.sm_patch, Kp = (PP3 + 7) / 8 * 8, G = c.sm_image / c.sm_patch;
+        const size_t hd = C / c.heads[0];
+        sb.add("patch_embed.projection.w", C * Kp, false);
+        sb.part("patch_embed.projection.w", 0, "patch_embed.projection.weight", C * PP3,
+                PackDims{{1, 1, (long long)C, (long long)Kp}, {0, 0, (long long)PP3, 1}, {0, 0, (long long)Kp, 1}, (long long)PP3});
+        sb.vec("patch_embed.projection.b", "patch_embed.projection.bias", C);
+        sb.vec("pos_embed", "pos_embed", G * G * C, false);
+        for (int k = 0; k < c.layers_per_block; ++k) {
+            const std::string b = "layers." + num(k);
+            const size_t n = (c.sm_global >> k) & 1ull ? G : (size_t)c.sm_window;
+            sb.norm(b + ".layer_norm1", C);
+            sb.linear(b + ".attn.qkv", 3 * C, C);
+            sb.vec(b + ".attn.rel_pos_h", b + ".attn.rel_pos_h", (2 * n - 1) * hd, false);
+            sb.vec(b + ".attn.rel_pos_w", b + ".attn.rel_pos_w", (2 * n - 1) * hd, false);
+            sb.linear(b + ".attn.proj", C, C);
+            sb.norm(b + ".layer_norm2", C);
+            sb.linear(b + ".mlp.lin1", I, C);
+            sb.linear(b + ".mlp.lin2", C, I);
+        }
+        sb.mat("neck.conv1.w", "neck.conv1.weight", O, C);
+        sb.norm("neck.layer_norm1", O);
+        sb.conv("neck.conv2.w", "neck.conv2.weight", O, O);
+        sb.norm("neck.layer_norm2", O);
+        break;
+    }
     case Kind::Loftr: {
         // Engine-side slot names (mvedit_amd/matcher.py maps the checkpoint's keys onto them: BatchNorm folded into the convolution in front of it,
         // the 196-wide stage padded to 200 channels with zeros, k | v concatenated, conv K order): the loader converts a tensor of the slot's size.

@@ -17,8 +17,8 @@
 //   * per-op HIP-event profiling and analytic FLOP accounting are built in (bench.py's roofline).
 //
 // Source layout (one translation unit): executor.h (types) -> executor_params.h (parameter slab + loader) -> executor_builder.h (plan
-// builder: arena, op recording, and every block more than one network uses) -> builder_{unet,vae,sr,lpips,clip,clip_vision,dpt,loftr}.h (the plans:
-// UNet and ControlNet, the two VAE halves, SRVGG, LPIPS, CLIP text, CLIP vision and the Resampler, DPT, LoFTR) -> this file (plan cache + C ABI).
+// builder: arena, op recording, and every block more than one network uses) -> builder_{unet,vae,sr,lpips,clip,clip_vision,dpt,loftr,sam}.h (the plans:
+// UNet and ControlNet, the two VAE halves, SRVGG, LPIPS, CLIP text, CLIP vision and the Resampler, DPT, LoFTR, the SAM image encoder) -> this file (plan cache + C ABI).
 #include "executor_builder.h"
 #include "builder_unet.h"
 #include "builder_vae.h"
@@ -28,6 +28,7 @@
 #include "builder_clip_vision.h"
 #include "builder_dpt.h"
 #include "builder_loftr.h"
+#include "builder_sam.h"
 
 namespace {
 
@@ -62,6 +63,7 @@ int ensure_plan(Unet& u, const PlanKey& k) {
         case Kind::Resampler: rc = b.build_resampler(k.B, k.H); break;
         case Kind::Dpt: rc = b.build_dpt(k.B); break;
         case Kind::Loftr: rc = b.build_loftr(k.B, k.H, k.W, k.n_img); break;
+        case Kind::Sam: rc = b.build_sam(k.B); break;
     }
     if (rc != MVE_OK) return rc;
     np->ctx_len = k.ctx_len;
@@ -660,6 +662,82 @@ int mve_loftr_forward_fine(void* handle, int N, int H, int W, int M, void* const
 }
 
 int mve_loftr_destroy(void* handle) { return mve_unet_destroy(handle); }
+
+int mve_sam_encoder_create(void** handle, int dtype, int image_size, int patch_size, int hidden_size, int num_layers, int num_heads, int mlp_dim, int window_size,
+                           const int* global_attn_indexes, int n_global, int output_channels, float layer_norm_eps, int use_rel_pos, int use_abs_pos) {
+    MVE_CHECK(handle, MVE_ERR_ARG, "sam_encoder_create: null handle");
+    MVE_CHECK(dtype == MVE_F16 || dtype == MVE_BF16, MVE_ERR_ARG, "sam_encoder_create: dtype must be f16 or bf16");
+    MVE_CHECK(image_size >= 1 && patch_size >= 1 && patch_size <= image_size && image_size <= 4096, MVE_ERR_ARG, "sam_encoder_create: bad image_size %d / patch_size %d",
+              image_size, patch_size);
+    MVE_CHECK(image_size % patch_size == 0, MVE_ERR_ARG, "sam_encoder_create: image_size %d must be a multiple of patch_size %d", image_size, patch_size);
+    const int G = image_size / patch_size;
+    MVE_CHECK(G <= 64, MVE_ERR_ARG, "sam_encoder_create: image_size / patch_size = %d exceeds the 64 x 64 grid of mve_attention_relpos", G);
+    MVE_CHECK(num_layers >= 1 && num_layers <= 64 && num_heads >= 1, MVE_ERR_ARG, "sam_encoder_create: bad num_layers %d (1..64) / num_heads %d", num_layers, num_heads);
+    MVE_CHECK(hidden_size == num_heads * 64 || hidden_size == num_heads * 80, MVE_ERR_ARG,
+              "sam_encoder_create: hidden_size %d / num_heads %d: head_dim must be 64 or 80", hidden_size, num_heads);
+    MVE_CHECK(hidden_size <= 2048, MVE_ERR_ARG, "sam_encoder_create: hidden_size %d exceeds the 2048 channels of mve_layernorm", hidden_size);
+    MVE_CHECK(mlp_dim >= 8 && mlp_dim % 8 == 0, MVE_ERR_ARG, "sam_encoder_create: mlp_dim %d must be a multiple of 8", mlp_dim);
+    MVE_CHECK(window_size >= 1 && window_size <= G, MVE_ERR_ARG, "sam_encoder_create: window_size %d must be in [1, %d] (the grid)", window_size, G);
+    MVE_CHECK(n_global >= 0 && (n_global == 0 || global_attn_indexes), MVE_ERR_ARG, "sam_encoder_create: bad global_attn_indexes (n_global %d)", n_global);
+    MVE_CHECK(output_channels >= 8 && output_channels % 8 == 0 && output_channels <= 2048, MVE_ERR_ARG,
+              "sam_encoder_create: output_channels %d must be a multiple of 8 (GEMM / conv rows), at most the 2048 channels of mve_layernorm", output_channels);
+    MVE_CHECK(layer_norm_eps > 0.f, MVE_ERR_ARG, "sam_encoder_create: layer_norm_eps must be positive");
+    MVE_CHECK(use_rel_pos, MVE_ERR_ARG, "sam_encoder_create: use_rel_pos = 0 is not implemented (the attention kernel always adds the decomposed bias)");
+    MVE_CHECK(use_abs_pos, MVE_ERR_ARG, "sam_encoder_create: use_abs_pos = 0 is not implemented (the plan always adds pos_embed)");
+    unsigned long long mask = 0;
+    for (int i = 0; i < n_global; ++i) {
+        MVE_CHECK(global_attn_indexes[i] >= 0 && global_attn_indexes[i] < num_layers, MVE_ERR_ARG, "sam_encoder_create: global_attn_indexes[%d] = %d is not a block index below %d",
+                  i, global_attn_indexes[i], num_layers);
+        mask |= 1ull << global_attn_indexes[i];
+    }
+    Unet* u = new Unet();
+    Config& c = u->cfg;
+    c.kind = Kind::Sam; c.sm_image = image_size; c.sm_patch = patch_size; c.sm_window = window_size; c.sm_out = output_channels; c.sm_global = mask;
+    c.clip_inter = mlp_dim; c.clip_act = MVE_ACT_GELU;
+    c.dtype = dtype; c.in_ch = 3; c.out_ch = 1; c.n_levels = 1; c.layers_per_block = num_layers;
+    c.ctx_dim = 8; c.groups = 1; c.eps = layer_norm_eps; c.linear_proj = 0;
+    c.ch[0] = hidden_size; c.attn[0] = 0; c.heads[0] = num_heads; c.tlayers[0] = 0;
+    layout_params(*u);
+    *handle = u;
+    return MVE_OK;
+}
+
+int mve_sam_encoder_plan(void* handle, int B, size_t* workspace_bytes, int* n_ops, double* flops) {
+    MVE_CHECK(handle && B > 0, MVE_ERR_ARG, "sam_encoder_plan: bad arguments");
+    Unet* u;
+    const int rc = as_engine(handle, "sam_encoder_plan", {Kind::Sam}, u);
+    if (rc) return rc;
+    PlanKey k;
+    k.B = B; k.H = k.W = u->cfg.sm_image; k.io_dtype = u->cfg.dtype;
+    return plan_and_report(*u, k, workspace_bytes, n_ops, flops);
+}
+
+int mve_sam_encoder_forward(void* handle, const void* d_pixels, int B, void* d_out, void* const* d_hidden_states, void* d_workspace, size_t workspace_bytes,
+                            float* op_ms, void* stream) {
+    Unet* u;
+    const Plan* pl;
+    const int rc = begin_forward(handle, "sam_encoder_forward", {Kind::Sam}, [&](const Unet& e, PlanKey& k) -> int {
+        MVE_CHECK(d_pixels && d_out, MVE_ERR_ARG, "sam_encoder_forward: null pointer (d_pixels / d_out)");
+        MVE_CHECK(B > 0, MVE_ERR_ARG, "sam_encoder_forward: bad B %d", B);
+        MVE_CHECK(((uintptr_t)d_pixels & 15) == 0 && ((uintptr_t)d_out & 15) == 0, MVE_ERR_ARG, "sam_encoder_forward: d_pixels / d_out must be 16-byte aligned");
+        k.B = B; k.H = k.W = e.cfg.sm_image; k.io_dtype = e.cfg.dtype;
+        return MVE_OK;
+    }, d_workspace, workspace_bytes, u, pl);
+    if (rc) return rc;
+    const int n_hidden = u->cfg.layers_per_block + 1;
+    std::vector<void*> taps(n_hidden, nullptr);
+    if (d_hidden_states)
+        for (int i = 0; i < n_hidden; ++i) {
+            MVE_CHECK(d_hidden_states[i], MVE_ERR_ARG, "sam_encoder_forward: null d_hidden_states[%d]", i);
+            taps[i] = d_hidden_states[i];
+        }
+    Run r = new_run(*u, d_workspace, stream);
+    r.sample = d_pixels; r.out = d_out;
+    r.cn_out = taps.data();
+    return run_plan_ops(*pl, r, 0, pl->ops.size(), op_ms);
+}
+
+int mve_sam_encoder_destroy(void* handle) { return mve_unet_destroy(handle); }
 
 int mve_lpips_create(void** handle, int dtype, int normalize_inputs) {
     MVE_CHECK(handle, MVE_ERR_ARG, "lpips_create: null handle");

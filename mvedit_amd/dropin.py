@@ -38,7 +38,8 @@ Not part of `install()`: `swap_text_encoder(pipe)` puts native CLIP text towers 
 (mvedit_amd/vision_encoder.py) behind `image_encoder` / `vision_encoder` and the native image projection (mvedit_amd/ip_adapter.py) behind
 `image_proj_model` of ONE object (an `IPAdapter`, a `Zero123PlusPipeline`, a `Zero123Pipeline`), on request; `swap_normal_model(pipe)` puts the
 native DPT-hybrid normal predictor (mvedit_amd/normal_model.py) behind `pipe.normal_model`, on request; `swap_matcher(runner)` puts the native
-LoFTR matcher (mvedit_amd/matcher.py) behind a loaded `runner.matcher`, on request.
+LoFTR matcher (mvedit_amd/matcher.py) behind a loaded `runner.matcher`, on request; `swap_sam_image_encoder(runner)` puts the native SAM image
+encoder (mvedit_amd/sam.py) behind `runner.predictor.model.image_encoder`, on request (prompt encoder and mask decoder stay torch).
 
 Nothing here computes: every replacement is one of the engines / mirrors INTEGRATION.md documents seam by seam, and a conversion that fails
 raises -- there is no fallback to the torch module.  `uninstall()` restores everything (tests).
@@ -284,6 +285,41 @@ def swap_matcher(obj):
     return obj
 
 
+def make_sam_image_encoder(m):
+    """segment_anything's `ImageEncoderViT` (`predictor.model.image_encoder`, lib/apis/adapter3d.py:363-372) or transformers' `SamVisionEncoder` /
+    `SamVisionModel`."""
+    from .sam import SamImageEncoderEngine
+    dtype, device = _module_dtype_device(m)
+    return SamImageEncoderEngine.from_module(m, dtype=dtype, device=device)
+
+
+def swap_sam_image_encoder(obj):
+    """Opt-in (install() / swap_engines leave the SAM predictor alone): replaces the `image_encoder` of a `Sam`-like object by a native engine
+    built from that module.  `obj` is the runner (through `.predictor`), a `SamPredictor` (through `.model`) or the `Sam` model itself; a
+    `predictor` that is `None` (not loaded yet) stays `None`.  `Sam` is an `nn.Module`: the engine is set past `nn.Module.__setattr__`, so the
+    torch encoder stays registered in `_modules` (and `uninstall()` puts it back in view).  The prompt encoder and the mask decoder are not
+    touched.  Idempotent; the engine is cached on the source module like the other seams'."""
+    sam = obj
+    if hasattr(sam, 'predictor') and not hasattr(sam, 'image_encoder'):
+        sam = sam.predictor
+    if sam is not None and hasattr(sam, 'model') and not hasattr(sam, 'image_encoder'):
+        sam = sam.model
+    if sam is None:
+        return obj
+    m = getattr(sam, 'image_encoder', None)
+    if m is None or getattr(m, '_mve_is_engine', False) or not hasattr(m, 'state_dict'):
+        return obj
+    fp = _fingerprint(m)
+    cached = getattr(m, '_mve_engine', None)
+    if cached is None or cached[0] != fp:
+        eng = make_sam_image_encoder(m)
+        object.__setattr__(eng, '_mve_is_engine', True)
+        cached = (fp, eng)
+        object.__setattr__(m, '_mve_engine', cached)
+    _set_instance(sam, 'image_encoder', cached[1])
+    return obj
+
+
 MAKERS = dict(unet=make_unet, controlnet=make_controlnet, vae=make_vae, image_enhancer=make_image_enhancer, segmentation=make_segmentation,
               mesh_renderer=make_mesh_renderer)
 
@@ -504,6 +540,13 @@ def install():
 
 
 def uninstall():
+    # instance swaps first: the opt-in swap_sam_image_encoder records one whether or not install() ran
+    for obj, name, had, old in reversed(_state['instances']):
+        if had:
+            object.__setattr__(obj, name, old)
+        else:
+            obj.__dict__.pop(name, None)
+    _state['instances'] = []
     if not _state['installed']:
         return
     if _state['finder'] in sys.meta_path:
@@ -516,11 +559,6 @@ def uninstall():
                 delattr(obj, name)
             except AttributeError:
                 pass
-    for obj, name, had, old in reversed(_state['instances']):
-        if had:
-            object.__setattr__(obj, name, old)
-        else:
-            obj.__dict__.pop(name, None)
     for name, old in reversed(_state['seeded']):
         if old is None:
             sys.modules.pop(name, None)
