@@ -576,6 +576,65 @@ MVE_API int mve_sam_window_unpartition(int dtype, const void* d_win, int B, int 
  * In place allowed (d_y == d_x). */
 MVE_API int mve_sam_pos_add(int dtype, const void* d_x, const void* d_pos, void* d_y, int B, int HW, int C, void* stream);
 
+/* ---- 2h. Segment Anything prompt encoder, mask decoder and mask post-processing primitives (csrc/sam_decoder.hip): what `SamPredictor.predict`
+ * runs behind the image encoder (lib/apis/adapter3d.py:721-735, lib/pipelines/utils.py:108-146), stated as transformers' SamPromptEncoder /
+ * SamMaskDecoder / SamPositionalEmbedding (models/sam/modeling_sam.py; the same arithmetic as segment_anything's).  ALL OF THEM ARE fp32 --
+ * parameters, activations and accumulation -- except the two that touch the encoder: mve_sam_preprocess writes its input in the
+ * encoder's dtype and mve_sam_src reads its output.  No atomics, no split-K: two runs give the same bits and an item's result does not depend on
+ * the number of items in the launch.  Every argument error returns MVE_ERR_ARG before the device is touched. */
+
+/* uint8 image [h][w][3] (already resized: longest side S) -> d_out [1][3][S][S] in `dtype` (f16 | bf16): (x - pixel_mean[c]) / pixel_std[c] in fp32
+ * with one rounding; the pad region (rows >= h, columns >= w) is zero in normalised space, as `Sam.preprocess` pads after normalising.
+ * pixel_mean / pixel_std: HOST pointers to 3 floats, NULL = segment_anything's 123.675, 116.28, 103.53 / 58.395, 57.12, 57.375. */
+MVE_API int mve_sam_preprocess(int dtype, const uint8_t* d_image, int h, int w, int S, const float* pixel_mean, const float* pixel_std, void* d_out, void* stream);
+/* The image-wide positional encoding d_out [G*G][C]: cell (i, j) has coordinates ((j + 0.5) / G, (i + 0.5) / G); c = 2 c - 1, c @ d_gaussian
+ * [2][C/2], times 2 pi, [sin | cos] with sinf / cosf (SamModel.get_image_wide_positional_embeddings, channels last). */
+MVE_API int mve_sam_dense_pe(const float* d_gaussian, float* d_out, int G, int C, void* stream);
+/* d_out [N][T][C]: the iou token, the num_mask_tokens mask tokens, then the sparse prompt embeddings -- points first, box corners after.  A
+ * point (x, y) of d_points [N][n_points][2] is the positional encoding of ((x + 0.5) / image_size, (y + 0.5) / image_size) plus
+ * d_point_embed[label] for label 0 | 1 (d_labels [N][n_points] int32); for label -1 the row is d_not_a_point.  Points without a box
+ * (d_boxes NULL) get one padding point of label -1 appended.  The corners (x0, y0), (x1, y1) of d_boxes [N][4] use d_point_embed[2] / [3]
+ * (d_point_embed [4][C]).  T must equal 1 + num_mask_tokens + n_points (+ 1 padding point) + 2 (with a box) and be at most 16. */
+MVE_API int mve_sam_prompt_tokens(const float* d_boxes, const float* d_points, const int32_t* d_labels, int N, int n_points, const float* d_gaussian,
+                                  const float* d_point_embed, const float* d_not_a_point, const float* d_iou_token, const float* d_mask_tokens, int num_mask_tokens,
+                                  int C, float image_size, float* d_out, int T, void* stream);
+/* d_embedding [B][C][G][G] in `dtype` (NCHW) -> d_out fp32 rows [N * G^2][C]: item n reads image n / P (N = B * P); + d_no_mask_embed[C]. */
+MVE_API int mve_sam_src(int dtype, const void* d_embedding, const float* d_no_mask_embed, float* d_out, int N, int P, int C, int G, void* stream);
+/* out [M][N] = A [M][K] . W [N][K]^T (+ d_bias [N]) (+ d_res [M][N], row stride ldr) (ReLU when relu != 0), row-major fp32 with row strides lda /
+ * ldw / ldc.  Plain VALU FMA over 64 x 64 LDS tiles (gfx950's fp32 MFMA runs at the vector rate).  Per output element: K in steps of 16, the 16
+ * products of a step summed in k order into a partial, the partials added in step order -- fixed, and independent of M and of the tile. */
+MVE_API int mve_gemm_f32(const float* d_A, int lda, const float* d_W, int ldw, const float* d_bias, const float* d_res, int ldr, float* d_out, int ldc, int M, int N,
+                         int K, int relu, void* stream);
+/* softmax(scale * Q K^T) V per (item, head) in fp32, operands laid out as mve_attention's: row (b, i) at d_X + (b * L + i) * ldx, head h at column
+ * h * head_dim.  head_dim 16 | 32, any Lq, Lk >= 1, row strides multiples of 4, pointers 16-byte aligned.  Lk <= 16: one thread per (item, query,
+ * head) and an online softmax over the keys; Lk > 16: one block per (item, query, head), thread t walks keys t, t + 256, ..., the 256 partial
+ * (max, sum, acc) triples merged by a tree in a fixed order.  A tail is a guard on the key index; no infinity is formed. */
+MVE_API int mve_attention_f32(const float* d_Q, int ldq, const float* d_K, int ldk, const float* d_V, int ldv, float* d_O, int ldo, int NB, int Lq, int Lk,
+                              int heads, int head_dim, float scale, void* stream);
+/* torch.nn.LayerNorm over the last dimension of dense fp32 rows (two-pass mean / variance, one wave per row); in place allowed. */
+MVE_API int mve_layernorm_f32(const float* d_x, float* d_y, int rows, int C, const float* d_gamma, const float* d_beta, float eps, void* stream);
+/* y[r, :] = x[r, :] + pe[r mod period_rows, :] over dense fp32 rows (queries + point embedding: period = rows; keys + dense PE: period = G^2). */
+MVE_API int mve_add_rows_f32(const float* d_x, const float* d_pe, float* d_y, int rows, int C, int period_rows, void* stream);
+/* ConvTranspose2d(Cin, Cout, kernel 2, stride 2) over pixel rows d_x [N * Gi^2][Cin]: a GEMM against d_W4 [4 Cout][Cin] (row (2 ky + kx) Cout + co
+ * = weight[ci][co][ky][kx]) into d_tmp [N * Gi^2][4 Cout], then the pixel shuffle to d_out [N][2 Gi][2 Gi][Cout] rows with the bias and what
+ * follows the convolution: mode 1 = LayerNorm2d over the channels of a pixel (d_ln_gamma / d_ln_beta, eps) then erf GELU, mode 2 = erf GELU. */
+MVE_API int mve_sam_upscale(const float* d_x, const float* d_W4, const float* d_bias, const float* d_ln_gamma, const float* d_ln_beta, float eps, float* d_tmp,
+                            float* d_out, int N, int Gi, int Cin, int Cout, int mode, void* stream);
+/* The num_mask_tokens hypernetwork MLPs and the iou head in one launch, each proj_in -> ReLU -> layers.0 -> ReLU -> proj_out (no sigmoid).
+ * MLP j < num_mask_tokens reads token 1 + j of d_queries [N][T][C] and writes d_hyper [N][num_mask_tokens][out_dim]; MLP num_mask_tokens (the iou
+ * head) reads token 0 and writes d_iou [N][num_mask_tokens].  Stacked weights, the iou head last: d_w0 [Mt+1][hidden][C], d_w1
+ * [Mt+1][hidden][hidden], d_w2 [Mt+1][out_dim][hidden] (the iou head fills its first Mt rows), biases alike.  Widths at most 512. */
+MVE_API int mve_sam_token_mlps(const float* d_queries, int N, int T, int C, int hidden, int out_dim, int num_mask_tokens, const float* d_w0, const float* d_b0,
+                               const float* d_w1, const float* d_b1, const float* d_w2, const float* d_b2, float* d_hyper, float* d_iou, void* stream);
+/* d_low_res [N][Mt][pixels] = sum_c d_hyper [N][Mt][c] * d_up [N][pixels][c], c ascending. */
+MVE_API int mve_sam_mask_product(const float* d_hyper, const float* d_up, float* d_low_res, int N, int num_mask_tokens, int Cu, int pixels, void* stream);
+/* `Sam.postprocess_masks` + threshold: d_low_res [planes][L][L] resized bilinearly (align_corners = False) to S x S, cropped to [:h_in, :w_in],
+ * resized bilinearly to (H, W) -- composed on the fly, 16 low-res reads per output pixel, no S x S buffer -- then d_masks [planes][H][W] uint8 =
+ * value > mask_threshold; d_logits (NULL or fp32 of the same shape) receives the value itself.  Bilinear rule as ATen states it:
+ * src = max((dst + 0.5) * (in / out) - 0.5, 0), i0 = floor(src), i1 = min(i0 + 1, in - 1), the scale in fp32. */
+MVE_API int mve_sam_postprocess(const float* d_low_res, int planes, int L, int S, int h_in, int w_in, int H, int W, float mask_threshold, uint8_t* d_masks,
+                                float* d_logits, void* stream);
+
 /* GroupNorm over NHWC input (optionally the channel-concat of two tensors) with optional fused SiLU (`silu` = 1) or ReLU (`silu` = 2):
  *   out[B*HW][C1+C2] = act( (x - mean_g) * rstd_g * gamma + beta ), torch.nn.GroupNorm semantics.
  * gamma/beta: [C1+C2] f32.  d_workspace: >= mve_groupnorm_workspace_bytes(B,HW,C,G) bytes.
@@ -965,7 +1024,7 @@ MVE_API int mve_loftr_forward_fine(void* handle, int N, int H, int W, int M, voi
 MVE_API int mve_loftr_destroy(void* handle);
 /* Segment Anything image encoder (segment_anything `ImageEncoderViT` = transformers `SamVisionEncoder`; the reference's
  * `predictor.model.image_encoder`, run once per request by `SamPredictor.set_image`).  The prompt encoder, the mask decoder and the mask
- * post-processing are NOT part of it.  An executor handle: parameters through mve_unet_load_param under transformers' names
+ * post-processing are NOT part of it (mve_sam_decoder_* below).  An executor handle: parameters through mve_unet_load_param under transformers' names
  * (`patch_embed.projection.*`, `pos_embed`, `layers.N.{layer_norm1,layer_norm2}.*`, `layers.N.attn.{qkv,proj}.*`,
  * `layers.N.attn.{rel_pos_h,rel_pos_w}`, `layers.N.mlp.{lin1,lin2}.*`, `neck.{conv1,conv2}.weight`, `neck.{layer_norm1,layer_norm2}.*`;
  * mvedit_amd/sam.py renames segment_anything's keys onto them).  A rel_pos table must have exactly 2n-1 rows (n = window_size, or the grid in
@@ -989,6 +1048,35 @@ MVE_API int mve_sam_encoder_plan(void* handle, int B, size_t* workspace_bytes, i
 MVE_API int mve_sam_encoder_forward(void* handle, const void* d_pixels, int B, void* d_out, void* const* d_hidden_states, void* d_workspace,
                                     size_t workspace_bytes, float* op_ms, void* stream);
 MVE_API int mve_sam_encoder_destroy(void* handle);
+/* Segment Anything prompt encoder + two-way mask decoder (transformers `SamPromptEncoder` + `SamMaskDecoder` = segment_anything's `PromptEncoder`
+ * + `MaskDecoder`; what `SamPredictor.predict` runs per prompt).  fp32 throughout; `dtype` (f16 | bf16) is the dtype of the image
+ * embedding it reads.  An executor handle: parameters through mve_unet_load_param under the names `SamModel.state_dict()` prints
+ * (`shared_image_embedding.positional_embedding`, `prompt_encoder.{point_embed.N,not_a_point_embed,no_mask_embed}.weight`,
+ * `mask_decoder.{iou_token,mask_tokens}.weight`, `mask_decoder.transformer.layers.N.{self_attn,cross_attn_token_to_image,
+ * cross_attn_image_to_token}.{q,k,v,out}_proj.*`, `...layers.N.{layer_norm1..4,mlp.lin1,mlp.lin2}.*`, `mask_decoder.transformer.
+ * {final_attn_token_to_image.*,layer_norm_final_attn.*}`, `mask_decoder.{upscale_conv1,upscale_conv2,upscale_layer_norm}.*`,
+ * `mask_decoder.{output_hypernetworks_mlps.N,iou_prediction_head}.{proj_in,layers.0,proj_out}.*`; mvedit_amd/sam.py renames segment_anything's keys
+ * onto them).  mve_sam_decoder_finalize runs mve_sam_dense_pe into the handle once the parameters are loaded; a forward before it is refused.
+ * Plan (csrc/builder_sam_decoder.h, which restates the two-way transformer): one plan serves N = B * P items (B images, P prompts per image, one
+ * prompt shape per call); mve_sam_prompt_tokens, mve_sam_src, then mve_gemm_f32 / mve_attention_f32 / mve_layernorm_f32 / mve_add_rows_f32,
+ * mve_sam_upscale twice, mve_sam_token_mlps, mve_sam_mask_product.  No host read.
+ * layer_norm_eps is that of layer_norm1..4, final_layer_norm_eps that of layer_norm_final_attn (transformers: 1e-6 / 1e-5; segment_anything: 1e-5
+ * / 1e-5).  Refused at create: hidden_size / num_heads not 32 (and hidden_size / attention_downsample_rate / num_heads not 16),
+ * attention_downsample_rate != 2, iou_head_depth != 3, iou_head_hidden_dim != hidden_size, hidden_size > 512 or not a multiple of 8,
+ * num_mask_tokens outside [1, 8], more than 8 layers, a grid above 128.  Refused at plan / forward: more than 16 tokens, no prompt, N > 128.
+ * d_embedding [B][hidden][G][G] NCHW in `dtype`; d_boxes NULL | fp32 [B*P][4] (x0, y0, x1, y1 in input-image pixels); d_points NULL | fp32
+ * [B*P][n_points][2], d_labels int32 [B*P][n_points] in {-1, 0, 1}; d_low_res fp32 [B*P][num_mask_tokens][4G][4G], d_iou fp32
+ * [B*P][num_mask_tokens] (ALL mask tokens: multimask_output selects [1:] or [:1] of them).  d_taps: NULL, or 2 * num_layers + 5 pointers, NULL
+ * entries skipped: tokens [N][T][C]; per layer queries [N][T][C], keys [N][G^2][C]; queries after the final attention; the upscaled embedding
+ * [N][16 G^2][C/8]; hyper_in [N][Mt][C/8]; the dense positional encoding [G^2][C]. */
+MVE_API int mve_sam_decoder_create(void** handle, int dtype, int hidden_size, int num_layers, int num_heads, int mlp_dim, int num_mask_tokens, int iou_head_hidden_dim,
+                                   int iou_head_depth, int attention_downsample_rate, int grid, int image_size, float layer_norm_eps, float final_layer_norm_eps);
+MVE_API int mve_sam_decoder_finalize(void* handle, void* stream);
+MVE_API int mve_sam_decoder_plan(void* handle, int B, int P, int n_points, int has_box, size_t* workspace_bytes, int* n_ops, double* flops);
+MVE_API int mve_sam_decoder_forward(void* handle, const void* d_embedding, int B, int P, const float* d_boxes, const float* d_points, const int32_t* d_labels,
+                                    int n_points, float* d_low_res, float* d_iou, void* const* d_taps, void* d_workspace, size_t workspace_bytes, float* op_ms,
+                                    void* stream);
+MVE_API int mve_sam_decoder_destroy(void* handle);
 /* LPIPS(net='vgg') perceptual loss, forward and backward w.r.t. the prediction: the `patch_loss` of the reference's reconstruct step
  * (lib/models/losses/lpips_loss.py:8-42 -> lpips==0.1.4 `LPIPS.forward`; lib/models/autoencoders/base_nerf.py:337-344, 8 patches of
  * 128 x 128 per optimisation iteration).  An executor handle: parameters through mve_unet_load_param under lpips' own state-dict

@@ -148,7 +148,7 @@ __global__ void k_group_mean(const typename Tag::T* __restrict__ x, typename Tag
 constexpr int CN_EMB[4] = {16, 32, 96, 256};      // diffusers ControlNetModel conditioning_embedding_out_channels (default)
 
 // which network a handle runs: one executor, one plan builder per kind (builder_*.h)
-enum class Kind { UNet, ControlNet, VaeDecoder, VaeEncoder, Srvgg, Lpips, ClipText, ClipVision, Resampler, Dpt, Loftr, Sam };
+enum class Kind { UNet, ControlNet, VaeDecoder, VaeEncoder, Srvgg, Lpips, ClipText, ClipVision, Resampler, Dpt, Loftr, Sam, SamDecoder };
 
 // the noun of "handle is ..., not ..." messages
 const char* kind_name(Kind k) {
@@ -164,6 +164,7 @@ const char* kind_name(Kind k) {
         case Kind::Dpt: return "a DPT model";
         case Kind::Loftr: return "a LoFTR model";
         case Kind::Sam: return "a SAM image encoder";
+        case Kind::SamDecoder: return "a SAM mask decoder";
     }
     return "an unknown engine";
 }
@@ -196,6 +197,12 @@ struct Config {
     // window_size, sm_out = output_channels (the neck's width), sm_global = bit k set: block k attends over the whole grid (global_attn_indexes)
     int sm_image = 0, sm_patch = 0, sm_window = 0, sm_out = 0;
     unsigned long long sm_global = 0;
+    // SAM prompt encoder + mask decoder (transformers SamPromptEncoder + SamMaskDecoder; builder_sam_decoder.h), fp32 throughout: ch[0] = hidden_size,
+    // heads[0], layers_per_block = num_hidden_layers of the two-way transformer, clip_inter = mlp_dim, eps = the eps of layer_norm1..4, sd_eps_final =
+    // that of layer_norm_final_attn; sd_grid = G (image_embedding_size), sd_image = the prompt encoder's input_image_size, sd_masks = num_mask_tokens;
+    // dtype = the dtype of the image embedding it reads
+    int sd_grid = 0, sd_image = 0, sd_masks = 0;
+    float sd_eps_final = 1e-5f;
     // LoFTR matcher (loftr/loftr.py with default_cfg; builder_loftr.h): a fixed topology, nothing to configure but the dtype
     int dtype, in_ch, out_ch, n_levels, layers_per_block, ctx_dim, groups, linear_proj;
     // UNet2DConditionModel / ControlNetModel addition_embed_type (mve_unet_set_addition_embed): 0 none, 1 'text_time' (SDXL);
@@ -251,6 +258,7 @@ struct Run {
     const float* add_ids = nullptr;           //              (mve_unet_bind_added_cond)
     int add_text_dtype = 0, add_text_dim = 0, add_n_ids = 0;
     int clip_eos = 0;                         // CLIP text tower: eos_token_id of this forward (pooling rule of mve_clip_pool)
+    const float* sd_boxes = nullptr; const float* sd_points = nullptr; const int32_t* sd_labels = nullptr;      // SAM decoder: the prompts of this forward (null: none)
     int loftr_M = 0, loftr_border = 2;        // LoFTR: match count of the fine call (host value), border / threshold of the coarse selection
     float loftr_thr = 0.2f;
     hipStream_t stream = nullptr;
@@ -381,6 +389,7 @@ struct Unet {
     unsigned char* ref_store = nullptr;
     size_t ref_store_bytes = 0;
     int n_ip_loaded = 0, n_xf_layers = 0;
+    bool sd_pe_ready = false;                   // SAM decoder: the dense positional encoding slot is filled (mve_sam_decoder_finalize)
     bool fuse_sc = false;                       // conv_shortcut folded into conv2's K loop (all widths multiples of 64)
     std::string err;
     // added conditions of a 'text_time' handle, bound by mve_unet_bind_added_cond (caller-owned device memory)
@@ -421,7 +430,7 @@ void enumerate(const Config& c, std::vector<ResnetDesc>& rs, std::vector<XfDesc>
     const int n = c.n_levels, L = c.layers_per_block;
     switch (c.kind) {
         case Kind::UNet: case Kind::ControlNet: case Kind::VaeDecoder: case Kind::VaeEncoder: break;      // resnets and transformers, listed below
-        default: return;     // plain conv stacks / the CLIP towers, the Resampler (builder_clip*.h), DPT (builder_dpt.h), LoFTR (builder_loftr.h), SAM (builder_sam.h)
+        default: return;     // plain conv stacks / the CLIP towers, the Resampler (builder_clip*.h), DPT (builder_dpt.h), LoFTR (builder_loftr.h), SAM (builder_sam.h, builder_sam_decoder.h)
     }
     if (c.is_vae()) {      // diffusers Encoder / Decoder (autoencoders/vae.py): resnets only, one attention in the mid block
         const int Cm = c.ch[n - 1];

@@ -612,7 +612,7 @@ struct Builder {
 
     // network-specific plan builders: build, mid_block, add_residual (builder_unet.h); vae_attention, build_vae (builder_vae.h); build_sr (builder_sr.h);
     // build_lpips (builder_lpips.h); build_clip (builder_clip.h); build_clip_vision, build_resampler (builder_clip_vision.h); build_dpt (builder_dpt.h);
-    // build_loftr (builder_loftr.h); build_sam (builder_sam.h)
+    // build_loftr (builder_loftr.h); build_sam (builder_sam.h); build_sam_decoder (builder_sam_decoder.h)
     Ref mid_block(Ref x, int C, int h, int w);
     Ref add_residual(Ref a, Ref src, int C, int h, int w, const char* label);
     Ref vae_attention(const std::string& name, Ref x, int C, int H, int W);
@@ -623,6 +623,7 @@ struct Builder {
     int build_dpt(int B_);
     int build_loftr(int N_, int H, int W, int phase);
     int build_sam(int B_);
+    int build_sam_decoder(int N_, int P, int n_points, int has_box);
     int build_sr(int B_, int H, int W, int io_dtype);
     int build_vae(int B_, int H, int W, int io_dtype);
     int build(int B_, int H, int W, int n_img, int has_res, int io_dtype, int res_nhwc);

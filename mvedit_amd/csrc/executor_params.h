@@ -261,6 +261,63 @@ void layout_params(Unet& u) {
         sb.norm("neck.layer_norm2", O);
         break;
     }
+    case Kind::SamDecoder: {
+        // the names `SamModel.state_dict()` prints (mvedit_amd/sam.py renames segment_anything's keys onto them).  EVERY slot is fp32 (vec()'s
+        // default): the slab carries fp32 slots next to 16-bit ones for every kind, so nothing changes for the others.  Linear weights stay [out][in].
+        // A ConvTranspose2d weight [Cin][Cout][2][2] becomes the GEMM operand [(2 ky + kx) Cout + co][Cin] of mve_sam_upscale.  The Mt hypernetwork
+        // MLPs and the iou head are stacked, the iou head last, in the three slots mve_sam_token_mlps reads (`mlps.w0 / w1 / w2` and biases; the iou
+        // head's proj_out fills the first Mt of its C / 8 rows, the rest stay zero).  `dense_pe` has no state-dict tensor: mve_sam_decoder_finalize
+        // computes it from the gaussian matrix.
+        const size_t C = c.ch[0], I = c.clip_inter, Mt = c.sd_masks, G = c.sd_grid, C4 = C / 4, C8 = C / 8, Ci = C / 2;
+        const std::string pe = "prompt_encoder.", md = "mask_decoder.", tf = md + "transformer.";
+        auto lin = [&](const std::string& p, size_t rows, size_t cols) { sb.vec(p + ".w", p + ".weight", rows * cols); sb.vec(p + ".b", p + ".bias", rows); };
+        auto attention = [&](const std::string& p, size_t inner) {
+            for (const char* pj : {".q_proj", ".k_proj", ".v_proj"}) lin(p + pj, inner, C);
+            lin(p + ".out_proj", C, inner);
+        };
+        sb.vec("gaussian", "shared_image_embedding.positional_embedding", C);
+        sb.add("dense_pe", G * G * C, true);
+        sb.add("point_embed", 4 * C, true);
+        for (int k = 0; k < 4; ++k) sb.part("point_embed", k * C, pe + "point_embed." + num(k) + ".weight", C, pack_flat(C));
+        sb.vec("not_a_point", pe + "not_a_point_embed.weight", C);
+        sb.vec("no_mask", pe + "no_mask_embed.weight", C);
+        sb.vec("iou_token", md + "iou_token.weight", C);
+        sb.vec("mask_tokens", md + "mask_tokens.weight", Mt * C);
+        for (int k = 0; k < c.layers_per_block; ++k) {
+            const std::string b = tf + "layers." + num(k);
+            attention(b + ".self_attn", C);
+            sb.norm(b + ".layer_norm1", C);
+            attention(b + ".cross_attn_token_to_image", Ci);
+            sb.norm(b + ".layer_norm2", C);
+            lin(b + ".mlp.lin1", I, C);
+            lin(b + ".mlp.lin2", C, I);
+            sb.norm(b + ".layer_norm3", C);
+            attention(b + ".cross_attn_image_to_token", Ci);
+            sb.norm(b + ".layer_norm4", C);
+        }
+        attention(tf + "final_attn_token_to_image", Ci);
+        sb.norm(tf + "layer_norm_final_attn", C);
+        const size_t cin[2] = {C, C4}, cout[2] = {C4, C8};
+        for (int k = 0; k < 2; ++k) {
+            const std::string u2 = md + "upscale_conv" + num(k + 1);
+            const long long ci = (long long)cin[k], co = (long long)cout[k];
+            sb.add(u2 + ".w", 4 * co * ci, true);
+            sb.part(u2 + ".w", 0, u2 + ".weight", 4 * co * ci, PackDims{{1, 4, co, ci}, {0, 1, 4, co * 4}, {0, co * ci, ci, 1}, ci});
+            sb.vec(u2 + ".b", u2 + ".bias", co);
+        }
+        sb.norm(md + "upscale_layer_norm", C4);
+        sb.add("mlps.w0", (Mt + 1) * C * C, true); sb.add("mlps.b0", (Mt + 1) * C, true);
+        sb.add("mlps.w1", (Mt + 1) * C * C, true); sb.add("mlps.b1", (Mt + 1) * C, true);
+        sb.add("mlps.w2", (Mt + 1) * C8 * C, true); sb.add("mlps.b2", (Mt + 1) * C8, true);
+        for (size_t j = 0; j <= Mt; ++j) {
+            const std::string m = j < Mt ? md + "output_hypernetworks_mlps." + num((int)j) : md + "iou_prediction_head";
+            const size_t no = j < Mt ? C8 : Mt;
+            sb.part("mlps.w0", j * C * C, m + ".proj_in.weight", C * C, pack_flat(C * C)); sb.part("mlps.b0", j * C, m + ".proj_in.bias", C, pack_flat(C));
+            sb.part("mlps.w1", j * C * C, m + ".layers.0.weight", C * C, pack_flat(C * C)); sb.part("mlps.b1", j * C, m + ".layers.0.bias", C, pack_flat(C));
+            sb.part("mlps.w2", j * C8 * C, m + ".proj_out.weight", no * C, pack_flat(no * C)); sb.part("mlps.b2", j * C8, m + ".proj_out.bias", no, pack_flat(no));
+        }
+        break;
+    }
     case Kind::Loftr: {
         // Engine-side slot names (mvedit_amd/matcher.py maps the checkpoint's keys onto them: BatchNorm folded into the convolution in front of it,
         // the 196-wide stage padded to 200 channels with zeros, k | v concatenated, conv K order): the loader converts a tensor of the slot's size.
@@ -522,6 +579,7 @@ int load_param(Unet& u, const std::string& name, const void* src, int src_dtype,
     }
     if (e.optional && !u.loaded.count(name)) ++u.n_ip_loaded;
     u.loaded[name] = true;
+    u.sd_pe_ready = false;      // the SAM decoder's dense positional encoding follows its gaussian matrix (mve_sam_decoder_finalize)
     return MVE_OK;
 }
 

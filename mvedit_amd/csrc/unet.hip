@@ -17,8 +17,8 @@
 //   * per-op HIP-event profiling and analytic FLOP accounting are built in (bench.py's roofline).
 //
 // Source layout (one translation unit): executor.h (types) -> executor_params.h (parameter slab + loader) -> executor_builder.h (plan
-// builder: arena, op recording, and every block more than one network uses) -> builder_{unet,vae,sr,lpips,clip,clip_vision,dpt,loftr,sam}.h (the plans:
-// UNet and ControlNet, the two VAE halves, SRVGG, LPIPS, CLIP text, CLIP vision and the Resampler, DPT, LoFTR, the SAM image encoder) -> this file (plan cache + C ABI).
+// builder: arena, op recording, and every block more than one network uses) -> builder_{unet,vae,sr,lpips,clip,clip_vision,dpt,loftr,sam,sam_decoder}.h (the plans:
+// UNet and ControlNet, the two VAE halves, SRVGG, LPIPS, CLIP text, CLIP vision and the Resampler, DPT, LoFTR, the SAM image encoder, the SAM mask decoder) -> this file (plan cache + C ABI).
 #include "executor_builder.h"
 #include "builder_unet.h"
 #include "builder_vae.h"
@@ -29,11 +29,13 @@
 #include "builder_dpt.h"
 #include "builder_loftr.h"
 #include "builder_sam.h"
+#include "builder_sam_decoder.h"
 
 namespace {
 
 // what a plan is built for and cached under, next to the handle's own options (AttnOpts, add_type).  The networks without conditioning use the first
-// three and io_dtype; the CLIP text tower and the Resampler put their sequence length in H, LoFTR its phase in n_img.
+// three and io_dtype; the CLIP text tower and the Resampler put their sequence length in H, LoFTR its phase in n_img, the SAM decoder its items in B, the prompts
+// per image in H, the points per prompt in W and the presence of a box in has_res.
 struct PlanKey { int B = 0, H = 0, W = 0, n_img = 1, has_res = 0, io_dtype = 0, res_nhwc = 0, ctx_len = 0; };
 
 int ensure_plan(Unet& u, const PlanKey& k) {
@@ -64,6 +66,7 @@ int ensure_plan(Unet& u, const PlanKey& k) {
         case Kind::Dpt: rc = b.build_dpt(k.B); break;
         case Kind::Loftr: rc = b.build_loftr(k.B, k.H, k.W, k.n_img); break;
         case Kind::Sam: rc = b.build_sam(k.B); break;
+        case Kind::SamDecoder: rc = b.build_sam_decoder(k.B, k.H, k.W, k.has_res); break;
     }
     if (rc != MVE_OK) return rc;
     np->ctx_len = k.ctx_len;
@@ -738,6 +741,94 @@ int mve_sam_encoder_forward(void* handle, const void* d_pixels, int B, void* d_o
 }
 
 int mve_sam_encoder_destroy(void* handle) { return mve_unet_destroy(handle); }
+
+int mve_sam_decoder_create(void** handle, int dtype, int hidden_size, int num_layers, int num_heads, int mlp_dim, int num_mask_tokens, int iou_head_hidden_dim,
+                           int iou_head_depth, int attention_downsample_rate, int grid, int image_size, float layer_norm_eps, float final_layer_norm_eps) {
+    MVE_CHECK(handle, MVE_ERR_ARG, "sam_decoder_create: null handle");
+    MVE_CHECK(dtype == MVE_F16 || dtype == MVE_BF16, MVE_ERR_ARG, "sam_decoder_create: dtype (of the image embedding) must be f16 or bf16");
+    MVE_CHECK(attention_downsample_rate == 2, MVE_ERR_ARG, "sam_decoder_create: attention_downsample_rate %d is not implemented (2: the cross-attentions run at head_dim 16)",
+              attention_downsample_rate);
+    MVE_CHECK(hidden_size >= 8 && hidden_size % 8 == 0 && hidden_size <= 512, MVE_ERR_ARG, "sam_decoder_create: hidden_size %d must be a multiple of 8, at most 512", hidden_size);
+    MVE_CHECK(num_heads >= 1 && hidden_size == num_heads * 32, MVE_ERR_ARG,
+              "sam_decoder_create: hidden_size %d / num_heads %d: the head dims must be 32 (self-attention) and 16 (cross-attention)", hidden_size, num_heads);
+    MVE_CHECK(num_layers >= 1 && num_layers <= 8, MVE_ERR_ARG, "sam_decoder_create: bad num_layers %d (1..8)", num_layers);
+    MVE_CHECK(mlp_dim >= 1, MVE_ERR_ARG, "sam_decoder_create: bad mlp_dim %d", mlp_dim);
+    MVE_CHECK(num_mask_tokens >= 1 && num_mask_tokens <= 8 && num_mask_tokens <= hidden_size / 8, MVE_ERR_ARG, "sam_decoder_create: num_mask_tokens %d must be in [1, 8]", num_mask_tokens);
+    MVE_CHECK(iou_head_depth == 3 && iou_head_hidden_dim == hidden_size, MVE_ERR_ARG,
+              "sam_decoder_create: iou head of depth %d / width %d: mve_sam_token_mlps runs it next to the hypernetwork MLPs (depth 3, width hidden_size)", iou_head_depth,
+              iou_head_hidden_dim);
+    MVE_CHECK(grid >= 1 && grid <= 128 && image_size >= 1, MVE_ERR_ARG, "sam_decoder_create: bad grid %d (1..128) / image_size %d", grid, image_size);
+    MVE_CHECK(layer_norm_eps > 0.f && final_layer_norm_eps > 0.f, MVE_ERR_ARG, "sam_decoder_create: the LayerNorm eps values must be positive");
+    Unet* u = new Unet();
+    Config& c = u->cfg;
+    c.kind = Kind::SamDecoder; c.sd_grid = grid; c.sd_image = image_size; c.sd_masks = num_mask_tokens; c.sd_eps_final = final_layer_norm_eps;
+    c.clip_inter = mlp_dim;
+    c.dtype = dtype; c.in_ch = 1; c.out_ch = 1; c.n_levels = 1; c.layers_per_block = num_layers;
+    c.ctx_dim = 8; c.groups = 1; c.eps = layer_norm_eps; c.linear_proj = 0;
+    c.ch[0] = hidden_size; c.attn[0] = 0; c.heads[0] = num_heads; c.tlayers[0] = 0;
+    layout_params(*u);
+    *handle = u;
+    return MVE_OK;
+}
+
+int mve_sam_decoder_finalize(void* handle, void* stream) {
+    Unet* u;
+    const int rc = as_engine(handle, "sam_decoder_finalize", {Kind::SamDecoder}, u);
+    if (rc) return rc;
+    char first[256];
+    const int miss = mve_unet_missing_params(handle, first, sizeof(first));
+    MVE_CHECK(miss == 0 && u->slab, MVE_ERR_STATE, "sam_decoder_finalize: %d parameters not loaded (first: %s)", miss, first);
+    const int rc2 = mve_sam_dense_pe((const float*)(u->slab + u->params["gaussian"].off), (float*)(u->slab + u->params["dense_pe"].off), u->cfg.sd_grid, u->cfg.ch[0], stream);
+    if (rc2) return rc2;
+    u->sd_pe_ready = true;
+    return MVE_OK;
+}
+
+static int sam_decoder_check(const char* who, int B, int P, int n_points, int has_box) {
+    MVE_CHECK(B >= 1 && P >= 1 && (long long)B * P <= 128, MVE_ERR_ARG, "%s: bad B %d / P %d (at most 128 items)", who, B, P);
+    MVE_CHECK(n_points >= 0 && n_points <= 16 && (has_box == 0 || has_box == 1), MVE_ERR_ARG, "%s: bad n_points %d / has_box %d", who, n_points, has_box);
+    return MVE_OK;
+}
+
+int mve_sam_decoder_plan(void* handle, int B, int P, int n_points, int has_box, size_t* workspace_bytes, int* n_ops, double* flops) {
+    Unet* u;
+    int rc = as_engine(handle, "sam_decoder_plan", {Kind::SamDecoder}, u);
+    if (rc) return rc;
+    rc = sam_decoder_check("sam_decoder_plan", B, P, n_points, has_box);
+    if (rc) return rc;
+    PlanKey k;
+    k.B = B * P; k.H = P; k.W = n_points; k.has_res = has_box; k.io_dtype = u->cfg.dtype;
+    return plan_and_report(*u, k, workspace_bytes, n_ops, flops);
+}
+
+int mve_sam_decoder_forward(void* handle, const void* d_embedding, int B, int P, const float* d_boxes, const float* d_points, const int32_t* d_labels, int n_points,
+                            float* d_low_res, float* d_iou, void* const* d_taps, void* d_workspace, size_t workspace_bytes, float* op_ms, void* stream) {
+    Unet* u;
+    const Plan* pl;
+    const int rc = begin_forward(handle, "sam_decoder_forward", {Kind::SamDecoder}, [&](const Unet& e, PlanKey& k) -> int {
+        MVE_CHECK(e.sd_pe_ready, MVE_ERR_STATE, "sam_decoder_forward: mve_sam_decoder_finalize has not run since the parameters were loaded");
+        MVE_CHECK(d_embedding && d_low_res && d_iou, MVE_ERR_ARG, "sam_decoder_forward: null pointer (d_embedding / d_low_res / d_iou)");
+        MVE_CHECK(n_points == 0 || (d_points && d_labels), MVE_ERR_ARG, "sam_decoder_forward: %d points without d_points / d_labels", n_points);
+        MVE_CHECK(n_points > 0 || (!d_points && !d_labels), MVE_ERR_ARG, "sam_decoder_forward: d_points / d_labels given with n_points 0");
+        const int rc2 = sam_decoder_check("sam_decoder_forward", B, P, n_points, d_boxes ? 1 : 0);
+        if (rc2) return rc2;
+        k.B = B * P; k.H = P; k.W = n_points; k.has_res = d_boxes ? 1 : 0; k.io_dtype = e.cfg.dtype;
+        return MVE_OK;
+    }, d_workspace, workspace_bytes, u, pl);
+    if (rc) return rc;
+    const int n_taps = 2 * u->cfg.layers_per_block + 5;
+    std::vector<void*> ptrs(1 + n_taps, nullptr);
+    ptrs[0] = d_iou;
+    if (d_taps)
+        for (int i = 0; i < n_taps; ++i) ptrs[1 + i] = d_taps[i];      // a null entry: that tap is not wanted
+    Run r = new_run(*u, d_workspace, stream);
+    r.sample = d_embedding; r.out = d_low_res;
+    r.sd_boxes = d_boxes; r.sd_points = d_points; r.sd_labels = d_labels;
+    r.cn_out = ptrs.data();
+    return run_plan_ops(*pl, r, 0, pl->ops.size(), op_ms);
+}
+
+int mve_sam_decoder_destroy(void* handle) { return mve_unet_destroy(handle); }
 
 int mve_lpips_create(void** handle, int dtype, int normalize_inputs) {
     MVE_CHECK(handle, MVE_ERR_ARG, "lpips_create: null handle");

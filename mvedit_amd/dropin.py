@@ -39,7 +39,8 @@ Not part of `install()`: `swap_text_encoder(pipe)` puts native CLIP text towers 
 `image_proj_model` of ONE object (an `IPAdapter`, a `Zero123PlusPipeline`, a `Zero123Pipeline`), on request; `swap_normal_model(pipe)` puts the
 native DPT-hybrid normal predictor (mvedit_amd/normal_model.py) behind `pipe.normal_model`, on request; `swap_matcher(runner)` puts the native
 LoFTR matcher (mvedit_amd/matcher.py) behind a loaded `runner.matcher`, on request; `swap_sam_image_encoder(runner)` puts the native SAM image
-encoder (mvedit_amd/sam.py) behind `runner.predictor.model.image_encoder`, on request (prompt encoder and mask decoder stay torch).
+encoder (mvedit_amd/sam.py) behind `runner.predictor.model.image_encoder`, on request (prompt encoder and mask decoder stay torch);
+`swap_sam_predictor(runner)` replaces the whole `runner.predictor` by the native `SamPredictorEngine`, on request.
 
 Nothing here computes: every replacement is one of the engines / mirrors INTEGRATION.md documents seam by seam, and a conversion that fails
 raises -- there is no fallback to the torch module.  `uninstall()` restores everything (tests).
@@ -317,6 +318,23 @@ def swap_sam_image_encoder(obj):
         cached = (fp, eng)
         object.__setattr__(m, '_mve_engine', cached)
     _set_instance(sam, 'image_encoder', cached[1])
+    return obj
+
+
+def swap_sam_predictor(obj):
+    """Opt-in (install() / swap_engines leave the SAM predictor alone): replaces `obj.predictor` -- the runner's `SamPredictor`
+    (lib/apis/adapter3d.py:363-372) -- by a `mvedit_amd.sam.SamPredictorEngine` built from its model: image encoder, prompt encoder, mask decoder and
+    the mask post-processing all run natively.  A `predictor` that is `None` (not loaded yet) stays `None`; `uninstall()` puts the original back.
+    Idempotent; the engine is cached on the source predictor.  `swap_sam_image_encoder` is independent of it and keeps working."""
+    from .sam import SamPredictorEngine
+    p = getattr(obj, 'predictor', None)
+    if p is None or isinstance(p, SamPredictorEngine):
+        return obj
+    cached = getattr(p, '_mve_predictor_engine', None)
+    if cached is None:
+        cached = SamPredictorEngine.from_predictor(p)
+        object.__setattr__(p, '_mve_predictor_engine', cached)
+    _set_instance(obj, 'predictor', cached)
     return obj
 
 
