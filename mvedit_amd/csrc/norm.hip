@@ -5,8 +5,10 @@
 // GroupNorm (torch.nn.GroupNorm semantics: biased variance over (C/G, H, W), eps inside the sqrt) is
 // split in three launches so that the reduction is deterministic (no float atomics):
 //   1. gn_partial : grid (split, colgroup, B); each thread owns one 8-channel chunk and walks rows,
-//                   block-reduces to per-channel (sum, sumsq) partials in fp32;
-//   2. gn_finalize: one thread per (b, group) merges partials in fp64 -> (mean, rstd);
+//                   block-reduces to per-channel (sum, sumsq) partials in fp32 -- of x - k_c, k_c = the channel's element
+//                   in the image's first row: a group whose mean is large against its spread loses no bits to the
+//                   fp32 sums (un-shifted, sumsq / n - mean^2 cancelled them: 2e-3 .. 7e-3 of the output at |mean| = 256 std);
+//   2. gn_finalize: one wave per (b, group) undoes the shift and merges the partials in fp64 -> (mean, rstd);
 //   3. gn_apply   : y = act((x-mean)*rstd*gamma + beta), optional SiLU, optional second input tensor
 //                   (the skip connection of an up block: the concatenated, normalised tensor is
 //                   written once, so the following conv reads a single dense input).
@@ -66,9 +68,26 @@ __device__ __forceinline__ void gn_load8(const GNSrc& s, int b, int r, int chunk
     }
 }
 
-template <class Tag, int GN_TX, bool PAIR = false>
-__global__ __launch_bounds__(GN_THREADS) void k_gn_partial(GNSrc s, int nsplit, float* __restrict__ partial) {
+// The shift k_c of channel c (k_gn_partial subtracts it, k_gn_finalize adds it back: both read it here, the same bits): the 16-bit element of the
+// even channel c & ~1 in the image's first row -- the same value in every split of a channel and in any batch.  With C / G even (every engine's
+// tensors) c & ~1 lies in c's group, so k_c is a sample of the group: the fp32 sums then carry |x - k_c| instead of |x|.  An atypical first element
+// (|k_c - mean| large against the group's spread) takes the sums back towards the un-shifted behaviour, never further than that distance.  One value
+// per two channels, read as the 16-bit half alone: 4 registers and no low-half load.  `shift` = 0 (C / G odd: a channel pair would straddle two
+// groups): k_c = 0, the plain sums.
+// NROWS rows are requested before the first one is summed.  The pair-reading instantiations keep 3 in flight, not 4: with the shift next to four
+// unpacked rows the 40-lane one needed 102 registers (80 before) and the pass lost 8 % with the sixth wave per SIMD; held to 80 by a launch bound
+// it spilled to scratch.  With 3 rows they take 76 registers and no scratch.  The order in which a thread sums its rows does not depend on NROWS.
+// Cost (64 images, tools/gn_pair_bench.py): plain tensors unchanged (0.100 ms at 4096 x 320); pair-reading +2 .. 4 % (0.170 -> 0.173 ms at 4096 x 320,
+// 0.462 -> 0.471 at 4096 x 960): the subtraction and one row less in flight.  bench.py's norm class 5.59 -> 5.66 ms.
+template <class Tag>
+__device__ __forceinline__ float gn_shift(const GNSrc& s, int b, int c) {
+    return Tag::to_f32(gn_chunk_ptr<Tag>(s, b, 0, c >> 3)[c & 6]);
+}
+
+template <class Tag, int GN_TX, bool PAIR = false, int NROWS = (PAIR && GN_TX != 16) ? 3 : 4>
+__global__ __launch_bounds__(GN_THREADS) void k_gn_partial(GNSrc s, int nsplit, int shift, float* __restrict__ partial) {
     constexpr int GN_TY = GN_THREADS / GN_TX;
+    constexpr int NR = NROWS;
     // partial: [B][nsplit][C][2]
     __shared__ float red[GN_TY][GN_TX][16];
     const int C = s.C1 + s.C2;
@@ -77,32 +96,38 @@ __global__ __launch_bounds__(GN_THREADS) void k_gn_partial(GNSrc s, int nsplit, 
     if (mve_second_half_skipped(s.skip_if, 2 * b >= s.B)) return;
     const int rows_per = (s.HW + nsplit - 1) / nsplit;
     const int r0 = split * rows_per, r1 = min(s.HW, r0 + rows_per);
-    float sum[8], sq[8];
+    // (two channels per packed fp32 instruction -- v_pk_add_f32 / v_pk_fma_f32: the subtraction of the shift costs the pass no issue slot)
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    f32x2 sum[4], sq[4];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { sum[e] = 0.f; sq[e] = 0.f; }
+    for (int e = 0; e < 4; ++e) { sum[e] = f32x2{0.f, 0.f}; sq[e] = f32x2{0.f, 0.f}; }
     const bool active = chunk * 8 < C;
     if (active) {
+        float k0[4];                                       // gn_shift of the chunk's four channel pairs, out of one 16-byte load
+        const typename Tag::V8 x0 = *reinterpret_cast<const typename Tag::V8*>(gn_chunk_ptr<Tag>(s, b, 0, chunk));
+#pragma unroll
+        for (int e = 0; e < 4; ++e) k0[e] = shift ? Tag::to_f32(x0[2 * e]) : 0.f;
         // four rows requested before the first one is summed (round 4: one 16-byte load in flight per thread left the pass at 3.9 TB/s); the
         // per-thread summation order over rows is unchanged: identical bits
         int r = r0 + threadIdx.y;
-        for (; r + 3 * GN_TY < r1; r += 4 * GN_TY) {
-            float v[4][8];
+        for (; r + (NR - 1) * GN_TY < r1; r += NR * GN_TY) {
+            float v[NR][8];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) gn_load8<Tag, PAIR>(s, b, r + k * GN_TY, chunk, v[k]);
+            for (int k = 0; k < NR; ++k) gn_load8<Tag, PAIR>(s, b, r + k * GN_TY, chunk, v[k]);
 #pragma unroll
-            for (int k = 0; k < 4; ++k)
+            for (int k = 0; k < NR; ++k)
 #pragma unroll
-                for (int e = 0; e < 8; ++e) { sum[e] += v[k][e]; sq[e] += v[k][e] * v[k][e]; }
+                for (int e = 0; e < 4; ++e) { const f32x2 d = f32x2{v[k][2 * e], v[k][2 * e + 1]} - f32x2{k0[e], k0[e]}; sum[e] += d; sq[e] += d * d; }
         }
         for (; r < r1; r += GN_TY) {
             float v[8];
             gn_load8<Tag, PAIR>(s, b, r, chunk, v);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) { sum[e] += v[e]; sq[e] += v[e] * v[e]; }
+            for (int e = 0; e < 4; ++e) { const f32x2 d = f32x2{v[2 * e], v[2 * e + 1]} - f32x2{k0[e], k0[e]}; sum[e] += d; sq[e] += d * d; }
         }
     }
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { red[threadIdx.y][threadIdx.x][e] = sum[e]; red[threadIdx.y][threadIdx.x][8 + e] = sq[e]; }
+    for (int e = 0; e < 8; ++e) { red[threadIdx.y][threadIdx.x][e] = sum[e >> 1][e & 1]; red[threadIdx.y][threadIdx.x][8 + e] = sq[e >> 1][e & 1]; }
     __syncthreads();
     if (threadIdx.y == 0 && active) {
         float* out = partial + (((size_t)b * nsplit + split) * C + chunk * 8) * 2;
@@ -117,20 +142,26 @@ __global__ __launch_bounds__(GN_THREADS) void k_gn_partial(GNSrc s, int nsplit, 
     }
 }
 
-__global__ void k_gn_finalize(const float* __restrict__ partial, int B, int nsplit, int C, int G, int HW, float eps,
-                              float* __restrict__ stats /* [B][G][2] mean, rstd */, const int* __restrict__ skip_if) {
-    // one wave per (b, group): lanes stride over the nsplit*cpg partials, fixed-order xor-tree merge in fp64
+template <class Tag>
+__global__ void k_gn_finalize(GNSrc s, const float* __restrict__ partial, int nsplit, int G, float eps,
+                              float* __restrict__ stats /* [B][G][2] mean, rstd */) {
+    // one wave per (b, group): lanes stride over the nsplit*cpg partials, fixed-order xor-tree merge in fp64.  A partial holds the sums of
+    // d = x - k over its n rows: sum x = sum d + n k, sum x^2 = sum d^2 + 2 k sum d + n k^2 (fp64: 2^-53 against a cancellation of mean^2 / var)
+    const int B = s.B, C = s.C1 + s.C2, HW = s.HW;
     const int i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (i >= B * G) return;
-    if (mve_second_half_skipped(skip_if, 2 * (i / G) >= B)) return;
+    if (mve_second_half_skipped(s.skip_if, 2 * (i / G) >= B)) return;
     const int lane = threadIdx.x & 63;
     const int b = i / G, g = i - b * G, cpg = C / G;
+    const int rows_per = (HW + nsplit - 1) / nsplit;
     double a = 0.0, q = 0.0;
     for (int t = lane; t < nsplit * cpg; t += 64) {
-        const int sp = t / cpg, c = t - sp * cpg;
-        const float* p = partial + (((size_t)b * nsplit + sp) * C + (size_t)g * cpg + c) * 2;
-        a += (double)p[0];
-        q += (double)p[1];
+        const int sp = t / cpg, c = t - sp * cpg, ch = g * cpg + c;
+        const float* p = partial + (((size_t)b * nsplit + sp) * C + ch) * 2;
+        const int r0 = sp * rows_per;
+        const double k = (cpg & 1) ? 0.0 : (double)gn_shift<Tag>(s, b, ch), n = (double)max(0, min(HW, r0 + rows_per) - r0), da = (double)p[0];
+        a += da + n * k;
+        q += (double)p[1] + 2.0 * k * da + n * k * k;
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) { a += __shfl_xor(a, d, 64); q += __shfl_xor(q, d, 64); }
@@ -511,15 +542,16 @@ int gn_run(const GNSrc& s, int G, float eps, const float* gamma, const float* be
         const int tx = gn_tx(C);
         const int ncg = (C / 8 + tx - 1) / tx;
         const int ns = gn_nsplit(s.B, s.HW, C);
+        const int shift = ((C / G) & 1) ? 0 : 1;      // see gn_shift
         float* partial = ws;
         float* stats = ws + (size_t)s.B * ns * C * 2;
         dim3 grid(ns, ncg, s.B), block(tx, GN_THREADS / tx);
-        if (tx == 40) k_gn_partial<Tag, 40, true><<<grid, block, 0, st>>>(s, ns, partial);
-        else if (tx == 16) k_gn_partial<Tag, 16, true><<<grid, block, 0, st>>>(s, ns, partial);
-        else if (tx == 32) k_gn_partial<Tag, 32, true><<<grid, block, 0, st>>>(s, ns, partial);
-        else k_gn_partial<Tag, 64, true><<<grid, block, 0, st>>>(s, ns, partial);
+        if (tx == 40) k_gn_partial<Tag, 40, true><<<grid, block, 0, st>>>(s, ns, shift, partial);
+        else if (tx == 16) k_gn_partial<Tag, 16, true><<<grid, block, 0, st>>>(s, ns, shift, partial);
+        else if (tx == 32) k_gn_partial<Tag, 32, true><<<grid, block, 0, st>>>(s, ns, shift, partial);
+        else k_gn_partial<Tag, 64, true><<<grid, block, 0, st>>>(s, ns, shift, partial);
         MVE_LAUNCH_CHECK();
-        k_gn_finalize<<<mve_cdiv(s.B * G, 4), 256, 0, st>>>(partial, s.B, ns, C, G, s.HW, eps, stats, s.skip_if);
+        k_gn_finalize<Tag><<<mve_cdiv(s.B * G, 4), 256, 0, st>>>(s, partial, ns, G, eps, stats);
         MVE_LAUNCH_CHECK();
         if (tx == 40) k_gn_apply<Tag, 40, true><<<grid, block, 0, st>>>(s, ns, G, stats, gamma, beta, silu, out);
         else if (tx == 16) k_gn_apply<Tag, 16, true><<<grid, block, 0, st>>>(s, ns, G, stats, gamma, beta, silu, out);
@@ -534,15 +566,16 @@ int gn_run(const GNSrc& s, int G, float eps, const float* gamma, const float* be
     const int tx = gn_tx(C);
     const int ncg = (C / 8 + tx - 1) / tx;
     const int ns = gn_nsplit(s.B, s.HW, C);
+    const int shift = ((C / G) & 1) ? 0 : 1;      // see gn_shift
     float* partial = ws;
     float* stats = ws + (size_t)s.B * ns * C * 2;
     dim3 grid(ns, ncg, s.B), block(tx, GN_THREADS / tx);
-    if (tx == 40) k_gn_partial<Tag, 40><<<grid, block, 0, st>>>(s, ns, partial);
-    else if (tx == 16) k_gn_partial<Tag, 16><<<grid, block, 0, st>>>(s, ns, partial);
-    else if (tx == 32) k_gn_partial<Tag, 32><<<grid, block, 0, st>>>(s, ns, partial);
-    else k_gn_partial<Tag, 64><<<grid, block, 0, st>>>(s, ns, partial);
+    if (tx == 40) k_gn_partial<Tag, 40><<<grid, block, 0, st>>>(s, ns, shift, partial);
+    else if (tx == 16) k_gn_partial<Tag, 16><<<grid, block, 0, st>>>(s, ns, shift, partial);
+    else if (tx == 32) k_gn_partial<Tag, 32><<<grid, block, 0, st>>>(s, ns, shift, partial);
+    else k_gn_partial<Tag, 64><<<grid, block, 0, st>>>(s, ns, shift, partial);
     MVE_LAUNCH_CHECK();
-    k_gn_finalize<<<mve_cdiv(s.B * G, 4), 256, 0, st>>>(partial, s.B, ns, C, G, s.HW, eps, stats, s.skip_if);
+    k_gn_finalize<Tag><<<mve_cdiv(s.B * G, 4), 256, 0, st>>>(s, partial, ns, G, eps, stats);
     MVE_LAUNCH_CHECK();
     if (tx == 40) k_gn_apply<Tag, 40><<<grid, block, 0, st>>>(s, ns, G, stats, gamma, beta, silu, out);
     else if (tx == 16) k_gn_apply<Tag, 16><<<grid, block, 0, st>>>(s, ns, G, stats, gamma, beta, silu, out);

@@ -234,3 +234,30 @@ def test_fine_match_on_the_golden_windows(mt, golden, case, dtype):
     print(f'fine match case {case} {dtype} M {M}: expec_f rel-L2 {e_expec:.3e} (bar {bar_expec:.3e}), offsets {e_off:.3e} (bar {bar_off:.3e})')
     assert e_expec <= bar_expec and e_off <= bar_off
     assert float(off.abs().max()) <= radius
+
+
+@pytest.mark.parametrize('dtype', DTYPES)
+def test_ln_add_on_hard_row_statistics(mt, dtype):
+    """mve_loftr_ln_add (y = x + LayerNorm(o), C = 256, 70 rows: a row tail in the last block) on the row statistics of tests/hard_stats.py -- a row mean
+    of up to 256 standard deviations, an outlier channel, constant rows, rows whose variance is below eps -- against float64 on the same 16-bit inputs,
+    per block of 64 rows, with the per-kernel bar of test_unet_ops.py; leading dimensions wider than C."""
+    import hard_stats as H
+    from mvedit_amd import _lib
+    from mvedit_amd.ops import dt
+    M, C, ld = 70, 256, 264
+    g = torch.Generator().manual_seed(9)
+    gamma, beta = (1 + 0.2 * torch.randn(C, generator=g)).cuda(), (0.2 * torch.randn(C, generator=g)).cuda()
+    x = torch.randn(M, C, generator=g).to(dtype).cuda()
+    failures = []
+    for fam in H.families(dtype):
+        o = H.make_rows(fam, M, C, dtype, 7, 'cuda')
+        ob, xb = torch.zeros(M, ld, dtype=dtype, device='cuda'), torch.zeros(M, ld, dtype=dtype, device='cuda')
+        ob[:, :C], xb[:, :C] = o.to(dtype), x
+        y = torch.full((M, ld), 7.0, dtype=dtype, device='cuda')
+        _lib.call('mve_loftr_ln_add', dt(dtype), _lib.ptr(ob), ld, _lib.ptr(xb), ld, _lib.ptr(y), ld, M, C, _lib.ptr(gamma), _lib.ptr(beta), 1e-5, _lib.stream_ptr(y.device))
+        assert bool((y[:, C:] == 7.0).all()), 'the kernel wrote outside its columns'
+        try:
+            H.check_rows('loftr_ln_add', fam, y[:, :C], x.double() + H.layernorm_ref(o, gamma, beta, 1e-5), dtype)
+        except AssertionError as e:
+            failures.append(str(e))
+    assert not failures, '\n'.join(failures)

@@ -302,3 +302,32 @@ def test_postprocess(L, S, h_in, w_in, H, W):
         check(logits, want, ref32, f'postprocess {L} -> {S} -> [{h_in}, {w_in}] -> ({H}, {W})')
         only, none = postprocess_masks(dev(low), S, (h_in, w_in), (H, W), thr, False)
         assert none is None and torch.equal(only, masks)
+
+
+def test_layernorm_f32_on_hard_row_statistics():
+    """mve_layernorm_f32 on the row statistics of tests/hard_stats.py (unrounded fp32 inputs): a row mean of up to 256 standard deviations, an outlier
+    channel, constant rows, rows whose variance is below eps.  Same bar as above: 4 x the error of torch's fp32 CPU LayerNorm against float64.
+    The constant rows of the `constant` family are held to an absolute bound instead (torch's Welford mean of equal values is exact, so a bar relative to
+    its error allows nothing there): the kernel's mean is 3 sequential adds per lane, 6 tree levels and a division, each rounding at most 2^-24 of the
+    row's value x, and a mean off by dm moves every output of the row by |g_c| dm / sqrt(var + eps) with var = 0; the last multiply-adds round the output
+    itself.  So |err[m, c]| <= 10 * 2^-24 |x_m| |g_c| / sqrt(eps) + 4 * 2^-24 |ref[m, c]|."""
+    import hard_stats as H
+    rs = np.random.RandomState(12)
+    M, C = 37, 256
+    g, b = rs.standard_normal(C), rs.standard_normal(C)
+    y = torch.empty(M, C, device='cuda')
+    for fam in H.FAMILIES:
+        x = H.make_rows(fam, M, C, None, 8).numpy()
+        const = np.zeros(M, bool)
+        if fam == 'constant':
+            const = (x == x[:, :1]).all(axis=1)
+            assert const.sum() == (M + H.SPECIAL_EVERY - 1) // H.SPECIAL_EVERY
+        for eps in (1e-5, 1e-6):
+            call('mve_layernorm_f32', dev(x), y, M, C, dev(g), dev(b), eps)
+            want, t = R.layernorm(x, g, b, eps), F.layer_norm(t32(x), (C,), t32(g), t32(b), eps)
+            check(y[torch.from_numpy(~const).cuda()], want[~const], t[torch.from_numpy(~const)], f'layernorm {fam} eps {eps}')
+            if const.any():
+                err = np.abs(y.double().cpu().numpy() - want)[const]
+                bound = 10 * 2.0 ** -24 * np.abs(x[const][:, :1].astype(np.float64)) * np.abs(g)[None, :] / np.sqrt(eps) + 4 * 2.0 ** -24 * np.abs(want[const])
+                print(f'    layernorm constant rows eps {eps}: worst err / bound {float((err / bound).max()):.3f}')
+                assert (err <= bound).all(), (fam, eps, float((err / bound).max()))
