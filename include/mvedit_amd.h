@@ -559,8 +559,8 @@ MVE_API int mve_loftr_fine_match(int dtype, const void* d_feat0, const void* d_f
  *   O[q] = softmax_k( scale * Q[q].K[k] + Q[q].rel_h[qh - kh + gh - 1] + Q[q].rel_w[qw - kw + gw - 1] ) V[k]
  * d_rel_h [2gh-1][head_dim] and d_rel_w [2gw-1][head_dim] in `dtype`, shared by every sequence and head; the UNSCALED Q multiplies them
  * (SamVisionAttention.get_decomposed_rel_pos with equal query and key grids and tables of exactly 2n-1 rows: no interpolation).
- * head_dim 64 or 80; 1 <= gh, gw <= 64 (the per-query products Q.rel_h^T, Q.rel_w^T are formed once per 64-query tile by MFMA and kept in LDS
- * as fp32: 64 x 64 needs ~100 KB of the CU's 160 KB); ldq / ldk / ldv multiples of 8.  Logits, both bias terms, maximum, exp and sum in
+ * head_dim 64 or 80; gh, gw >= 1 and gh + gw <= 128 (the per-query products Q.rel_h^T, Q.rel_w^T are formed once per 64-query tile by MFMA and
+ * kept in LDS as fp32, 2 (gh + gw) - 2 values per query: 64 x 64 needs ~100 KB of the CU's 160 KB); ldq / ldk / ldv multiples of 8.  Logits, both bias terms, maximum, exp and sum in
  * fp32 -- the bias is never rounded to 16 bit; the tail of the last 64-key tile is masked by a select (probability exactly 0, no infinity is
  * formed); both products on the MFMA, fp32 accumulation, one rounding of O.  No atomics: two runs give the same bits, and a sequence's result
  * does not depend on NS. */

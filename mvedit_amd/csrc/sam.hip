@@ -208,8 +208,8 @@ int launch_attention_relpos_hd(const void* Q, int ldq, const void* K, int ldk, c
                                int gh, int gw, int heads, float scale, hipStream_t s) {
     typedef typename Tag::T T;
     const int nqt = (gh * gw + RP_QT - 1) / RP_QT;
-    // the kernel is allowed the LDS of the largest grid (64 x 64: ~100 KB) once per device; a launch asks for what its own grid needs, so the 14 x 14
-    // windows (~48 KB) keep three blocks on a CU
+    // the kernel is allowed the LDS of the largest grid (gh + gw = 128, the table pitch of 64 x 64: ~100 KB) once per device; a launch asks for what
+    // its own grid needs, so the 14 x 14 windows (~48 KB) keep three blocks on a CU
     static bool configured[64] = {};
     int dev = 0;
     MVE_HIP(hipGetDevice(&dev));
@@ -306,7 +306,8 @@ extern "C" int mve_attention_relpos(int dtype, const void* Q, int ldq, const voi
     MVE_CHECK(dtype == MVE_F16 || dtype == MVE_BF16, MVE_ERR_ARG, "attention_relpos: dtype %d must be f16 or bf16", dtype);
     MVE_CHECK(Q && K && V && O && rel_h && rel_w, MVE_ERR_ARG, "attention_relpos: null pointer (d_Q / d_K / d_V / d_rel_h / d_rel_w / d_O)");
     MVE_CHECK(head_dim == 64 || head_dim == 80, MVE_ERR_ARG, "attention_relpos: head_dim %d must be 64 or 80", head_dim);
-    MVE_CHECK(gh >= 1 && gw >= 1 && gh <= 64 && gw <= 64, MVE_ERR_ARG, "attention_relpos: gh %d / gw %d must be in [1, 64] (the per-query bias tables live in LDS)", gh, gw);
+    MVE_CHECK(gh >= 1 && gw >= 1 && (long long)gh + gw <= 128, MVE_ERR_ARG,
+              "attention_relpos: gh %d / gw %d must be >= 1 with gh + gw <= 128 (the per-query bias tables live in LDS)", gh, gw);
     MVE_CHECK(NS >= 1 && heads >= 1, MVE_ERR_ARG, "attention_relpos: bad NS %d / heads %d", NS, heads);
     const long long L = (long long)gh * gw, width = (long long)heads * head_dim;
     MVE_CHECK((long long)NS * heads * ((L + RP_QT - 1) / RP_QT) < (1ll << 31), MVE_ERR_ARG, "attention_relpos: NS %d x heads %d overflows the grid", NS, heads);

@@ -1,6 +1,8 @@
 """Activation statistics that real checkpoints produce and `randn` does not, float64 references of the reduction ops, and the per-group check.
 
 Shared by test_norm_stress_gpu.py, test_attention_paths_gpu.py and the LayerNorm cases of test_loftr_kernels_gpu.py / test_sam_decoder_kernels_gpu.py.
+The attention inputs (families, shapes and float64 references of the causal, relative-position, linear and vision-shape attention kernels) are
+described at `attn_qkv` / `attn_case` below and shared by test_attention_stress_gpu.py and test_attention_bar_teeth.py.
 
 Input families.  `make(family, rows, C, G, dtype, seed)` returns an fp32 tensor [rows, C] already rounded to `dtype` (dtype None: left unrounded,
 to be split with ops.split_pair).  A "group" is the reduction unit: channels [g C/G, (g + 1) C/G) of every row for GroupNorm; for LayerNorm the
@@ -122,6 +124,177 @@ def attention_ref(q, k, v, B, Lq, Lk, heads, d, scale=None):
     return (p @ v).transpose(1, 2).reshape(B * Lq, heads * d)
 
 
+def _heads(t, B, L, heads, d):
+    return t.double().reshape(B, L, heads, d).transpose(1, 2)
+
+
+def causal_attention_ref(q, k, v, B, L, heads, d, scale=None):
+    """float64 causal softmax attention (query i sees keys 0..i); q / k / v [B L, heads d] -> [B L, heads d]"""
+    q, k, v = (_heads(t, B, L, heads, d) for t in (q, k, v))
+    s = q @ k.transpose(-1, -2) * (d ** -0.5 if scale is None else scale)
+    s = s.masked_fill(~torch.ones(L, L, dtype=torch.bool).tril(), float('-inf'))
+    return (softmax_ref(s) @ v).transpose(1, 2).reshape(B * L, heads * d)
+
+
+def relpos_logits(q, k, rel_h, rel_w, gh, gw, scale):
+    """q, k [..., L, d] (any float dtype: the arithmetic runs in it), rel_h [2 gh - 1, d], rel_w [2 gw - 1, d] ->
+    scale q.k + q.Rh[qh - kh + gh - 1] + q.Rw[qw - kw + gw - 1] with (qh, qw) = (q / gw, q % gw), [..., L, L]"""
+    i = torch.arange(gh * gw)
+    ih, iw = i // gw, i % gw
+    th, tw = q @ rel_h.transpose(0, 1), q @ rel_w.transpose(0, 1)                   # [..., L, 2 gh - 1], [..., L, 2 gw - 1]
+    jh = (ih[:, None] - ih[None, :] + gh - 1).expand(q.shape[:-2] + (-1, -1))
+    jw = (iw[:, None] - iw[None, :] + gw - 1).expand(q.shape[:-2] + (-1, -1))
+    return q @ k.transpose(-1, -2) * scale + th.gather(-1, jh) + tw.gather(-1, jw)
+
+
+def relpos_attention_ref(q, k, v, rel_h, rel_w, NS, gh, gw, heads, d, scale=None):
+    """float64 attention with the decomposed relative-position bias (the statement of tests/sam_rule.py's relpos_attention: the two agree, see
+    test_attention_bar_teeth.py); q / k / v [NS gh gw, heads d] -> [NS gh gw, heads d]"""
+    L = gh * gw
+    q, k, v = (_heads(t, NS, L, heads, d) for t in (q, k, v))
+    s = relpos_logits(q, k, rel_h.double(), rel_w.double(), gh, gw, d ** -0.5 if scale is None else scale)
+    return (softmax_ref(s) @ v).transpose(1, 2).reshape(NS * L, heads * d)
+
+
+def linear_attention_ref(q, k, v, B, L, S, heads, D, eps=1e-6):
+    """float64 linear attention, phi(x) = x + 1 for x > 0 and exp(x) otherwise (elu + 1); q [B L, heads D], k / v [B S, heads D] ->
+    (out [B L, heads D], KV [B heads, D D], Ksum [B heads, D])"""
+    phi = lambda t: torch.where(t > 0, t + 1, torch.exp(t.clamp(max=0)))
+    Q, K, V = phi(q.double()).reshape(B, L, heads, D), phi(k.double()).reshape(B, S, heads, D), v.double().reshape(B, S, heads, D)
+    KV = torch.einsum('nshd,nshv->nhdv', K, V)
+    Ksum = K.sum(1)
+    Z = 1 / (torch.einsum('nlhd,nhd->nlh', Q, Ksum) + eps)
+    out = torch.einsum('nlhd,nhdv,nlh->nlhv', Q, KV, Z).reshape(B * L, heads * D)
+    return out, KV.reshape(B * heads, D * D), Ksum.reshape(B * heads, D)
+
+
+# ---- attention inputs ------------------------------------------------------------------------------------------------------------------------------
+# Softmax attention (mve_attention, mve_attention_causal, mve_attention_relpos): one packed [B L, 3 C] buffer of the storage dtype, q | k | v its column
+# blocks, made from rnd(..., scale 1.5).  Every change is applied in every batch item and head.
+#   randn          the buffer as it is: the anchor
+#   spike          one query row x 6 and one key row copied from it: the logit of that pair is far above the row's others, so the running maximum
+#                  of an online softmax jumps at that key.  Non-causal: query 5, key L - 3 -- or L - 1 where L - 3 is not in the last, partly
+#                  filled tile of `tile` keys (L = 65: key 64).  Causal: the key must be visible, so query L - 2 and key L - 3
+#   large+offset   q and k x 2 (sharp rows), V + 2: an error of the denominator shows in every output element
+#   negative       q = -(|q| + 2), k = |k| + 2: every logit far below zero; a zero-padded key (logit 0) would win the maximum and the sum
+#   sink           causal only: key row 0 x 4, every query shifted by 0.5 sign(k0), V[0] x 40 -- every row puts a large share on key 0, whose value
+#                  is 40 x the others'
+# Rel-pos tables: rnd(..., scale `tables`) of the storage dtype; 0.1 (q.R of order 1) or 1.0 ('tables x1': q.R of order 10, the bias decides nearly
+# every argmax; run with the randn and the negative buffer).
+ATTN_FAMILIES = ('randn', 'spike', 'large+offset', 'negative', 'sink', 'tables x1', 'tables x1 neg')
+PLAIN_FAMILIES = ('randn', 'spike', 'large+offset')
+CAUSAL_FAMILIES = ('randn', 'spike', 'large+offset', 'negative', 'sink')
+RELPOS_FAMILIES = ('randn', 'spike', 'large+offset', 'negative', 'tables x1', 'tables x1 neg')
+LINATTN_FAMILIES = ('randn', 'keys-12', 'keys-20', 'qkv+8', 'v+32', 'outlier')
+
+
+def _rnd(shape, dtype, seed, scale):
+    from test_unet_ops import rnd
+    return rnd(shape, dtype, seed, scale)
+
+
+def spike_rows(L, causal, tile=64):
+    """(query, key) of the spike family"""
+    if causal:
+        return L - 2, L - 3
+    return 5, (L - 3 if (L - 3) // tile == (L - 1) // tile else L - 1)
+
+
+def attn_qkv(family, B, L, heads, d, dtype, seed, causal=False):
+    """packed [B L, 3 heads d] buffer of `dtype` (CPU)"""
+    C = heads * d
+    x = _rnd((B * L, 3 * C), dtype, seed, 1.5).float().reshape(B, L, 3, C)
+    q, k, v = x[:, :, 0], x[:, :, 1], x[:, :, 2]
+    base = {'tables x1': 'randn', 'tables x1 neg': 'negative'}.get(family, family)
+    if base == 'spike':
+        qi, ki = spike_rows(L, causal)
+        q[:, qi] = (q[:, qi] * 6).to(dtype).float()
+        k[:, ki] = q[:, qi]
+    elif base == 'large+offset':
+        q *= 2
+        k *= 2
+        v += 2
+    elif base == 'negative':
+        q.copy_(-(q.abs() + 2))
+        k.copy_(k.abs() + 2)
+    elif base == 'sink':
+        assert causal
+        k[:, 0] *= 4
+        q += 0.5 * torch.sign(k[:, :1])
+        v[:, 0] *= 40
+    elif base != 'randn':
+        raise ValueError(family)
+    return x.reshape(B * L, 3 * C).to(dtype)
+
+
+def relpos_tables(family, gh, gw, d, dtype, seed):
+    std = 1.0 if family.startswith('tables x1') else 0.1
+    return _rnd((2 * gh - 1, d), dtype, seed, std), _rnd((2 * gw - 1, d), dtype, seed + 1, std)
+
+
+def linattn_qkv(family, B, L, S, heads, D, dtype, seed):
+    """(ql [B L, 3 C], ks [B S, 3 C]) of `dtype` (CPU): q is the first column block of ql, k | v the second and third of ks.  z = randn:
+      randn      q = k = v = z
+      keys-12    k = 0.5 z - 12: phi(k) = 6e-6
+      keys-20    k = 0.5 z - 20: phi(k) = 2e-9, q.Ksum of the order of eps = 1e-6; elu(x) + 1 evaluated in fp32 would be 0 here
+      qkv+8      q, k, v = z + 8
+      v+32       v = 0.5 z + 32: the output is 32 +- 0.5 / sqrt(S), a ratio of two sums that share every rounding of phi
+      outlier    one q / k channel and one v channel of every head x 40"""
+    C = heads * D
+    ql, ks = _rnd((B * L, 3 * C), dtype, seed, 1.0).float(), _rnd((B * S, 3 * C), dtype, seed + 1, 1.0).float()
+    q, k, v = ql[:, :C], ks[:, C:2 * C], ks[:, 2 * C:]
+    if family in ('keys-12', 'keys-20'):
+        k.copy_(0.5 * k - float(family[5:]))
+    elif family == 'qkv+8':
+        q += 8
+        k += 8
+        v += 8
+    elif family == 'v+32':
+        v.copy_(0.5 * v + 32)
+    elif family == 'outlier':
+        h = torch.arange(heads)
+        q[:, h * D + (3 * h + 1) % D] *= 40
+        k[:, h * D + (3 * h + 1) % D] *= 40
+        v[:, h * D + (5 * h + 2) % D] *= 40
+    elif family != 'randn':
+        raise ValueError(family)
+    return ql.to(dtype), ks.to(dtype)
+
+
+# The cases of test_attention_stress_gpu.py and test_attention_bar_teeth.py.  B (or NS) = 2 and heads = 2: the head and item offsets are exercised.
+ATTN_B, ATTN_HEADS = 2, 2
+CAUSAL_L = (17, 77, 128)                                               # d = 64
+RELPOS_SHAPES = ((6, 10, 64), (10, 6, 80), (5, 13, 64), (1, 70, 80), (14, 14, 64))      # (gh, gw, d)
+LINATTN_SHAPES = ((70, 300, 32), (25, 25, 16), (99, 99, 32))           # (L, S, D)
+PLAIN_SHAPES = ((65, 64), (257, 80))                                   # (L, d) of mve_attention
+
+
+@functools.lru_cache(maxsize=None)
+def attn_case(kind, shape, family, dtype):
+    """The inputs and the float64 reference of one case, computed once per process and shared (treat as read-only).
+      'plain'   shape (L, d)        -> (qkv, ref)
+      'causal'  shape L             -> (qkv, ref)
+      'relpos'  shape (gh, gw, d)   -> (qkv, rel_h, rel_w, ref)
+      'linear'  shape (L, S, D)     -> (ql, ks, ref, KV, Ksum)"""
+    B, H = ATTN_B, ATTN_HEADS
+    if kind == 'linear':
+        L, S, D = shape
+        C = H * D
+        ql, ks = linattn_qkv(family, B, L, S, H, D, dtype, 11 + S)
+        return (ql, ks) + linear_attention_ref(ql[:, :C], ks[:, C:2 * C], ks[:, 2 * C:], B, L, S, H, D)
+    if kind == 'relpos':
+        gh, gw, d = shape
+        L, C = gh * gw, H * d
+        qkv = attn_qkv(family, B, L, H, d, dtype, 21 + L)
+        rel_h, rel_w = relpos_tables(family, gh, gw, d, dtype, 31 + L)
+        return qkv, rel_h, rel_w, relpos_attention_ref(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], rel_h, rel_w, B, gh, gw, H, d)
+    L, d = (shape, 64) if kind == 'causal' else shape
+    C = H * d
+    qkv = attn_qkv(family, B, L, H, d, dtype, 41 + L, causal=kind == 'causal')
+    f = causal_attention_ref if kind == 'causal' else (lambda q, k, v, B, L, H, d: attention_ref(q, k, v, B, L, L, H, d))
+    return qkv, f(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], B, L, H, d)
+
+
 # ---- the check -------------------------------------------------------------------------------------------------------------------------------------
 def _tol(dtype):
     from test_unet_ops import TOL
@@ -197,7 +370,8 @@ class Worst:
 
     def table(self, fams=FAMILIES):
         paths = sorted({(p, d) for p, f, d in self.t if f in fams})
-        lines = [f'{"path":46s} {"dtype":8s} ' + ' '.join(f'{f:>9s}' for f in fams)]
+        w = [max(9, len(f)) for f in fams]
+        lines = [f'{"path":46s} {"dtype":8s} ' + ' '.join(f'{f:>{n}s}' for f, n in zip(fams, w))]
         for p, d in paths:
-            lines.append(f'{p:46s} {d:8s} ' + ' '.join(f'{self.t[(p, f, d)]:9.1e}' if (p, f, d) in self.t else f'{"-":>9s}' for f in fams))
+            lines.append(f'{p:46s} {d:8s} ' + ' '.join(f'{self.t[(p, f, d)]:{n}.1e}' if (p, f, d) in self.t else f'{"-":>{n}s}' for f, n in zip(fams, w)))
         return '\n'.join(lines)

@@ -1,12 +1,15 @@
 """The CLIP text tower's kernels (csrc/clip_text.hip) through ctypes against float64 torch computations on the same 16-bit-rounded inputs.
 
-mve_attention_causal: fp16 is held to the per-kernel bar of 1e-3 rel-L2; bf16 has no bar, its error is printed (measured on an MI355X:
-see the docstring of test_causal_attention_against_float64).  The structural properties are bit-exact: row 0 is V[0], rows <= p do not depend
+mve_attention_causal: fp16 is held to the per-kernel bar of 1e-3 rel-L2, bf16 to TOL of tests/test_unet_ops.py (8e-3) on rel-L2 and on
+max|err| / max|ref| (measured on an MI355X: see the docstring of test_causal_attention_against_float64); the hard input families and the bound per
+16-row block are in tests/test_attention_stress_gpu.py.  The structural properties are bit-exact: row 0 is V[0], rows <= p do not depend
 on keys / values > p, two runs agree, an item does not depend on the batch."""
 import ctypes
 
 import pytest
 import torch
+
+from test_unet_ops import TOL
 
 pytestmark = pytest.mark.gpu
 
@@ -46,15 +49,18 @@ def _rel(a, ref):
 @pytest.mark.parametrize('dtype', [torch.float16, torch.bfloat16])
 @pytest.mark.parametrize('B,heads,L', SHAPES)
 def test_causal_attention_against_float64(lib, B, heads, L, dtype):
-    """fp16: rel-L2 <= 1e-3.  bf16: no bar, printed.  Measured on an MI355X over the six shapes: fp16 2.07e-4 ... 2.22e-4 and bf16
-    1.62e-3 ... 1.76e-3 (both exactly 0 at L = 1, where the output is V[0])."""
+    """fp16: rel-L2 <= 1e-3.  bf16: rel-L2 and max|err| / max|ref| <= 8e-3 (TOL).  Measured on an MI355X over the six shapes: fp16 2.07e-4 ...
+    2.22e-4 and bf16 1.62e-3 ... 1.76e-3 rel-L2 (both exactly 0 at L = 1, where the output is V[0])."""
     qkv = _qkv(B, heads, L, dtype)
     out = _causal(lib, qkv, B, heads, L)
     assert torch.isfinite(out.float()).all()
-    rel = _rel(out, _reference(qkv, B, heads, L))
-    print(f'causal attention {dtype} B={B} heads={heads} L={L}: rel-L2 {rel:.3e}')
+    ref = _reference(qkv, B, heads, L)
+    rel, rmax = _rel(out, ref), float((out.double().cpu() - ref).abs().max() / ref.abs().max())
+    print(f'causal attention {dtype} B={B} heads={heads} L={L}: rel-L2 {rel:.3e}, max|err| / max|ref| {rmax:.3e}')
     if dtype == torch.float16:
         assert rel <= 1e-3, rel
+    else:
+        assert rel <= TOL[dtype] and rmax <= TOL[dtype], (rel, rmax)
 
 
 @pytest.mark.parametrize('dtype', [torch.float16, torch.bfloat16])

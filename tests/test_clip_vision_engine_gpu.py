@@ -33,7 +33,7 @@ Measured on an MI355X (engine / the 16-bit CPU module, rel-L2 against float64; R
 
 hidden_states[-2] is hidden_states[1] in cases A and C and hidden_states[2] in case B; hidden_states[-1] is last_hidden_state.  The worst ratio is
 1.13 (bf16 B pooler_output), the best 0.66; hidden_states[0] (patch GEMM, embedding sum, pre_layrnorm) equals transformers' error in fp16 (ratio 1.00).
-mve_attention alone at the new shapes (tests/test_clip_vision_kernels_gpu.py): fp16 2.25e-4 .. 2.28e-4 (bar 1e-3), bf16 1.80e-3 .. 1.83e-3 (no bar).
+mve_attention alone at the new shapes (tests/test_clip_vision_kernels_gpu.py): fp16 2.25e-4 .. 2.28e-4 (bar 1e-3), bf16 1.80e-3 .. 1.83e-3 (bar 8e-3, on max|err| / max|ref| too).
 """
 import importlib.util
 import os

@@ -1,12 +1,15 @@
 """The CLIP vision tower's kernels (csrc/clip_vision.hip) through ctypes, and mve_attention at the shapes the tower and the Resampler add.
 
 mve_clip_patchify and mve_clip_vision_embed are bit-exact: the first moves data, the second rounds one fp32 sum.  mve_attention: fp16 is held to
-the per-kernel bar of 1e-3 rel-L2 against float64 torch on the same 16-bit-rounded inputs; bf16 has no bar, its error is printed (measured on an
-MI355X over the five shapes: fp16 2.25e-4 .. 2.28e-4, bf16 1.80e-3 .. 1.83e-3)."""
+the per-kernel bar of 1e-3 rel-L2 against float64 torch on the same 16-bit-rounded inputs, bf16 to TOL of tests/test_unet_ops.py (8e-3) on rel-L2
+and on max|err| / max|ref| (measured on an MI355X over the five shapes: fp16 2.25e-4 .. 2.28e-4, bf16 1.80e-3 .. 1.83e-3 rel-L2); the hard input
+families and the bound per 16-row block are in tests/test_attention_stress_gpu.py."""
 import ctypes
 
 import pytest
 import torch
+
+from test_unet_ops import TOL
 
 pytestmark = pytest.mark.gpu
 
@@ -44,6 +47,16 @@ def _rel(a, ref):
     return float((a.double().cpu() - ref).norm() / ref.norm())
 
 
+def _hold(what, out, ref, dtype):
+    """fp16: rel-L2 <= 1e-3.  bf16: rel-L2 and max|err| / max|ref| <= TOL."""
+    rel, rmax = _rel(out, ref), float((out.double().cpu() - ref).abs().max() / ref.abs().max())
+    print(f'{what}: rel-L2 {rel:.3e}, max|err| / max|ref| {rmax:.3e}')
+    if dtype == torch.float16:
+        assert rel <= 1e-3, rel
+    else:
+        assert rel <= TOL[dtype] and rmax <= TOL[dtype], (rel, rmax)
+
+
 def _sdpa64(q, k, v, B, heads, hd, scale):
     """q [B*Lq, heads*hd], k / v [B*Lk, heads*hd] (16-bit values) -> float64 [B*Lq, heads*hd]"""
     q, k, v = (t.double().cpu().reshape(B, -1, heads, hd).transpose(1, 2) for t in (q, k, v))
@@ -54,7 +67,8 @@ def _sdpa64(q, k, v, B, heads, hd, scale):
 @pytest.mark.parametrize('L,hd', [(65, 64), (257, 64), (65, 80), (257, 80)])
 def test_attention_at_the_vision_shapes(lib, L, hd, dtype):
     """Self-attention over the packed q|k|v rows as the tower's GEMM leaves them: 65 tokens (one past a 64-key tile) and 257 (ViT-*/14 at 224).
-    fp16: rel-L2 <= 1e-3.  bf16: no bar, printed.  Measured on an MI355X over the four shapes: fp16 2.25e-4 .. 2.28e-4, bf16 1.80e-3 .. 1.83e-3."""
+    fp16: rel-L2 <= 1e-3.  bf16: rel-L2 and max|err| / max|ref| <= 8e-3 (TOL).  Measured on an MI355X over the four shapes: fp16 2.25e-4 .. 2.28e-4,
+    bf16 1.80e-3 .. 1.83e-3 rel-L2."""
     B, heads = 2, 2
     C, scale = heads * hd, hd ** -0.5
     qkv = (torch.randn(B * L, 3 * C, generator=torch.Generator().manual_seed(L + hd)) * 1.5).to(dtype).cuda()
@@ -63,16 +77,14 @@ def test_attention_at_the_vision_shapes(lib, L, hd, dtype):
              heads, hd, ctypes.c_float(scale), lib.stream_ptr(out.device))
     torch.cuda.synchronize()
     assert torch.isfinite(out.float()).all()
-    rel = _rel(out, _sdpa64(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], B, heads, hd, scale))
-    print(f'attention {dtype} L={L} head_dim={hd}: rel-L2 {rel:.3e}')
-    if dtype == torch.float16:
-        assert rel <= 1e-3, rel
+    _hold(f'attention {dtype} L={L} head_dim={hd}', out, _sdpa64(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], B, heads, hd, scale), dtype)
 
 
 @pytest.mark.parametrize('dtype', [torch.float16, torch.bfloat16])
 def test_attention_at_the_resampler_shape(lib, dtype):
     """The Perceiver layer: 16 latent queries over 257 image keys and, as the second KV segment, the 16 latent keys -- equal to attention over
-    cat(x, latents).  fp16: rel-L2 <= 1e-3.  bf16: no bar, printed.  Measured on an MI355X: fp16 2.26e-4, bf16 1.80e-3."""
+    cat(x, latents).  fp16: rel-L2 <= 1e-3.  bf16: rel-L2 and max|err| / max|ref| <= 8e-3 (TOL).  Measured on an MI355X: fp16 2.26e-4, bf16 1.80e-3
+    rel-L2."""
     B, heads, hd, Lq, Lk, Lk2 = 2, 2, 64, 16, 257, 16
     inner = heads * hd
     g = torch.Generator().manual_seed(9)
@@ -85,7 +97,4 @@ def test_attention_at_the_resampler_shape(lib, dtype):
     torch.cuda.synchronize()
     assert torch.isfinite(out.float()).all()
     kv = torch.cat([kvx.reshape(B, Lk, -1), kvl.reshape(B, Lk2, -1)], 1).reshape(B * (Lk + Lk2), 2 * inner)
-    rel = _rel(out, _sdpa64(q, kv[:, :inner], kv[:, inner:], B, heads, hd, 0.125))
-    print(f'attention {dtype} Lq={Lq} Lk={Lk} Lk2={Lk2} head_dim={hd}: rel-L2 {rel:.3e}')
-    if dtype == torch.float16:
-        assert rel <= 1e-3, rel
+    _hold(f'attention {dtype} Lq={Lq} Lk={Lk} Lk2={Lk2} head_dim={hd}', out, _sdpa64(q, kv[:, :inner], kv[:, inner:], B, heads, hd, 0.125), dtype)

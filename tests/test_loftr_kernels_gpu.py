@@ -3,8 +3,9 @@
   stem rows, LeakyReLU, position add, unfold     move data or round one fp32 result: bit-exact against a numpy / torch restatement
   linear attention     (S, D) = (144, 32), (99, 32), (25, 16) -- the two golden token counts (neither a multiple of the 64-row tile, 144 two chunks
                        of 128) and the fine window -- plus (300, 32) (three chunks, a partial tile) against float64 einsum of the formula on the same
-                       16-bit inputs.  fp16 <= 1e-3 rel-L2 (the per-kernel bar); bf16 printed without a bar, as for mve_attention.  Two runs are
-                       bit-identical (fixed summation order, no float atomics).
+                       16-bit inputs.  fp16 <= 1e-3 rel-L2 (the per-kernel bar); bf16 <= 8e-3 (TOL of test_unet_ops.py) on rel-L2 and on
+                       max|err| / max|ref|.  Two runs are bit-identical (fixed summation order, no float atomics).  The hard input families
+                       (keys far below zero, offsets, outlier channels) and the bound per 16-row block: test_attention_stress_gpu.py.
   dual softmax         on the golden's float64 sim_matrix cast to fp32, against the float64 softmax product.  Bar: 4 x the error of torch's own fp32
                        CPU dual softmax (golden `dsmax_fp32_err`) -- the device exp is another approximation and the sums run in another order.
                        Case B (S = 99) runs in a buffer with leading dimension 104 whose padding holds +1e30 and must give the same bits as the
@@ -15,7 +16,7 @@
 Measured on an MI355X (rel-L2):
   linear attention (L, S, D)     (144, 144, 32)   (99, 99, 32)   (25, 25, 16)   (70, 300, 32)
     fp16 (bar 1e-3)                2.073e-4         2.122e-4       2.099e-4       2.079e-4
-    bf16 (no bar)                  1.672e-3         1.678e-3       1.687e-3       1.644e-3
+    bf16 (bar 8e-3)                1.672e-3         1.678e-3       1.687e-3       1.644e-3
     KV | Ksum, fp32                1.4e-7           1.3e-7         7.5e-8         1.1e-7
   dual softmax                   case A 5.914e-6 (bar 2.361e-5)      case B 5.580e-6 (bar 2.233e-5)
   fine match, expec_f            A fp16 5.38e-7 (bar 3.31e-6)  A bf16 4.63e-7 (2.88e-6)  B fp16 5.35e-7 (2.48e-6)  B bf16 4.64e-7 (2.97e-6)
@@ -35,6 +36,7 @@ import torch.nn.functional as F
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import loftr_rule                                      # noqa: E402
+from test_unet_ops import TOL                          # noqa: E402
 
 _spec = importlib.util.spec_from_file_location('make_loftr_golden', os.path.join(HERE, 'golden', 'make_loftr_golden.py'))
 G = importlib.util.module_from_spec(_spec)
@@ -108,10 +110,13 @@ def test_linear_attention_against_float64_einsum(mt, B, L, S, D, dtype):
     kv_ref = torch.cat([KV.reshape(B * heads, D * D), K.sum(1).reshape(B * heads, D)], 1)
     err_kv = float((kv.double().cpu() - kv_ref).norm() / kv_ref.norm())
     err = float((out.double().cpu() - ref).norm() / ref.norm())
-    print(f'linear attention {dtype} B {B} L {L} S {S} D {D}: rel-L2 {err:.3e} (KV | Ksum in fp32: {err_kv:.3e})')
+    err_max = float((out.double().cpu() - ref).abs().max() / ref.abs().max())
+    print(f'linear attention {dtype} B {B} L {L} S {S} D {D}: rel-L2 {err:.3e}, max|err| / max|ref| {err_max:.3e} (KV | Ksum in fp32: {err_kv:.3e})')
     assert err == err and err_kv <= 1e-5                               # the fp32 sums themselves: a few fp32 roundings
     if dtype == torch.float16:
         assert err <= 1e-3
+    else:
+        assert err <= TOL[dtype] and err_max <= TOL[dtype], (err, err_max)
 
 
 @pytest.mark.parametrize('case', ['A', 'B'])

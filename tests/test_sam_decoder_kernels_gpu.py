@@ -97,6 +97,29 @@ def test_attention_f32_subtracts_the_maximum(Lk):
     check(O, want, ref32, f'attention +80 / -80, Lk {Lk}')
 
 
+@pytest.mark.parametrize('Lk', [9, 300])
+def test_attention_f32_on_ascending_logits(Lk):
+    """logits strictly ascending along the keys (one q . k channel per head, 30 j / Lk on row 0, up to 2.5 x steeper on the rows below; inputs exact
+    in fp32): every key is a new maximum, so every step of the short kernel's online softmax, every per-thread step and every level of the long
+    kernel's tree merge rescales what it holds"""
+    N, heads, hd, Lq = 2, 8, 16, 7
+    D = heads * hd
+    rs = np.random.RandomState(Lk)
+    q, k = np.zeros((N, Lq, D)), np.zeros((N, Lk, D))
+    q[:, :, ::hd] = 4.0 * (1 + 0.25 * np.arange(Lq))[None, :, None]          # x scale 1/4: the logit is (1 + 0.25 row) k
+    k[:, :, ::hd] = (30.0 * np.arange(Lk) / Lk).astype(np.float32)[None, :, None]
+    v = rs.standard_normal((N, Lk, D)).astype(np.float32).astype(np.float64)
+    s = (q.reshape(N, Lq, heads, hd).transpose(0, 2, 1, 3) @ k.reshape(N, Lk, heads, hd).transpose(0, 2, 3, 1)) * hd ** -0.5
+    assert (np.diff(s, axis=-1) > 0).all()
+    want = R.attention(q, k, v, heads)
+    O = torch.empty(N, Lq, D, device='cuda')
+    call('mve_attention_f32', dev(q), D, dev(k), D, dev(v), D, O, D, N, Lq, Lk, heads, hd, float(hd ** -0.5))
+    assert bool(torch.isfinite(O).all())
+    sp = lambda t: t32(t).reshape(N, -1, heads, hd).transpose(1, 2)
+    ref32 = (torch.softmax(sp(q) @ sp(k).transpose(2, 3) * hd ** -0.5, dim=-1) @ sp(v)).transpose(1, 2).reshape(N, Lq, D)
+    check(O, want, ref32, f'attention on ascending logits, Lk {Lk}')
+
+
 # ---- GEMM -----------------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('N,K', [(128, 256), (256, 128), (2048, 256), (256, 2048), (256, 256), (128, 64)])
 @pytest.mark.parametrize('M', [1, 7, 9, 144, 4096])

@@ -25,7 +25,7 @@ Measured on an MI355X (engine / the 16-bit CPU module, rel-L2 against float64):
 The worst ratio is 1.00 (hidden_states[0]: patch GEMM and the position add round where transformers rounds), every other tensor sits at 0.70 .. 0.84
 (the module rounds q * scale, the bias and the softmax to 16 bit; the engine keeps them in fp32).  Block 1 (A) / 3 (B) is the global one.  With the
 two tables zeroed the neck output moves by 2.98e-1 (A) / 1.79e-1 (B), in the engine as in transformers' float64 module.
-mve_attention_relpos alone (tests/test_sam_kernels_gpu.py): fp16 2.23e-4 .. 2.25e-4 (bar 1e-3), bf16 1.77e-3 .. 1.78e-3 (no bar).
+mve_attention_relpos alone (tests/test_sam_kernels_gpu.py): fp16 2.23e-4 .. 2.25e-4 (bar 1e-3), bf16 1.77e-3 .. 1.78e-3 (bar 8e-3, on max|err| / max|ref| too).
 """
 import importlib.util
 import os

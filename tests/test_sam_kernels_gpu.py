@@ -4,7 +4,8 @@ mve_attention_relpos: fp16 is held to the per-kernel bar of 1e-3 rel-L2 against 
 
     softmax_k( scale q.k + q.Rh[qh - kh + gh - 1] + q.Rw[qw - kw + gw - 1] ) v
 
-on the same 16-bit-rounded inputs; bf16 has no bar, its error is printed (as for the other attention kernels).  mve_sam_window_partition /
+on the same 16-bit-rounded inputs; bf16 is held to TOL of tests/test_unet_ops.py (8e-3) on rel-L2 and on max|err| / max|ref| (as the other attention
+kernels; the hard input families and the bound per 16-row block are in tests/test_attention_stress_gpu.py).  mve_sam_window_partition /
 mve_sam_window_unpartition move data and mve_sam_pos_add rounds one fp32 sum: bit-exact.
 
 Measured on an MI355X (rel-L2 against float64):
@@ -25,6 +26,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import sam_rule as R  # noqa: E402
+from test_unet_ops import TOL  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -59,22 +61,26 @@ def _reference(qkv, rel_h, rel_w, NS, gh, gw, heads, hd):
 @pytest.mark.parametrize('NS,gh,gw,heads,hd', [(3, 14, 14, 2, 64), (1, 20, 20, 2, 80), (2, 6, 10, 1, 64), (1, 64, 64, 1, 80)])
 def test_attention_relpos_against_the_float64_rule(lib, NS, gh, gw, heads, hd, dtype):
     """The production window (196 keys: three full 64-key tiles and a tail of 4), 400 keys at head_dim 80, a non-square grid (k / gw against k % gw)
-    and the production global grid (4096 keys, 127-row tables).  fp16: rel-L2 <= 1e-3.  bf16: no bar, printed."""
+    and the production global grid (4096 keys, 127-row tables).  fp16: rel-L2 <= 1e-3.  bf16: rel-L2 and max|err| / max|ref| <= 8e-3 (TOL).  In
+    both types the output is far from the same attention without the two bias terms, which itself is far from the rule."""
     qkv, rel_h, rel_w = _inputs(NS, gh, gw, heads, hd, dtype)
     d = [t.cuda() for t in (qkv, rel_h, rel_w)]
     out = _run(lib, dtype, *d, NS, gh, gw, heads, hd)
     assert torch.isfinite(out.float()).all()
     ref = _reference(qkv, rel_h, rel_w, NS, gh, gw, heads, hd)
     got = out.double().cpu().numpy()
-    rel = float(np.linalg.norm(got - ref) / np.linalg.norm(ref))
+    rel, rmax = float(np.linalg.norm(got - ref) / np.linalg.norm(ref)), float(np.abs(got - ref).max() / np.abs(ref).max())
     # the same inputs without the two bias terms are a different function: the bar is not met by a kernel that drops them
     flat = R.relpos_attention(*(qkv[:, i * heads * hd:(i + 1) * heads * hd].double().numpy().reshape(NS, gh * gw, heads, hd) for i in range(3)),
                               np.zeros((2 * gh - 1, hd)), np.zeros((2 * gw - 1, hd)), gh, gw, hd ** -0.5).reshape(ref.shape) if gh * gw <= 400 else None
-    print(f'attention_relpos {dtype} NS={NS} grid={gh}x{gw} heads={heads} head_dim={hd}: rel-L2 {rel:.3e}')
+    print(f'attention_relpos {dtype} NS={NS} grid={gh}x{gw} heads={heads} head_dim={hd}: rel-L2 {rel:.3e}, max|err| / max|ref| {rmax:.3e}')
     if flat is not None:
         assert np.linalg.norm(flat - ref) / np.linalg.norm(ref) > 0.1
+        assert np.linalg.norm(got - flat) / np.linalg.norm(flat) > 0.1         # in both types: the kernel does not compute the bias-free function
     if dtype == torch.float16:
         assert rel <= 1e-3, rel
+    else:
+        assert rel <= TOL[dtype] and rmax <= TOL[dtype], (rel, rmax)
     assert torch.equal(out, _run(lib, dtype, *d, NS, gh, gw, heads, hd))                  # two runs give the same bits
 
 

@@ -179,7 +179,7 @@ def test_c_abi_argument_errors_name_the_argument(lib):
     bad('mve_attention_relpos', *attn(dtype=0), match='dtype')
     bad('mve_attention_relpos', *attn(rel_w=None), match='null')
     bad('mve_attention_relpos', *attn(head_dim=48), match='head_dim 48')
-    bad('mve_attention_relpos', *attn(gh=65), match='gh 65')
+    bad('mve_attention_relpos', *attn(gh=115), match='gh 115')                 # 115 + 14 > 128: the two tables of a query do not fit
     bad('mve_attention_relpos', *attn(gw=0), match='gw 0')
     bad('mve_attention_relpos', *attn(NS=0), match='NS 0')
     bad('mve_attention_relpos', *attn(ldq=100), match='ldq 100')
