@@ -813,6 +813,24 @@ MVE_API int mve_mesh_normals_forward(const float* d_verts, int V, const int32_t*
 MVE_API int mve_mesh_normals_backward(const float* d_verts, int V, const int32_t* d_faces, int F, const float* d_vn_sum, const float* d_g_vn,
                                       const float* d_g_face_normals, float* d_scratch, float* d_g_verts, void* stream);
 
+/* Capacity (host-read-free) form of the four calls above, for a mesh out of mve_dmtet_extract_n (rules: csrc/mesh_capacity_core.h).
+ * verts [v_cap,3], faces [f_cap,3]; d_live = device int32 [2] = (live vertices, live faces), clamped into [0, capacity] where it is read.
+ * Faces and vertices at or beyond the live counts contribute nothing, are never dereferenced and receive zero gradient; padded rows of
+ * face_normals and vn are written as (0, 0, 0) on every call.  The half-edge buckets are built from the live faces only, the means
+ * divide by the live counts and the loss tree runs over the live 256-vertex blocks only, in the exact call's order: the two losses
+ * equal mve_mesh_reg_forward(V = live vertices, F = live faces) bit for bit.  Zero live faces: both losses and every gradient are 0.
+ * Workspace: mve_mesh_reg_workspace_bytes(v_cap, f_cap). */
+MVE_API int mve_mesh_reg_forward_n(const float* d_verts, int v_cap, const int32_t* d_faces, int f_cap, const int32_t* d_live,
+                                   const float* d_face_normals, void* d_ws, size_t ws_bytes, float* d_losses, void* stream);
+MVE_API int mve_mesh_reg_backward_n(const float* d_verts, int v_cap, const int32_t* d_faces, int f_cap, const int32_t* d_live,
+                                    const float* d_face_normals, void* d_ws, size_t ws_bytes, const float* d_g_losses, float* d_g_verts,
+                                    float* d_g_face_normals, void* stream);
+MVE_API int mve_mesh_normals_forward_n(const float* d_verts, int v_cap, const int32_t* d_faces, int f_cap, const int32_t* d_live,
+                                       float* d_face_normals, float* d_vn_sum, float* d_vn, void* stream);
+MVE_API int mve_mesh_normals_backward_n(const float* d_verts, int v_cap, const int32_t* d_faces, int f_cap, const int32_t* d_live,
+                                        const float* d_vn_sum, const float* d_g_vn, const float* d_g_face_normals, float* d_scratch,
+                                        float* d_g_verts, void* stream);
+
 /* =========================================================================
  * 3. UNet2DCondition executor (native runtime behind the reference's UNet seam).
  *    Replaces `self.unet(sample, t, encoder_hidden_states=..., cross_attention_kwargs=...,
@@ -1345,6 +1363,10 @@ MVE_API int mve_bake_finalize(const float* d_accum, int map_size, float* d_albed
  *   box_downsample   : F.interpolate(mode='area', scale_factor=1/factor) on channel-last images (interpolate_hwc, :15-19, :380-383). */
 MVE_API size_t mve_edge_opposites_workspace_bytes(int F);
 MVE_API int mve_edge_opposites(const int32_t* d_tri, int F, int32_t* d_opp, void* d_workspace, size_t workspace_bytes, void* stream);
+/* Capacity form (csrc/mesh_capacity_core.h): tri [f_cap,3], d_live = device int32 [2] (live vertices, live faces).  The edge table takes the
+ * live faces only; rows of opp at or beyond the live face count are -1.  Workspace: mve_edge_opposites_workspace_bytes(f_cap). */
+MVE_API int mve_edge_opposites_n(const int32_t* d_tri, int f_cap, const int32_t* d_live, int32_t* d_opp, void* d_workspace,
+                                 size_t workspace_bytes, void* stream);
 MVE_API int mve_antialias(const float* d_color, int B, int H, int W, int C, const float* d_rast, const float* d_pos, int V,
                           const int32_t* d_tri, int F, const int32_t* d_opp, float* d_out, void* stream);
 MVE_API int mve_texture_bilinear(const float* d_tex, int Bt, int th, int tw, int C, const float* d_uv, const float* d_rast, int n, int h,
@@ -1367,6 +1389,20 @@ MVE_API int mve_dmtet_write(const float* d_pos, const float* d_sdf, const int32_
  * d_grad_pos [Nv,3] and d_grad_sdf [Nv] are ACCUMULATED into (float atomics; either may be NULL). */
 MVE_API int mve_dmtet_backward(const float* d_pos, const float* d_sdf, const int32_t* d_edges, size_t n_out_verts,
                                const float* d_grad_verts, float* d_grad_pos, float* d_grad_sdf, void* stream);
+/* Capacity (host-read-free) form, rules in csrc/mesh_capacity_core.h: count and write in ONE call into verts [v_cap,3], faces [f_cap,3]
+ * and (optional) edges [v_cap,2], with the passes, the rounding and the vertex / face order of mve_dmtet_count + mve_dmtet_write.
+ *   d_counts   int32 [2]  the true totals (n_verts, n_faces), also when they do not fit;
+ *   d_overflow int32 [1]  1 when n_verts > v_cap or n_faces > f_cap, else 0;
+ *   d_live     int32 [2]  (n_verts, n_faces) when nothing overflows, (0, 0) when anything does: the empty mesh, never a truncated one.
+ * Rows at and beyond the live counts are written on every call: vertices 0.0, faces (0, 0, 0), edges (0, 0).
+ * Workspace: mve_dmtet_workspace_bytes(n_verts, n_tets). */
+MVE_API int mve_dmtet_extract_n(const float* d_pos, const float* d_sdf, const int32_t* d_tets, size_t n_verts, size_t n_tets, int v_cap,
+                                int f_cap, float* d_out_verts, int32_t* d_out_faces, int32_t* d_out_edges, int32_t* d_counts,
+                                int32_t* d_live, int32_t* d_overflow, void* d_workspace, size_t workspace_bytes, void* stream);
+/* Backward over the live rows of edges [v_cap,2] / grad_verts [v_cap,3] (d_live as above; a padded (0, 0) edge is never read: its
+ * s_a - s_b is 0).  d_grad_pos / d_grad_sdf are accumulated into, as in mve_dmtet_backward. */
+MVE_API int mve_dmtet_backward_n(const float* d_pos, const float* d_sdf, const int32_t* d_edges, int v_cap, const int32_t* d_live,
+                                 const float* d_grad_verts, float* d_grad_pos, float* d_grad_sdf, void* stream);
 
 /* Backward of the render ops w.r.t. their colour-like input (mesh half): what nvdiffrast's autograd supplies
  * when the reference optimises textures / vertex colours through MeshRenderer.forward (lib/pipelines/mvedit_3d_pipeline.py:716-847,

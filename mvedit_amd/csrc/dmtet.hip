@@ -15,8 +15,16 @@
 // Two-call protocol (the output sizes are data dependent, like march_rays_train): mve_dmtet_count -> host reads
 // (n_verts, n_faces) -> mve_dmtet_write into exactly sized buffers; the workspace carries the state between the calls.
 // Compiled with -ffp-contract=off: the interpolation must round like the reference's separate mul / add / div.
+//
+// Capacity form (mve_dmtet_extract_n, mve_dmtet_backward_n; rules in mesh_capacity_core.h): the same passes in ONE call into buffers of
+// caller-chosen size, the totals, the live counts and an overflow flag left in device memory, the rows beyond the live counts padded.
+// The write kernels take a row limit (capacity + device count); the exact form passes "no limit", a null count.
+#include <limits.h>
+
 #include "common.h"
 #include "scan.h"
+
+#include "mesh_capacity_core.h"
 
 namespace {
 
@@ -83,14 +91,17 @@ __global__ __launch_bounds__(DB) void k_bucket_unique(const int* __restrict__ ba
 
 __global__ __launch_bounds__(DB) void k_interp_verts(const float* __restrict__ pos, const float* __restrict__ sdf, const int* __restrict__ base,
                                                      const int* __restrict__ uniq, const int* __restrict__ ubase, const int* __restrict__ bucket,
-                                                     int Nv, float* __restrict__ verts, int32_t* __restrict__ edges) {
+                                                     int Nv, float* __restrict__ verts, int32_t* __restrict__ edges, int row_cap,
+                                                     const int32_t* __restrict__ row_live) {
     const int a = blockIdx.x * DB + threadIdx.x;
     if (a >= Nv) return;
+    const int lim = mcap_live(row_cap, row_live);
     const int m = uniq[a];
     const int* b = bucket + base[a];
     const float sa = sdf[a];
     for (int j = 0; j < m; ++j) {
         const int vb = b[j];
+        if (ubase[a] + j >= lim) break;                       // capacity form: rows beyond the live count belong to the padding
         // edges_to_interp_sdf = [s_a, -s_b]; denominator = s_a - s_b; weights = flip / denominator  (:170-176)
         const float nb = sdf[vb] * -1.0f;
         const float den = sa + nb;
@@ -108,7 +119,7 @@ __global__ __launch_bounds__(DB) void k_emit_faces(const float* __restrict__ sdf
                                                    const unsigned long long* __restrict__ tri_off, unsigned long long tri_total_unused,
                                                    const unsigned long long* __restrict__ tri_total, const int* __restrict__ base,
                                                    const int* __restrict__ uniq, const int* __restrict__ ubase, const int* __restrict__ bucket,
-                                                   int32_t* __restrict__ faces) {
+                                                   int32_t* __restrict__ faces, int row_cap, const int32_t* __restrict__ row_live) {
     const size_t t = (size_t)blockIdx.x * DB + threadIdx.x;
     if (t >= Nt) return;
     int v[4];
@@ -119,6 +130,7 @@ __global__ __launch_bounds__(DB) void k_emit_faces(const float* __restrict__ sdf
     const unsigned long long off = tri_off[t];
     const unsigned n1 = (unsigned)(*tri_total & 0xffffffffull);
     const size_t row = nt == 1 ? (size_t)(off & 0xffffffffull) : (size_t)n1 + 2 * (size_t)(off >> 32);
+    if (!mcap_rows_fit(row, (uint32_t)nt, mcap_live(row_cap, row_live))) return;
     for (int k = 0; k < 3 * nt; ++k) {
         const int e = c_tri_table[code][k];
         const int ia = c_edge_a[e], ib = c_edge_b[e];
@@ -133,10 +145,10 @@ __global__ __launch_bounds__(DB) void k_emit_faces(const float* __restrict__ sdf
 // d verts -> d pos, d sdf.  v = pa * wa + pb * wb, wa = -sb / (sa - sb), wb = sa / (sa - sb)  (base_mesh_renderer.py:170-176), so
 //   d pa = wa g,  d pb = wb g,  d sa = sb (g . (pa - pb)) / (sa - sb)^2,  d sb = -sa (g . (pa - pb)) / (sa - sb)^2.
 __global__ __launch_bounds__(DB) void k_dmtet_backward(const float* __restrict__ pos, const float* __restrict__ sdf, const int32_t* __restrict__ edges,
-                                                       int n_out, const float* __restrict__ g_verts, float* __restrict__ g_pos,
-                                                       float* __restrict__ g_sdf) {
+                                                       int n_out, const int32_t* __restrict__ n_live, const float* __restrict__ g_verts,
+                                                       float* __restrict__ g_pos, float* __restrict__ g_sdf) {
     const int k = blockIdx.x * DB + threadIdx.x;
-    if (k >= n_out) return;
+    if (k >= mcap_live(n_out, n_live)) return;                // a padded (0, 0) edge has sa - sb = 0: never read
     const int a = edges[2 * k], b = edges[2 * k + 1];
     const float sa = sdf[a], sb = sdf[b];
     const float den = sa - sb, wa = -sb / den, wb = sa / den;
@@ -186,6 +198,29 @@ __global__ void k_dmtet_counts(const int* __restrict__ n_verts, const unsigned l
     }
 }
 
+// capacity form: counts [2] (the totals mve_dmtet_count wrote) -> live [2], overflow [1]
+__global__ void k_dmtet_resolve(const int32_t* __restrict__ counts, int v_cap, int f_cap, int32_t* __restrict__ live, int32_t* __restrict__ overflow) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        int32_t c[2];
+        mcap_resolve(counts[0], counts[1], v_cap, f_cap, c, live, overflow);
+    }
+}
+
+// capacity form: the rows at and beyond the live counts
+__global__ __launch_bounds__(DB) void k_dmtet_pad(float* __restrict__ verts, int32_t* __restrict__ edges, int32_t* __restrict__ faces, int v_cap,
+                                                  int f_cap, const int32_t* __restrict__ live) {
+    const int i = blockIdx.x * DB + threadIdx.x;
+    if (i < v_cap && i >= mcap_live(v_cap, live)) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) verts[3ll * i + k] = MVE_MCAP_PAD_VERT;
+        if (edges) { edges[2ll * i] = MVE_MCAP_PAD_INDEX; edges[2ll * i + 1] = MVE_MCAP_PAD_INDEX; }
+    }
+    if (i < f_cap && i >= mcap_live(f_cap, live + 1)) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) faces[3ll * i + k] = MVE_MCAP_PAD_INDEX;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -230,11 +265,13 @@ int mve_dmtet_write(const float* d_pos, const float* d_sdf, const int32_t* d_tet
     Layout L = layout(d_workspace, n_verts, n_tets);
     const unsigned gt = (unsigned)((n_tets + DB - 1) / DB), gv = (unsigned)((n_verts + DB - 1) / DB);
     if (d_out_verts || d_out_edges) {
-        k_interp_verts<<<gv, DB, 0, s>>>(d_pos, d_sdf, L.base, L.uniq, L.ubase, L.bucket, (int)n_verts, d_out_verts, d_out_edges);
+        k_interp_verts<<<gv, DB, 0, s>>>(d_pos, d_sdf, L.base, L.uniq, L.ubase, L.bucket, (int)n_verts, d_out_verts, d_out_edges, INT_MAX,
+                                           nullptr);
         MVE_LAUNCH_CHECK();
     }
     if (d_out_faces) {
-        k_emit_faces<<<gt, DB, 0, s>>>(d_sdf, d_tets, n_tets, L.off, 0ull, L.total_u64, L.base, L.uniq, L.ubase, L.bucket, d_out_faces);
+        k_emit_faces<<<gt, DB, 0, s>>>(d_sdf, d_tets, n_tets, L.off, 0ull, L.total_u64, L.base, L.uniq, L.ubase, L.bucket, d_out_faces, INT_MAX,
+                                         nullptr);
         MVE_LAUNCH_CHECK();
     }
     return MVE_OK;
@@ -244,8 +281,43 @@ int mve_dmtet_backward(const float* d_pos, const float* d_sdf, const int32_t* d_
                        float* d_grad_pos, float* d_grad_sdf, void* stream) {
     if (n_out_verts == 0) return MVE_OK;
     MVE_CHECK(d_pos && d_sdf && d_edges && d_grad_verts && (d_grad_pos || d_grad_sdf), MVE_ERR_ARG, "dmtet_backward: null pointer");
-    k_dmtet_backward<<<(unsigned)((n_out_verts + DB - 1) / DB), DB, 0, (hipStream_t)stream>>>(d_pos, d_sdf, d_edges, (int)n_out_verts, d_grad_verts,
-                                                                                               d_grad_pos, d_grad_sdf);
+    k_dmtet_backward<<<(unsigned)((n_out_verts + DB - 1) / DB), DB, 0, (hipStream_t)stream>>>(d_pos, d_sdf, d_edges, (int)n_out_verts, nullptr,
+                                                                                               d_grad_verts, d_grad_pos, d_grad_sdf);
+    MVE_LAUNCH_CHECK();
+    return MVE_OK;
+}
+
+int mve_dmtet_extract_n(const float* d_pos, const float* d_sdf, const int32_t* d_tets, size_t n_verts, size_t n_tets, int v_cap, int f_cap,
+                        float* d_out_verts, int32_t* d_out_faces, int32_t* d_out_edges, int32_t* d_counts, int32_t* d_live, int32_t* d_overflow,
+                        void* d_workspace, size_t workspace_bytes, void* stream) {
+    MVE_CHECK(v_cap > 0 && f_cap > 0, MVE_ERR_ARG, "dmtet_extract_n: capacities must be positive (v_cap=%d f_cap=%d)", v_cap, f_cap);
+    MVE_CHECK(d_out_verts && d_out_faces && d_counts && d_live && d_overflow, MVE_ERR_ARG, "dmtet_extract_n: null output");
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = mve_dmtet_count(d_sdf, d_tets, n_verts, n_tets, d_counts, d_workspace, workspace_bytes, stream)) return rc;
+    k_dmtet_resolve<<<1, 64, 0, s>>>(d_counts, v_cap, f_cap, d_live, d_overflow);
+    MVE_LAUNCH_CHECK();
+    if (n_tets != 0 && n_verts != 0) {
+        MVE_CHECK(d_pos, MVE_ERR_ARG, "dmtet_extract_n: null pointer");
+        Layout L = layout(d_workspace, n_verts, n_tets);
+        const unsigned gt = (unsigned)((n_tets + DB - 1) / DB), gv = (unsigned)((n_verts + DB - 1) / DB);
+        k_interp_verts<<<gv, DB, 0, s>>>(d_pos, d_sdf, L.base, L.uniq, L.ubase, L.bucket, (int)n_verts, d_out_verts, d_out_edges, v_cap, d_live);
+        MVE_LAUNCH_CHECK();
+        k_emit_faces<<<gt, DB, 0, s>>>(d_sdf, d_tets, n_tets, L.off, 0ull, L.total_u64, L.base, L.uniq, L.ubase, L.bucket, d_out_faces, f_cap,
+                                       d_live + 1);
+        MVE_LAUNCH_CHECK();
+    }
+    const int rows = v_cap > f_cap ? v_cap : f_cap;
+    k_dmtet_pad<<<(unsigned)((rows + DB - 1) / DB), DB, 0, s>>>(d_out_verts, d_out_edges, d_out_faces, v_cap, f_cap, d_live);
+    MVE_LAUNCH_CHECK();
+    return MVE_OK;
+}
+
+int mve_dmtet_backward_n(const float* d_pos, const float* d_sdf, const int32_t* d_edges, int v_cap, const int32_t* d_live,
+                         const float* d_grad_verts, float* d_grad_pos, float* d_grad_sdf, void* stream) {
+    MVE_CHECK(v_cap > 0, MVE_ERR_ARG, "dmtet_backward_n: capacity must be positive");
+    MVE_CHECK(d_pos && d_sdf && d_edges && d_live && d_grad_verts && (d_grad_pos || d_grad_sdf), MVE_ERR_ARG, "dmtet_backward_n: null pointer");
+    k_dmtet_backward<<<(unsigned)((v_cap + DB - 1) / DB), DB, 0, (hipStream_t)stream>>>(d_pos, d_sdf, d_edges, v_cap, d_live, d_grad_verts, d_grad_pos,
+                                                                                         d_grad_sdf);
     MVE_LAUNCH_CHECK();
     return MVE_OK;
 }

@@ -10,6 +10,10 @@
 #include "scan.h"
 
 #include "mesh_reg_core.h"
+#include "mesh_capacity_core.h"
+
+// Capacity form (the _n entry points; rules in mesh_capacity_core.h): V and F are the capacities of the buffers and live [2] = (live
+// vertices, live faces) sits in device memory.  Every kernel below takes that pointer; null is the exact form, every row live.
 
 namespace {
 
@@ -42,16 +46,16 @@ Ws carve(void* ws, size_t V, size_t F) {
     return w;
 }
 
-__global__ __launch_bounds__(NT) void k_mr_count(const int32_t* __restrict__ faces, int F, int* __restrict__ cnt) {
+__global__ __launch_bounds__(NT) void k_mr_count(const int32_t* __restrict__ faces, int F, const int32_t* __restrict__ live, int* __restrict__ cnt) {
     const int t = blockIdx.x * NT + threadIdx.x;
-    if (t >= F) return;
+    if (t >= mcap_live(F, live ? live + 1 : nullptr)) return;
     for (int k = 0; k < 3; ++k) atomicAdd(cnt + faces[3 * t + k], 2);
 }
 
-__global__ __launch_bounds__(NT) void k_mr_fill(const int32_t* __restrict__ faces, int F, const int* __restrict__ base, int* __restrict__ fill,
-                                                uint64_t* __restrict__ bucket) {
+__global__ __launch_bounds__(NT) void k_mr_fill(const int32_t* __restrict__ faces, int F, const int32_t* __restrict__ live, const int* __restrict__ base,
+                                                int* __restrict__ fill, uint64_t* __restrict__ bucket) {
     const int t = blockIdx.x * NT + threadIdx.x;
-    if (t >= F) return;
+    if (t >= mcap_live(F, live ? live + 1 : nullptr)) return;
     const int v[3] = {faces[3 * t], faces[3 * t + 1], faces[3 * t + 2]};
     for (int k = 0; k < 3; ++k) {
         const int a = v[k], b = v[(k + 1) % 3], side = a > b ? 1 : 0;
@@ -60,12 +64,13 @@ __global__ __launch_bounds__(NT) void k_mr_fill(const int32_t* __restrict__ face
     }
 }
 
-__global__ __launch_bounds__(NT) void k_mr_vertex_fwd(const float* __restrict__ verts, int V, const float* __restrict__ face_normals, Ws w) {
+__global__ __launch_bounds__(NT) void k_mr_vertex_fwd(const float* __restrict__ verts, int V, const int32_t* __restrict__ live,
+                                                      const float* __restrict__ face_normals, Ws w) {
     __shared__ float sh[NT];
     const int i = blockIdx.x * NT + threadIdx.x;
     float lap = 0.f, nc = 0.f;
     int ne = 0;
-    if (i < V) {
+    if (i < mcap_live(V, live)) {
         uint64_t* b = w.bucket + w.base[i];
         mr_sort(b, w.cnt[i]);
         lap = mr_vertex_fwd(i, b, w.cnt[i], verts, face_normals, w.u + 3 * i, &nc, &ne);
@@ -74,12 +79,14 @@ __global__ __launch_bounds__(NT) void k_mr_vertex_fwd(const float* __restrict__ 
     if (threadIdx.x == 0) { w.part[blockIdx.x] = s0; w.part[w.nbv + blockIdx.x] = s1; w.ne_part[blockIdx.x] = (int)s2; }
 }
 
-__global__ __launch_bounds__(NT) void k_mr_reduce(Ws w, int V, float* __restrict__ losses) {
+__global__ __launch_bounds__(NT) void k_mr_reduce(Ws w, int V, const int32_t* __restrict__ live, float* __restrict__ losses) {
     __shared__ float sh[NT];
     __shared__ int shi[NT];
     float a = 0.f, b = 0.f;
     int e = 0;
-    for (unsigned c = threadIdx.x; c < w.nbv; c += NT) { a += w.part[c]; b += w.part[w.nbv + c]; e += w.ne_part[c]; }
+    V = mcap_live(V, live);                                 // the mean divides by the live count, the tree walks the live blocks only
+    const unsigned nb = mcap_blocks(V, NT);
+    for (unsigned c = threadIdx.x; c < nb; c += NT) { a += w.part[c]; b += w.part[w.nbv + c]; e += w.ne_part[c]; }
     const float lap = mve_block_sum<NT>(a, sh), nc = mve_block_sum<NT>(b, sh);
     shi[threadIdx.x] = e;
     __syncthreads();
@@ -90,15 +97,20 @@ __global__ __launch_bounds__(NT) void k_mr_reduce(Ws w, int V, float* __restrict
     if (threadIdx.x == 0) {
         const int E = shi[0];
         w.total[1] = E;
-        losses[0] = lap / (float)V;
+        losses[0] = V > 0 ? lap / (float)V : 0.f;
         losses[1] = E > 0 ? nc / (float)E : 0.f;
     }
 }
 
-__global__ __launch_bounds__(NT) void k_mr_vertex_bwd(int V, const float* __restrict__ face_normals, Ws w, const float* __restrict__ d_gl,
-                                                      float* __restrict__ g_verts, float* __restrict__ g_fn) {
+__global__ __launch_bounds__(NT) void k_mr_vertex_bwd(int V, const int32_t* __restrict__ live, const float* __restrict__ face_normals, Ws w,
+                                                      const float* __restrict__ d_gl, float* __restrict__ g_verts, float* __restrict__ g_fn) {
     const int i = blockIdx.x * NT + threadIdx.x;
     if (i >= V) return;
+    V = mcap_live(V, live);
+    if (i >= V) {                                           // a padded vertex receives zero gradient
+        for (int k = 0; k < 3; ++k) g_verts[3 * i + k] = 0.f;
+        return;
+    }
     const float gl_lap = d_gl ? d_gl[0] : 1.0f, gl_nc = d_gl ? d_gl[1] : 1.0f;
     const int E = w.total[1];
     const uint64_t* b = w.bucket + w.base[i];
@@ -108,35 +120,107 @@ __global__ __launch_bounds__(NT) void k_mr_vertex_bwd(int V, const float* __rest
 
 // ---- Mesh.auto_normal -------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(NT) void k_mn_face_fwd(const float* __restrict__ verts, const int32_t* __restrict__ faces, int F,
-                                                    float* __restrict__ face_normals, float* __restrict__ vn_sum) {
+                                                    const int32_t* __restrict__ live, float* __restrict__ face_normals, float* __restrict__ vn_sum) {
     const int t = blockIdx.x * NT + threadIdx.x;
-    if (t < F) mr_normals_face_fwd(verts, faces, t, face_normals, vn_sum);
+    if (t >= F) return;
+    if (t < mcap_live(F, live ? live + 1 : nullptr)) mr_normals_face_fwd(verts, faces, t, face_normals, vn_sum);
+    else for (int k = 0; k < 3; ++k) face_normals[3 * t + k] = MVE_MCAP_PAD_NORMAL;
 }
 
-__global__ __launch_bounds__(NT) void k_mn_vertex_fwd(int V, const float* __restrict__ vn_sum, float* __restrict__ vn) {
+__global__ __launch_bounds__(NT) void k_mn_vertex_fwd(int V, const int32_t* __restrict__ live, const float* __restrict__ vn_sum, float* __restrict__ vn) {
     const int i = blockIdx.x * NT + threadIdx.x;
     if (i >= V) return;
+    if (i >= mcap_live(V, live)) {
+        for (int k = 0; k < 3; ++k) vn[3 * i + k] = MVE_MCAP_PAD_NORMAL;
+        return;
+    }
     const float l = sqrtf(mr_dot3(vn_sum + 3 * i, vn_sum + 3 * i)), inv = 1.0f / fmaxf(l, 1e-12f);
     for (int k = 0; k < 3; ++k) vn[3 * i + k] = vn_sum[3 * i + k] * inv;
 }
 
-__global__ __launch_bounds__(NT) void k_mn_vertex_bwd(int V, const float* __restrict__ vn_sum, const float* __restrict__ g_vn, float* __restrict__ g_sum) {
+__global__ __launch_bounds__(NT) void k_mn_vertex_bwd(int V, const int32_t* __restrict__ live, const float* __restrict__ vn_sum, const float* __restrict__ g_vn,
+                                                      float* __restrict__ g_sum) {
     const int i = blockIdx.x * NT + threadIdx.x;
     if (i >= V) return;
+    if (i >= mcap_live(V, live)) {
+        for (int k = 0; k < 3; ++k) g_sum[3 * i + k] = 0.f;
+        return;
+    }
     const float zero[3] = {0.f, 0.f, 0.f};
     mr_normalize_bwd(vn_sum + 3 * i, g_vn ? g_vn + 3 * i : zero, g_sum + 3 * i);
 }
 
 __global__ __launch_bounds__(NT) void k_mn_face_bwd(const float* __restrict__ verts, const int32_t* __restrict__ faces, int F,
-                                                    const float* __restrict__ g_fn_ext, const float* __restrict__ g_sum, float* __restrict__ g_verts) {
+                                                    const int32_t* __restrict__ live, const float* __restrict__ g_fn_ext,
+                                                    const float* __restrict__ g_sum, float* __restrict__ g_verts) {
     const int t = blockIdx.x * NT + threadIdx.x;
-    if (t < F) mr_normals_face_bwd(verts, faces, t, g_fn_ext, g_sum, g_verts);
+    if (t < mcap_live(F, live ? live + 1 : nullptr)) mr_normals_face_bwd(verts, faces, t, g_fn_ext, g_sum, g_verts);
 }
 
 int check(const char* who, const float* verts, int V, const int32_t* faces, int F, const float* fn, const void* ws, size_t ws_bytes) {
     MVE_CHECK(verts && faces && fn && ws, MVE_ERR_ARG, "%s: null pointer", who);
     MVE_CHECK(V > 0 && F > 0 && (long long)F * 6 < (1ll << 31), MVE_ERR_ARG, "%s: bad mesh size V=%d F=%d", who, V, F);
     MVE_CHECK(ws_bytes >= ws_bytes_of(V, F), MVE_ERR_ARG, "%s: workspace %zu < %zu bytes", who, ws_bytes, ws_bytes_of(V, F));
+    return MVE_OK;
+}
+
+// the four operations, exact (live == nullptr) and capacity form (live = device int32 [2], V / F the capacities) in one body each
+int reg_forward(const char* who, const float* d_verts, int V, const int32_t* d_faces, int F, const int32_t* d_live, const float* d_face_normals,
+                void* d_ws, size_t ws_bytes, float* d_losses, void* stream) {
+    if (int rc = check(who, d_verts, V, d_faces, F, d_face_normals, d_ws, ws_bytes)) return rc;
+    MVE_CHECK(d_losses, MVE_ERR_ARG, "%s: null output", who);
+    hipStream_t s = (hipStream_t)stream;
+    const Ws w = carve(d_ws, V, F);
+    MVE_HIP(hipMemsetAsync(w.cnt, 0, sizeof(int) * (size_t)V, s));
+    MVE_HIP(hipMemsetAsync(w.fill, 0, sizeof(int) * (size_t)V, s));
+    const unsigned nbf = mve_cdiv(F, NT);
+    k_mr_count<<<nbf, NT, 0, s>>>(d_faces, F, d_live, w.cnt);
+    MVE_LAUNCH_CHECK();
+    if (int rc = exclusive_scan<int>(w.cnt, w.base, (size_t)V, w.tile, w.total, s)) { mve_set_error("%s: scan launch failed", who); return rc; }
+    k_mr_fill<<<nbf, NT, 0, s>>>(d_faces, F, d_live, w.base, w.fill, w.bucket);
+    MVE_LAUNCH_CHECK();
+    k_mr_vertex_fwd<<<w.nbv, NT, 0, s>>>(d_verts, V, d_live, d_face_normals, w);
+    MVE_LAUNCH_CHECK();
+    k_mr_reduce<<<1, NT, 0, s>>>(w, V, d_live, d_losses);
+    MVE_LAUNCH_CHECK();
+    return MVE_OK;
+}
+
+int reg_backward(const char* who, const float* d_verts, int V, const int32_t* d_faces, int F, const int32_t* d_live, const float* d_face_normals,
+                 void* d_ws, size_t ws_bytes, const float* d_g_losses, float* d_g_verts, float* d_g_face_normals, void* stream) {
+    if (int rc = check(who, d_verts, V, d_faces, F, d_face_normals, d_ws, ws_bytes)) return rc;
+    MVE_CHECK(d_g_verts && d_g_face_normals, MVE_ERR_ARG, "%s: null output", who);
+    hipStream_t s = (hipStream_t)stream;
+    const Ws w = carve(d_ws, V, F);
+    MVE_HIP(hipMemsetAsync(d_g_face_normals, 0, sizeof(float) * 3 * (size_t)F, s));
+    k_mr_vertex_bwd<<<w.nbv, NT, 0, s>>>(V, d_live, d_face_normals, w, d_g_losses, d_g_verts, d_g_face_normals);
+    MVE_LAUNCH_CHECK();
+    return MVE_OK;
+}
+
+int normals_forward(const char* who, const float* d_verts, int V, const int32_t* d_faces, int F, const int32_t* d_live, float* d_face_normals,
+                    float* d_vn_sum, float* d_vn, void* stream) {
+    MVE_CHECK(d_verts && d_faces && d_face_normals && d_vn_sum && d_vn, MVE_ERR_ARG, "%s: null pointer", who);
+    MVE_CHECK(V > 0 && F > 0, MVE_ERR_ARG, "%s: bad mesh size V=%d F=%d", who, V, F);
+    hipStream_t s = (hipStream_t)stream;
+    MVE_HIP(hipMemsetAsync(d_vn_sum, 0, sizeof(float) * 3 * (size_t)V, s));
+    k_mn_face_fwd<<<mve_cdiv(F, NT), NT, 0, s>>>(d_verts, d_faces, F, d_live, d_face_normals, d_vn_sum);
+    MVE_LAUNCH_CHECK();
+    k_mn_vertex_fwd<<<mve_cdiv(V, NT), NT, 0, s>>>(V, d_live, d_vn_sum, d_vn);
+    MVE_LAUNCH_CHECK();
+    return MVE_OK;
+}
+
+int normals_backward(const char* who, const float* d_verts, int V, const int32_t* d_faces, int F, const int32_t* d_live, const float* d_vn_sum,
+                     const float* d_g_vn, const float* d_g_face_normals, float* d_scratch, float* d_g_verts, void* stream) {
+    MVE_CHECK(d_verts && d_faces && d_vn_sum && d_scratch && d_g_verts, MVE_ERR_ARG, "%s: null pointer", who);
+    MVE_CHECK(V > 0 && F > 0, MVE_ERR_ARG, "%s: bad mesh size V=%d F=%d", who, V, F);
+    hipStream_t s = (hipStream_t)stream;
+    MVE_HIP(hipMemsetAsync(d_g_verts, 0, sizeof(float) * 3 * (size_t)V, s));
+    k_mn_vertex_bwd<<<mve_cdiv(V, NT), NT, 0, s>>>(V, d_live, d_vn_sum, d_g_vn, d_scratch);
+    MVE_LAUNCH_CHECK();
+    k_mn_face_bwd<<<mve_cdiv(F, NT), NT, 0, s>>>(d_verts, d_faces, F, d_live, d_g_face_normals, d_scratch, d_g_verts);
+    MVE_LAUNCH_CHECK();
     return MVE_OK;
 }
 
@@ -148,61 +232,50 @@ size_t mve_mesh_reg_workspace_bytes(int V, int F) { return (V > 0 && F > 0) ? ws
 
 int mve_mesh_reg_forward(const float* d_verts, int V, const int32_t* d_faces, int F, const float* d_face_normals, void* d_ws, size_t ws_bytes,
                          float* d_losses, void* stream) {
-    if (int rc = check("mesh_reg_forward", d_verts, V, d_faces, F, d_face_normals, d_ws, ws_bytes)) return rc;
-    MVE_CHECK(d_losses, MVE_ERR_ARG, "mesh_reg_forward: null output");
-    hipStream_t s = (hipStream_t)stream;
-    const Ws w = carve(d_ws, V, F);
-    MVE_HIP(hipMemsetAsync(w.cnt, 0, sizeof(int) * (size_t)V, s));
-    MVE_HIP(hipMemsetAsync(w.fill, 0, sizeof(int) * (size_t)V, s));
-    const unsigned nbf = mve_cdiv(F, NT);
-    k_mr_count<<<nbf, NT, 0, s>>>(d_faces, F, w.cnt);
-    MVE_LAUNCH_CHECK();
-    if (int rc = exclusive_scan<int>(w.cnt, w.base, (size_t)V, w.tile, w.total, s)) { mve_set_error("mesh_reg_forward: scan launch failed"); return rc; }
-    k_mr_fill<<<nbf, NT, 0, s>>>(d_faces, F, w.base, w.fill, w.bucket);
-    MVE_LAUNCH_CHECK();
-    k_mr_vertex_fwd<<<w.nbv, NT, 0, s>>>(d_verts, V, d_face_normals, w);
-    MVE_LAUNCH_CHECK();
-    k_mr_reduce<<<1, NT, 0, s>>>(w, V, d_losses);
-    MVE_LAUNCH_CHECK();
-    return MVE_OK;
+    return reg_forward("mesh_reg_forward", d_verts, V, d_faces, F, nullptr, d_face_normals, d_ws, ws_bytes, d_losses, stream);
 }
 
 int mve_mesh_reg_backward(const float* d_verts, int V, const int32_t* d_faces, int F, const float* d_face_normals, void* d_ws, size_t ws_bytes,
                           const float* d_g_losses, float* d_g_verts, float* d_g_face_normals, void* stream) {
-    if (int rc = check("mesh_reg_backward", d_verts, V, d_faces, F, d_face_normals, d_ws, ws_bytes)) return rc;
-    MVE_CHECK(d_g_verts && d_g_face_normals, MVE_ERR_ARG, "mesh_reg_backward: null output");
-    hipStream_t s = (hipStream_t)stream;
-    const Ws w = carve(d_ws, V, F);
-    MVE_HIP(hipMemsetAsync(d_g_face_normals, 0, sizeof(float) * 3 * (size_t)F, s));
-    k_mr_vertex_bwd<<<w.nbv, NT, 0, s>>>(V, d_face_normals, w, d_g_losses, d_g_verts, d_g_face_normals);
-    MVE_LAUNCH_CHECK();
-    return MVE_OK;
+    return reg_backward("mesh_reg_backward", d_verts, V, d_faces, F, nullptr, d_face_normals, d_ws, ws_bytes, d_g_losses, d_g_verts, d_g_face_normals,
+                        stream);
 }
 
 int mve_mesh_normals_forward(const float* d_verts, int V, const int32_t* d_faces, int F, float* d_face_normals, float* d_vn_sum, float* d_vn,
                              void* stream) {
-    MVE_CHECK(d_verts && d_faces && d_face_normals && d_vn_sum && d_vn, MVE_ERR_ARG, "mesh_normals_forward: null pointer");
-    MVE_CHECK(V > 0 && F > 0, MVE_ERR_ARG, "mesh_normals_forward: bad mesh size V=%d F=%d", V, F);
-    hipStream_t s = (hipStream_t)stream;
-    MVE_HIP(hipMemsetAsync(d_vn_sum, 0, sizeof(float) * 3 * (size_t)V, s));
-    k_mn_face_fwd<<<mve_cdiv(F, NT), NT, 0, s>>>(d_verts, d_faces, F, d_face_normals, d_vn_sum);
-    MVE_LAUNCH_CHECK();
-    k_mn_vertex_fwd<<<mve_cdiv(V, NT), NT, 0, s>>>(V, d_vn_sum, d_vn);
-    MVE_LAUNCH_CHECK();
-    return MVE_OK;
+    return normals_forward("mesh_normals_forward", d_verts, V, d_faces, F, nullptr, d_face_normals, d_vn_sum, d_vn, stream);
 }
 
 int mve_mesh_normals_backward(const float* d_verts, int V, const int32_t* d_faces, int F, const float* d_vn_sum, const float* d_g_vn,
                               const float* d_g_face_normals, float* d_scratch, float* d_g_verts, void* stream) {
-    MVE_CHECK(d_verts && d_faces && d_vn_sum && d_scratch && d_g_verts, MVE_ERR_ARG, "mesh_normals_backward: null pointer");
-    MVE_CHECK(V > 0 && F > 0, MVE_ERR_ARG, "mesh_normals_backward: bad mesh size V=%d F=%d", V, F);
-    hipStream_t s = (hipStream_t)stream;
-    MVE_HIP(hipMemsetAsync(d_g_verts, 0, sizeof(float) * 3 * (size_t)V, s));
-    k_mn_vertex_bwd<<<mve_cdiv(V, NT), NT, 0, s>>>(V, d_vn_sum, d_g_vn, d_scratch);
-    MVE_LAUNCH_CHECK();
-    k_mn_face_bwd<<<mve_cdiv(F, NT), NT, 0, s>>>(d_verts, d_faces, F, d_g_face_normals, d_scratch, d_g_verts);
-    MVE_LAUNCH_CHECK();
-    return MVE_OK;
+    return normals_backward("mesh_normals_backward", d_verts, V, d_faces, F, nullptr, d_vn_sum, d_g_vn, d_g_face_normals, d_scratch, d_g_verts, stream);
+}
+
+// ---- capacity form: V = v_cap, F = f_cap, d_live = device int32 [2] (live vertices, live faces) ---------------------------------------------
+int mve_mesh_reg_forward_n(const float* d_verts, int v_cap, const int32_t* d_faces, int f_cap, const int32_t* d_live, const float* d_face_normals,
+                           void* d_ws, size_t ws_bytes, float* d_losses, void* stream) {
+    MVE_CHECK(d_live, MVE_ERR_ARG, "mesh_reg_forward_n: null live counts");
+    return reg_forward("mesh_reg_forward_n", d_verts, v_cap, d_faces, f_cap, d_live, d_face_normals, d_ws, ws_bytes, d_losses, stream);
+}
+
+int mve_mesh_reg_backward_n(const float* d_verts, int v_cap, const int32_t* d_faces, int f_cap, const int32_t* d_live, const float* d_face_normals,
+                            void* d_ws, size_t ws_bytes, const float* d_g_losses, float* d_g_verts, float* d_g_face_normals, void* stream) {
+    MVE_CHECK(d_live, MVE_ERR_ARG, "mesh_reg_backward_n: null live counts");
+    return reg_backward("mesh_reg_backward_n", d_verts, v_cap, d_faces, f_cap, d_live, d_face_normals, d_ws, ws_bytes, d_g_losses, d_g_verts,
+                        d_g_face_normals, stream);
+}
+
+int mve_mesh_normals_forward_n(const float* d_verts, int v_cap, const int32_t* d_faces, int f_cap, const int32_t* d_live, float* d_face_normals,
+                               float* d_vn_sum, float* d_vn, void* stream) {
+    MVE_CHECK(d_live, MVE_ERR_ARG, "mesh_normals_forward_n: null live counts");
+    return normals_forward("mesh_normals_forward_n", d_verts, v_cap, d_faces, f_cap, d_live, d_face_normals, d_vn_sum, d_vn, stream);
+}
+
+int mve_mesh_normals_backward_n(const float* d_verts, int v_cap, const int32_t* d_faces, int f_cap, const int32_t* d_live, const float* d_vn_sum,
+                                const float* d_g_vn, const float* d_g_face_normals, float* d_scratch, float* d_g_verts, void* stream) {
+    MVE_CHECK(d_live, MVE_ERR_ARG, "mesh_normals_backward_n: null live counts");
+    return normals_backward("mesh_normals_backward_n", d_verts, v_cap, d_faces, f_cap, d_live, d_vn_sum, d_g_vn, d_g_face_normals, d_scratch,
+                            d_g_verts, stream);
 }
 
 }  // extern "C"

@@ -15,6 +15,8 @@
 // atomics race.  The depth/id buffer (8 B/pixel) lives in L2 / Infinity Cache for the 512^2 x 6 view batches of the pipeline.
 #include "common.h"
 
+#include "mesh_capacity_core.h"
+
 namespace {
 
 constexpr int RB = 256;
@@ -450,10 +452,10 @@ __device__ __forceinline__ unsigned edge_hash(unsigned long long k, unsigned mas
 }
 
 // open-addressing table keyed by the undirected edge; every slot counts its users and remembers the first two
-__global__ __launch_bounds__(RB) void k_edge_insert(const int32_t* __restrict__ tri, int F, unsigned mask, unsigned long long* __restrict__ keys,
-                                                    int* __restrict__ cnt, int* __restrict__ ent) {
+__global__ __launch_bounds__(RB) void k_edge_insert(const int32_t* __restrict__ tri, int F, const int32_t* __restrict__ f_live, unsigned mask,
+                                                    unsigned long long* __restrict__ keys, int* __restrict__ cnt, int* __restrict__ ent) {
     const int i = blockIdx.x * RB + threadIdx.x;
-    if (i >= 3 * F) return;
+    if (i >= 3 * mcap_live(F, f_live)) return;              // capacity form: padded faces would all insert the key (0, 0)
     const int f = i / 3, e = i - 3 * f;
     const unsigned long long key = edge_key(tri[3 * f + e], tri[3 * f + (e + 1) % 3]);
     unsigned h = edge_hash(key, mask);
@@ -467,11 +469,12 @@ __global__ __launch_bounds__(RB) void k_edge_insert(const int32_t* __restrict__ 
         h = (h + 1) & mask;
     }
 }
-__global__ __launch_bounds__(RB) void k_edge_opposites(const int32_t* __restrict__ tri, int F, unsigned mask,
+__global__ __launch_bounds__(RB) void k_edge_opposites(const int32_t* __restrict__ tri, int F, const int32_t* __restrict__ f_live, unsigned mask,
                                                        const unsigned long long* __restrict__ keys, const int* __restrict__ cnt,
                                                        const int* __restrict__ ent, int32_t* __restrict__ opp) {
     const int i = blockIdx.x * RB + threadIdx.x;
     if (i >= 3 * F) return;
+    if (i >= 3 * mcap_live(F, f_live)) { opp[i] = MVE_MCAP_PAD_OPP; return; }
     const int f = i / 3, e = i - 3 * f;
     const unsigned long long key = edge_key(tri[3 * f + e], tri[3 * f + (e + 1) % 3]);
     unsigned h = edge_hash(key, mask);
@@ -616,7 +619,9 @@ size_t mve_edge_opposites_workspace_bytes(int F) {
     return T * (8 + 4 + 8) + 256;
 }
 
-int mve_edge_opposites(const int32_t* d_tri, int F, int32_t* d_opp, void* d_workspace, size_t workspace_bytes, void* stream) {
+// exact (d_f_live == nullptr) and capacity form (F = f_cap, *d_f_live = live faces) in one body
+static int edge_opposites_impl(const int32_t* d_tri, int F, const int32_t* d_f_live, int32_t* d_opp, void* d_workspace, size_t workspace_bytes,
+                               void* stream) {
     if (F == 0) return MVE_OK;
     MVE_CHECK(d_tri && d_opp && d_workspace, MVE_ERR_ARG, "edge_opposites: null pointer");
     MVE_CHECK(workspace_bytes >= mve_edge_opposites_workspace_bytes(F), MVE_ERR_NOMEM, "edge_opposites: workspace too small");
@@ -628,11 +633,21 @@ int mve_edge_opposites(const int32_t* d_tri, int F, int32_t* d_opp, void* d_work
     int* ent = cnt + T;
     MVE_HIP(hipMemsetAsync(keys, 0xff, T * 8, s));
     MVE_HIP(hipMemsetAsync(cnt, 0, T * 4, s));
-    k_edge_insert<<<mve_cdiv(3 * F, RB), RB, 0, s>>>(d_tri, F, (unsigned)(T - 1), keys, cnt, ent);
+    k_edge_insert<<<mve_cdiv(3 * F, RB), RB, 0, s>>>(d_tri, F, d_f_live, (unsigned)(T - 1), keys, cnt, ent);
     MVE_LAUNCH_CHECK();
-    k_edge_opposites<<<mve_cdiv(3 * F, RB), RB, 0, s>>>(d_tri, F, (unsigned)(T - 1), keys, cnt, ent, d_opp);
+    k_edge_opposites<<<mve_cdiv(3 * F, RB), RB, 0, s>>>(d_tri, F, d_f_live, (unsigned)(T - 1), keys, cnt, ent, d_opp);
     MVE_LAUNCH_CHECK();
     return MVE_OK;
+}
+
+int mve_edge_opposites(const int32_t* d_tri, int F, int32_t* d_opp, void* d_workspace, size_t workspace_bytes, void* stream) {
+    return edge_opposites_impl(d_tri, F, nullptr, d_opp, d_workspace, workspace_bytes, stream);
+}
+
+int mve_edge_opposites_n(const int32_t* d_tri, int f_cap, const int32_t* d_live, int32_t* d_opp, void* d_workspace, size_t workspace_bytes,
+                         void* stream) {
+    MVE_CHECK(f_cap > 0 && d_live, MVE_ERR_ARG, "edge_opposites_n: capacity must be positive and the live counts given");
+    return edge_opposites_impl(d_tri, f_cap, d_live + 1, d_opp, d_workspace, workspace_bytes, stream);
 }
 
 int mve_antialias(const float* d_color, int B, int H, int W, int C, const float* d_rast, const float* d_pos, int V, const int32_t* d_tri,

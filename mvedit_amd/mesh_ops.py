@@ -121,15 +121,28 @@ def _interpolate_raw(attr, rast, tri):
     return out
 
 
-def edge_opposites(tri):
-    """opp [F,3] int32: vertex opposite to edge e of every triangle in the adjacent triangle (-1: boundary / non-manifold)."""
+def _check_live(live, device):
+    """`live`: the device int32 [2] = (live vertices, live faces) a capacity extraction leaves (DMTet(..., capacity=...).live)."""
+    assert torch.is_tensor(live) and live.is_cuda and live.dtype == torch.int32 and live.numel() == 2 and live.is_contiguous(), \
+        'live: int32 [2] on the device'
+    assert live.device == device, 'live must sit on the mesh\'s device'
+    return live
+
+
+def edge_opposites(tri, live=None):
+    """opp [F,3] int32: vertex opposite to edge e of every triangle in the adjacent triangle (-1: boundary / non-manifold).
+    live (device int32 [2], capacity form): only the live faces enter the edge table, the padded rows are -1.  No host read."""
     tri = tri.to(torch.int32).contiguous()
     F = tri.shape[0]
     opp = torch.empty_like(tri)
     nbytes = _lib.raw('mve_edge_opposites_workspace_bytes')(F)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=tri.device)
     with torch.cuda.device(tri.device):
-        _lib.call('mve_edge_opposites', _lib.ptr(tri), F, _lib.ptr(opp), _lib.ptr(ws), nbytes, _lib.stream_ptr(tri.device))
+        if live is not None:
+            _lib.call('mve_edge_opposites_n', _lib.ptr(tri), F, _lib.ptr(_check_live(live, tri.device)), _lib.ptr(opp), _lib.ptr(ws), nbytes,
+                      _lib.stream_ptr(tri.device))
+        else:
+            _lib.call('mve_edge_opposites', _lib.ptr(tri), F, _lib.ptr(opp), _lib.ptr(ws), nbytes, _lib.stream_ptr(tri.device))
     return opp
 
 
@@ -359,8 +372,10 @@ class MeshRenderer:
         v_clip = torch.nn.functional.pad(v_cam, (0, 1), value=1.0) @ proj.transpose(-1, -2)
         return v_cam, v_clip, r_c2w
 
-    def render_geometry(self, v, f, vn, fn, poses, intrinsics, h, w, normal_bg=(0.5, 0.5, 1.0)):
-        """rasterise + depth + camera-space normals + alpha (the texture-free part of forward)."""
+    def render_geometry(self, v, f, vn, fn, poses, intrinsics, h, w, normal_bg=(0.5, 0.5, 1.0), host_read_free=False):
+        """rasterise + depth + camera-space normals + alpha (the texture-free part of forward).  host_read_free (the capacity form): the
+        background normal is laid in with a select instead of a masked assignment (which reads the mask's population on the host); the
+        values are the same."""
         if self.ssaa > 1:
             h, w, intrinsics = h * self.ssaa, w * self.ssaa, intrinsics * self.ssaa
         v_cam, v_clip, r_c2w = self.project(v.float(), poses.float(), intrinsics.float(), h, w)
@@ -370,22 +385,31 @@ class MeshRenderer:
         depth = depth.masked_fill(~fg, 0)
         normal = torch.nn.functional.normalize(interpolate(vn[None], rast, fn), dim=-1)
         rot_normal = (normal @ r_c2w[:, None]) / 2 + 0.5
-        rot_normal[~fg] = rot_normal.new_tensor(normal_bg)
+        if host_read_free:
+            bg = torch.cat([rot_normal.new_full((1,), float(c)) for c in normal_bg])
+            rot_normal = torch.where(fg[..., None], rot_normal, bg)
+        else:
+            rot_normal[~fg] = rot_normal.new_tensor(normal_bg)
         return dict(rast=rast, alpha=fg.float()[..., None], depth=depth, normal=rot_normal, v_clip=v_clip, world_normal=normal)
 
     def forward(self, meshes, poses, intrinsics, h, w, shading_fun=None, dilate_edges=0, normal_bg=(0.5, 0.5, 1.0), aa=True,
                 render_vc=False):
         """Same signature / result as the reference: poses [1,b,3|4,4], intrinsics [1,b,4] ->
-        dict(rgba [1,b,h,w,4], depth [1,b,h,w], normal [1,b,h,w,3])."""
+        dict(rgba [1,b,h,w,4], depth [1,b,h,w], normal [1,b,h,w,3]).
+
+        A mesh that carries `live` (the capacity form, Mesh(..., live=dm.live)) is rendered at its full capacity without a host read: the
+        padded faces are (0, 0, 0), which the rasteriser drops, and the edge table of the antialias pass takes the live faces only."""
         assert len(meshes) == 1 and poses.shape[0] == 1, 'one mesh per call (num_scenes = 1)'
         mesh = meshes[0]
+        live = getattr(mesh, 'live', None)
         ssaa = self.ssaa
         self.ssaa = 1                                               # render_geometry would scale again
         try:
             hh, ww, intr = h * ssaa, w * ssaa, intrinsics[0].float() * ssaa
             f = mesh.f.to(torch.int32).contiguous()
             fn = mesh.fn if getattr(mesh, 'fn', None) is not None else f
-            g = self.render_geometry(mesh.v.float(), f, mesh.vn.float(), fn, poses[0].float(), intr, hh, ww, normal_bg)
+            g = self.render_geometry(mesh.v.float(), f, mesh.vn.float(), fn, poses[0].float(), intr, hh, ww, normal_bg,
+                                     host_read_free=live is not None)
         finally:
             self.ssaa = ssaa
         rast, alpha, depth, rot_normal = g['rast'], g['alpha'], g['depth'], g['normal']
@@ -430,7 +454,8 @@ class MeshRenderer:
             x = rgba.permute(0, 3, 1, 2)
             rgba = edge_dilation(x, x[:, 3:], dilate_edges).permute(0, 2, 3, 1)
         if aa:
-            packed = antialias(torch.cat([rgba, depth[..., None], rot_normal], dim=-1), rast, g['v_clip'], f)
+            packed = antialias(torch.cat([rgba, depth[..., None], rot_normal], dim=-1), rast, g['v_clip'], f,
+                               opp=None if live is None else edge_opposites(f, live))
             rgba, depth, rot_normal = packed[..., :4], packed[..., 4], packed[..., 5:8]
         if ssaa > 1:
             rgba = box_downsample(rgba, ssaa)
@@ -628,12 +653,49 @@ class _AutoNormalFn(torch.autograd.Function):
         return g_v.to(ctx.dtype), None
 
 
+class _AutoNormalNFn(torch.autograd.Function):
+    """Capacity form of _AutoNormalFn: verts [v_cap,3], faces [f_cap,3], live = device int32 [2]; padded rows of vn / face_normals are
+    zeros and padded vertices receive zero gradient.  No host read."""
+
+    @staticmethod
+    def forward(ctx, verts, faces, live):
+        assert verts.is_cuda and faces.is_cuda and verts.dim() == 2 and verts.shape[1] == 3 and faces.dim() == 2 and faces.shape[1] == 3
+        v = verts.detach().to(torch.float32).contiguous()
+        f = faces.to(torch.int32).contiguous()
+        live = _check_live(live, v.device)
+        V, F = v.shape[0], f.shape[0]
+        fn = torch.empty(F, 3, dtype=torch.float32, device=v.device)
+        vs, vn = torch.empty_like(v), torch.empty_like(v)
+        with torch.cuda.device(v.device):
+            _lib.call('mve_mesh_normals_forward_n', _lib.ptr(v), V, _lib.ptr(f), F, _lib.ptr(live), _lib.ptr(fn), _lib.ptr(vs), _lib.ptr(vn),
+                      _lib.stream_ptr(v.device))
+        ctx.save_for_backward(v, f, vs, live)
+        ctx.dtype = verts.dtype
+        return vn.to(verts.dtype), fn.to(verts.dtype)
+
+    @staticmethod
+    def backward(ctx, g_vn, g_fn):
+        v, f, vs, live = ctx.saved_tensors
+        g_vn = None if g_vn is None else g_vn.detach().to(torch.float32).contiguous()
+        g_fn = None if g_fn is None else g_fn.detach().to(torch.float32).contiguous()
+        scratch, g_v = torch.empty_like(v), torch.empty_like(v)
+        with torch.cuda.device(v.device):
+            _lib.call('mve_mesh_normals_backward_n', _lib.ptr(v), v.shape[0], _lib.ptr(f), f.shape[0], _lib.ptr(live), _lib.ptr(vs), _lib.ptr(g_vn),
+                      _lib.ptr(g_fn), _lib.ptr(scratch), _lib.ptr(g_v), _lib.stream_ptr(v.device))
+        return g_v.to(ctx.dtype), None, None
+
+
 class Mesh:
     """Stand-in for lib.models.decoders.mesh_renderer.mesh_utils.Mesh: the attributes the render / bake / optimisation paths touch, and
-    `auto_normal` (mesh_utils.py:359-382) on native kernels."""
+    `auto_normal` (mesh_utils.py:359-382) on native kernels.
 
-    def __init__(self, v, f, vt=None, ft=None, vn=None, fn=None, albedo=None, vc=None, device=None):
+    live (device int32 [2], optional): the mesh is the capacity form of a DMTet extraction -- v [v_cap,3] and f [f_cap,3] with
+    (live vertices, live faces) in device memory (DMTet(..., capacity=...).live).  auto_normal and MeshRenderer.forward then take the
+    count-aware kernels and read nothing on the host."""
+
+    def __init__(self, v, f, vt=None, ft=None, vn=None, fn=None, albedo=None, vc=None, device=None, live=None):
         self.v, self.f, self.vt, self.ft, self.vn, self.fn, self.albedo, self.vc = v, f, vt, ft, vn, fn, albedo, vc
+        self.live = live
         self.face_normals = None
         self.textureless = albedo is None
 
@@ -642,7 +704,10 @@ class Mesh:
         torch.unique) is not on the optimisation path and not built."""
         if seamless:
             raise NotImplementedError('Mesh.auto_normal(seamless=True) is outside the native path')
-        self.vn, self.face_normals = _AutoNormalFn.apply(self.v, self.f)
+        if self.live is not None:
+            self.vn, self.face_normals = _AutoNormalNFn.apply(self.v, self.f, self.live)
+        else:
+            self.vn, self.face_normals = _AutoNormalFn.apply(self.v, self.f)
         self.fn = self.f.to(torch.int32)
 
 
@@ -667,19 +732,59 @@ class _DMTetFn(torch.autograd.Function):
         return None, g_pos, g_sdf, None
 
 
+class _DMTetNFn(torch.autograd.Function):
+    """Capacity form of _DMTetFn: verts [v_cap,3], faces [f_cap,3]; the counts stay on the device (dm.counts / dm.live / dm.overflow)."""
+
+    @staticmethod
+    def forward(ctx, dm, pos, sdf, tets32, v_cap, f_cap):
+        verts, faces, edges, live = dm._extract_n(pos, sdf, tets32, v_cap, f_cap)
+        ctx.save_for_backward(pos, sdf, edges, live)
+        ctx.mark_non_differentiable(faces)
+        return verts, faces
+
+    @staticmethod
+    def backward(ctx, g_verts, _g_faces):
+        pos, sdf, edges, live = ctx.saved_tensors
+        g_pos, g_sdf = torch.zeros_like(pos), torch.zeros_like(sdf)
+        g = g_verts.float().contiguous()
+        with torch.cuda.device(pos.device):
+            _lib.call('mve_dmtet_backward_n', _lib.ptr(pos), _lib.ptr(sdf), _lib.ptr(edges), edges.shape[0], _lib.ptr(live), _lib.ptr(g),
+                      _lib.ptr(g_pos), _lib.ptr(g_sdf), _lib.stream_ptr(pos.device))
+        return None, g_pos, g_sdf, None, None, None
+
+
 class DMTet:
     """Mirror of the reference's DMTet (base_mesh_renderer.py:104-188): `DMTet(device)(pos_nx3, sdf_n, tet_fx4) -> verts, faces`.
-    When pos or sdf require grad the vertices carry autograd history (native backward), as in the reference's mesh optimisation."""
+    When pos or sdf require grad the vertices carry autograd history (native backward), as in the reference's mesh optimisation.
+
+    capacity=(v_cap, f_cap), opt-in: the host-read-free form.  verts [v_cap,3] and faces [f_cap,3] are sized by the caller, and every
+    call leaves three fresh device tensors on the object: `counts` (int32 [2], the true totals, also when they do not fit), `overflow`
+    (int32 [1]) and `live` (int32 [2]: the totals, or (0, 0) on overflow -- the empty mesh).  Rows beyond the live counts are zeros (a
+    (0, 0, 0) face is dropped by the rasteriser).  Hand `live` to Mesh(..., live=) / mesh_regularizers(..., live=), fold `overflow`
+    into the optimiser step with adam_step_n(..., skip_if=overflow), and grow the capacity from `counts` where the loop synchronises anyway."""
 
     def __init__(self, device='cuda'):
         self.device = torch.device(device)
         self._tets_key, self._tets32 = None, None
+        self.counts = self.live = self.overflow = None
 
-    def __call__(self, pos_nx3, sdf_n, tet_fx4):
+    def __call__(self, pos_nx3, sdf_n, tet_fx4, capacity=None):
+        if capacity is not None:
+            v_cap, f_cap = (int(c) for c in capacity)
+            if v_cap <= 0 or f_cap <= 0:
+                raise ValueError(f'capacity must be two positive row counts (v_cap, f_cap), got {tuple(capacity)}')
         key = (tet_fx4.data_ptr(), tuple(tet_fx4.shape), tet_fx4.dtype)
         if key != self._tets_key:                                   # the tet grid is constant across iterations: convert once
             self._tets32 = tet_fx4.to(self.device, torch.int32).contiguous()
             self._tets_key = key
+        if capacity is not None:
+            pos = pos_nx3.to(self.device, torch.float32).contiguous()
+            sdf = sdf_n.to(self.device, torch.float32).contiguous()
+            if torch.is_grad_enabled() and (pos.requires_grad or sdf.requires_grad):
+                verts, faces = _DMTetNFn.apply(self, pos, sdf, self._tets32, v_cap, f_cap)
+            else:
+                verts, faces, _, _ = self._extract_n(pos, sdf, self._tets32, v_cap, f_cap, want_edges=False)
+            return verts, faces.long()
         if torch.is_grad_enabled() and (pos_nx3.requires_grad or sdf_n.requires_grad):
             pos = pos_nx3.to(self.device, torch.float32).contiguous()
             sdf = sdf_n.to(self.device, torch.float32).contiguous()
@@ -705,6 +810,22 @@ class DMTet:
             _lib.call('mve_dmtet_write', _lib.ptr(pos), _lib.ptr(sdf), _lib.ptr(tets), nv, nt, _lib.ptr(verts), _lib.ptr(faces),
                       _lib.ptr(edges), _lib.ptr(ws), nbytes, sp)
         return verts, faces, edges
+
+    def _extract_n(self, pos, sdf, tets, v_cap, f_cap, want_edges=True):
+        pos, sdf = pos.detach(), sdf.detach()
+        nv, nt = pos.shape[0], tets.shape[0]
+        nbytes = _lib.raw('mve_dmtet_workspace_bytes')(nv, nt)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        state = torch.empty(5, dtype=torch.int32, device=self.device)          # counts [2] | live [2] | overflow [1], written by the call
+        self.counts, self.live, self.overflow = state[0:2], state[2:4], state[4:5]
+        verts = torch.empty(v_cap, 3, dtype=torch.float32, device=self.device)
+        faces = torch.empty(f_cap, 3, dtype=torch.int32, device=self.device)
+        edges = torch.empty(v_cap, 2, dtype=torch.int32, device=self.device) if want_edges else None
+        with torch.cuda.device(self.device):
+            _lib.call('mve_dmtet_extract_n', _lib.ptr(pos), _lib.ptr(sdf), _lib.ptr(tets), nv, nt, v_cap, f_cap, _lib.ptr(verts), _lib.ptr(faces),
+                      _lib.ptr(edges), _lib.ptr(self.counts), _lib.ptr(self.live), _lib.ptr(self.overflow), _lib.ptr(ws), nbytes,
+                      _lib.stream_ptr(self.device))
+        return verts, faces, edges, self.live
 
 
 class _MeshRegFn(torch.autograd.Function):
@@ -741,11 +862,82 @@ class _MeshRegFn(torch.autograd.Function):
         return g_v.to(ctx.dtypes[0]), g_fn.to(ctx.dtypes[1]), None
 
 
-def mesh_regularizers(verts, faces, face_normals):
+class _MeshRegNFn(torch.autograd.Function):
+    """Capacity form of _MeshRegFn: verts [v_cap,3], faces / face_normals [f_cap,3], live = device int32 [2].  No host read."""
+
+    @staticmethod
+    def forward(ctx, verts, face_normals, faces, live):
+        assert verts.is_cuda and faces.is_cuda and verts.dim() == 2 and verts.shape[1] == 3 and faces.dim() == 2 and faces.shape[1] == 3
+        dev = verts.device
+        v = verts.detach().to(torch.float32).contiguous()
+        fn = face_normals.detach().to(device=dev, dtype=torch.float32).contiguous()
+        f = faces.to(torch.int32).contiguous()
+        live = _check_live(live, dev)
+        V, F = v.shape[0], f.shape[0]
+        assert fn.shape == (F, 3)
+        ws = torch.empty(_lib.raw('mve_mesh_reg_workspace_bytes')(V, F), dtype=torch.uint8, device=dev)     # carried to backward
+        losses = torch.empty(2, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.call('mve_mesh_reg_forward_n', _lib.ptr(v), V, _lib.ptr(f), F, _lib.ptr(live), _lib.ptr(fn), _lib.ptr(ws), ws.numel(),
+                      _lib.ptr(losses), _lib.stream_ptr(dev))
+        ctx.save_for_backward(v, f, fn, ws, live)
+        ctx.dtypes = (verts.dtype, face_normals.dtype)
+        return losses[0].clone(), losses[1].clone()
+
+    @staticmethod
+    def backward(ctx, g_lap, g_nc):
+        v, f, fn, ws, live = ctx.saved_tensors
+        dev = v.device
+        zero = torch.zeros((), dtype=torch.float32, device=dev)
+        gl = torch.stack([zero if g_lap is None else g_lap.detach().float().reshape(()), zero if g_nc is None else g_nc.detach().float().reshape(())])
+        g_v, g_fn = torch.empty_like(v), torch.empty_like(fn)
+        with torch.cuda.device(dev):
+            _lib.call('mve_mesh_reg_backward_n', _lib.ptr(v), v.shape[0], _lib.ptr(f), f.shape[0], _lib.ptr(live), _lib.ptr(fn), _lib.ptr(ws),
+                      ws.numel(), _lib.ptr(gl), _lib.ptr(g_v), _lib.ptr(g_fn), _lib.stream_ptr(dev))
+        return g_v.to(ctx.dtypes[0]), g_fn.to(ctx.dtypes[1]), None, None
+
+
+def mesh_regularizers(verts, faces, face_normals, live=None):
     """-> (laplacian_smooth_loss(verts, faces), normal_consistency(face_normals, faces)) of
     lib/models/decoders/mesh_renderer/base_mesh_renderer.py:55-101 in one native pass (the pair the mesh-optimisation loop adds at
-    mvedit_3d_pipeline.py:775-776), differentiable w.r.t. verts and face_normals."""
+    mvedit_3d_pipeline.py:775-776), differentiable w.r.t. verts and face_normals.
+
+    live (device int32 [2], the capacity form): only the live rows count; the two losses equal the exact call on the live rows bit for
+    bit, padded rows receive zero gradient, an empty mesh gives zeros.  No host read."""
+    if live is not None:
+        return _MeshRegNFn.apply(verts, face_normals, faces, live)
     return _MeshRegFn.apply(verts, face_normals, faces)
+
+
+def adam_state_n(params):
+    """A zeroed device-side optimiser state for `adam_step_n`: both moments of every tensor and the step counter (int32 [1])."""
+    return dict(moments=[(torch.zeros_like(p), torch.zeros_like(p)) for p in params],
+                step=torch.zeros(1, dtype=torch.int32, device=params[0].device))
+
+
+def adam_step_n(params, grads, state, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, skip_if=None):
+    """One torch.optim.Adam step, in place, on a list of float32 tensors of any shape (the mesh loop's tet_sdf and deform) with the
+    optimiser state on the device (`adam_state_n`; `state` may start as an empty dict).  skip_if (device int32 [1], e.g. DMTet.overflow):
+    when non-zero the whole step -- parameters, both moments, step counter -- is left undone.  lr: one value or one per tensor.
+    No host read."""
+    assert len(params) == len(grads) and len(params) > 0
+    dev = params[0].device
+    if skip_if is None:
+        skip_if = torch.zeros(1, dtype=torch.int32, device=dev)
+    assert skip_if.is_cuda and skip_if.dtype == torch.int32 and skip_if.numel() == 1, 'skip_if: one int32 on the device'
+    if 'step' not in state:
+        state.update(adam_state_n(params))
+    lrs = list(lr) if isinstance(lr, (list, tuple)) else [lr] * len(params)
+    assert len(lrs) == len(params)
+    with torch.cuda.device(dev):
+        for p, g, (m1, m2), lr_k in zip(params, grads, state['moments'], lrs):
+            assert p.is_cuda and p.dtype == torch.float32 and p.is_contiguous(), 'adam_step_n: contiguous float32 tensors on the device'
+            g = g.detach().to(torch.float32).contiguous()
+            assert g.shape == p.shape
+            _lib.call('mve_adam_step_n', _lib.ptr(p), _lib.ptr(g), _lib.ptr(m1), _lib.ptr(m2), p.numel(), float(lr_k), float(betas[0]),
+                      float(betas[1]), float(eps), _lib.ptr(state['step']), _lib.ptr(skip_if), _lib.stream_ptr(dev))
+        _lib.call('mve_adam_advance_n', _lib.ptr(state['step']), _lib.ptr(skip_if), _lib.stream_ptr(dev))
+    return state
 
 
 def laplacian_smooth_loss(verts, faces):
