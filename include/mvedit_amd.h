@@ -1424,8 +1424,12 @@ MVE_API int mve_antialias_backward(const float* d_grad_out, int B, int H, int W,
  *   point's two coordinates for that plane (plane_cfg; flip_z negates z);  base_x = base_net(features) [+ ingp_base_net(hash-grid encoding
  *   of (xyz + bound) / (2 bound), tiny-cuda-nn HashGrid with Smoothstep interpolation)];  sigma = sigma_activation(density_net(act(base_x)));
  *   rgb = sigmoid(color_net(cat[act(base_x), SH_4(dir)])) * (1 + 2 s) - s.
- * Supported topology (the classes' defaults): base_net = one Linear(3C -> hidden), density_net = Linear(hidden -> 1), color_net =
- * Linear(hidden + 16 -> hidden2), act, Linear(hidden2 -> 3); hidden, hidden2 in {64, 128}; dir_layers = None; ingp_base_layers = 1.
+ * Two topologies, selected by `topology`; both have base_net = one Linear(3C -> hidden), density_net = Linear(hidden -> 1), ingp_base_layers = 1:
+ *   MVE_TRIPLANE_DEFAULT (0, the classes' constructor defaults; a descriptor filled as before this field existed):
+ *       color_net = Linear(hidden + 16 -> hidden2), act, Linear(hidden2 -> 3) over cat[act(base_x), SH_4(dir)]; hidden, hidden2 in {64, 128}.
+ *   MVE_TRIPLANE_DIRNET (1, what every config file of the reference asks for: dir_layers = [16, hidden], color_layers = [hidden, 3]):
+ *       rgb = sigmoid(color_net(act(base_x + dir_net(SH_4(dir))))) * (1 + 2 s) - s with dir_net = Linear(16 -> hidden) in d_dir_wT / d_dir_b
+ *       and color_net = ONE Linear(hidden -> 3) in d_col2_w / d_col2_b; hidden in {64, 128}; hidden2 and d_col1_* are ignored.
  * Weight matrices are passed TRANSPOSED ([in][out], fp32) so that a wave reads an input's fan-out as one contiguous scalar load.
  * code is channels-last [3][h][w][C].  activation: 0 relu, 1 silu, 2 softplus; sigma_activation: the same, 3 = trunc_exp (exp). */
 typedef struct MveTriplaneDesc {
@@ -1448,7 +1452,11 @@ typedef struct MveTriplaneDesc {
     int32_t activation, sigma_activation;
     float sigmoid_saturation;
     float *d_sigmas, *d_rgbs;                        /* [N], [N,3] (d_rgbs unused when d_dirs is NULL) */
+    int32_t topology;                                /* MVE_TRIPLANE_DEFAULT / MVE_TRIPLANE_DIRNET */
+    const float *d_dir_wT, *d_dir_b;                 /* dir-net topology: [16][hidden], [hidden]; must be NULL for the default topology */
 } MveTriplaneDesc;
+#define MVE_TRIPLANE_DEFAULT 0
+#define MVE_TRIPLANE_DIRNET 1
 MVE_API int mve_triplane_decode(const MveTriplaneDesc* desc, void* stream);
 /* Backward of mve_triplane_decode: gradients of sum(d_grad_sigmas * sigma) + sum(d_grad_rgbs * rgb) (d_grad_rgbs NULL: density only) -- what
  * autograd supplies when nerf_optim optimises a TriPlaneiNGPDecoder scene (lib/pipelines/mvedit_3d_pipeline.py:507-633 through
@@ -1462,9 +1470,13 @@ typedef struct MveTriplaneGrads {
     float *d_ingp_w, *d_ingp_b;                      /* [hidden][2 n_levels], [hidden] (NULL without a hash branch) */
     float *d_dens_w, *d_dens_b;                      /* [1][hidden], [1] */
     float *d_col1_w, *d_col1_b;                      /* [hidden2][hidden + 16], [hidden2] */
-    float *d_col2_w, *d_col2_b;                      /* [3][hidden2], [3] */
+    float *d_col2_w, *d_col2_b;                      /* [3][hidden2], [3]; dir-net topology: color_net's one Linear, [3][hidden], [3] */
+    float *d_dir_w, *d_dir_b;                        /* dir-net topology only: [hidden][16], [hidden] (d_col1_* are not read then) */
 } MveTriplaneGrads;
+/* With d_grad_rgbs NULL the colour-net (and dir_net) gradients are left untouched.  The workspace size depends on the topology: the dir-net
+ * one has its own query (no hidden2). */
 MVE_API size_t mve_triplane_backward_workspace_bytes(int N, int C, int hidden, int hidden2, int n_levels);
+MVE_API size_t mve_triplane_dirnet_backward_workspace_bytes(int N, int C, int hidden, int n_levels);
 MVE_API int mve_triplane_backward(const MveTriplaneDesc* desc, const float* d_grad_sigmas, const float* d_grad_rgbs, const MveTriplaneGrads* grads,
                                   void* d_workspace, size_t workspace_bytes, void* stream);
 

@@ -4,6 +4,8 @@
 // produce them -- the 96-wide feature vector never exists; weights are wave-uniform and transposed ([in][out]), so one input's fan-out is
 // one contiguous scalar load; the activated hidden vector goes through LDS ([k][lane]: conflict-free) so that the second layer can loop over
 // its inputs at run time with all its outputs in registers.  The hash-grid encoding is the one of nerf.hip (hashgrid.h).
+// Two topologies (MveTriplaneDesc.topology): the classes' defaults (k_triplane_decode / k_triplane_backward) and the dir-net one of the
+// reference's config files (k_triplane_dirnet_decode / k_triplane_dirnet_backward), which keeps the hidden vector in registers throughout.
 #include "raymarch_core.h"
 
 #include "hashgrid.h"
@@ -21,6 +23,7 @@ struct TriParams {
     int axes[6];
     int flip_z;
     const float *base_wT, *base_b, *ingp_wT, *ingp_b, *dens_w, *dens_b, *col1_wT, *col1_b, *col2_w, *col2_b;
+    const float *dir_wT, *dir_b;          // dir-net topology: [16][H], [H] (col2_* is then its one-Linear colour net, [3][H])
     int activation, sigma_activation;
     float sat;
     float *sigmas, *rgbs;
@@ -34,37 +37,41 @@ __device__ __forceinline__ float act_fn(int a, float x) {
     return __expf(x);                                              // trunc_exp forward
 }
 
-template <int H, int H2, int NL>
-__global__ __launch_bounds__(WAVE) void k_triplane_decode(const TriParams p, const ShK16 kk) {
-    __shared__ float hid[(H + 16) * WAVE];            // activated hidden vector + SH encoding, [k][lane]
-    const int lane = threadIdx.x;
-    const int i = blockIdx.x * WAVE + lane;
-    const bool live = i < p.N;
-    const int ii = live ? i : p.N - 1;
-    const float x[3] = {p.xyz[3 * ii], p.xyz[3 * ii + 1], p.flip_z ? -p.xyz[3 * ii + 2] : p.xyz[3 * ii + 2]};
-    float acc[H];
+// One plane's bilinear taps of a point: F.grid_sample(align_corners=False, padding_mode='border') -- unnormalise, clip to [0, size - 1]
+struct TriTap { int x0, x1, y0, y1; float w[4]; };
+__device__ __forceinline__ TriTap tri_tap(const TriParams& p, float u, float v) {
+    float fx = ((u + 1.0f) * (float)p.w - 1.0f) * 0.5f, fy = ((v + 1.0f) * (float)p.h - 1.0f) * 0.5f;
+    fx = fminf(fmaxf(fx, 0.f), (float)(p.w - 1));
+    fy = fminf(fmaxf(fy, 0.f), (float)(p.h - 1));
+    const float x0f = floorf(fx), y0f = floorf(fy);
+    TriTap t;
+    t.x0 = (int)x0f; t.y0 = (int)y0f;
+    t.x1 = t.x0 + 1 < p.w ? t.x0 + 1 : p.w - 1; t.y1 = t.y0 + 1 < p.h ? t.y0 + 1 : p.h - 1;     // weight 0 where clipped
+    const float tx = fx - x0f, ty = fy - y0f;
+    t.w[0] = (1.f - tx) * (1.f - ty); t.w[1] = tx * (1.f - ty); t.w[2] = (1.f - tx) * ty; t.w[3] = tx * ty;
+    return t;
+}
+
+// base_x, shared by the four kernels: base_b + base_net(plane features) [+ ingp_base_net(hash encoding) + ingp_b], accumulated feature by
+// feature.  taps / ws_feat / ws_enc (the backward kernels: this point's taps, and its rows of the feature and encoding workspaces, NULL for
+// a lane past N) are optional.
+template <int H, int NL>
+__device__ __forceinline__ void tri_base_x(const TriParams& p, const float (&x)[3], float (&acc)[H], TriTap* taps = nullptr,
+                                           float* ws_feat = nullptr, float* ws_enc = nullptr) {
 #pragma unroll
     for (int j = 0; j < H; ++j) acc[j] = p.base_b[j];
-    // ---- plane features, accumulated into the first layer as they come -----------------------------------------------------
     for (int pl = 0; pl < 3; ++pl) {
-        const float u = x[p.axes[2 * pl]], v = x[p.axes[2 * pl + 1]];
-        // F.grid_sample(align_corners=False, padding_mode='border'): unnormalise, clip to [0, size - 1], bilinear
-        float fx = ((u + 1.0f) * (float)p.w - 1.0f) * 0.5f, fy = ((v + 1.0f) * (float)p.h - 1.0f) * 0.5f;
-        fx = fminf(fmaxf(fx, 0.f), (float)(p.w - 1));
-        fy = fminf(fmaxf(fy, 0.f), (float)(p.h - 1));
-        const float x0f = floorf(fx), y0f = floorf(fy);
-        const int x0 = (int)x0f, y0 = (int)y0f;
-        const int x1 = x0 + 1 < p.w ? x0 + 1 : p.w - 1, y1 = y0 + 1 < p.h ? y0 + 1 : p.h - 1;     // weight 0 where clipped
-        const float tx = fx - x0f, ty = fy - y0f;
-        const float w00 = (1.f - tx) * (1.f - ty), w10 = tx * (1.f - ty), w01 = (1.f - tx) * ty, w11 = tx * ty;
+        const TriTap t = tri_tap(p, x[p.axes[2 * pl]], x[p.axes[2 * pl + 1]]);
+        if (taps) taps[pl] = t;
         const float* pc = p.code + (size_t)pl * p.h * p.w * p.C;
-        const float* c00 = pc + ((size_t)y0 * p.w + x0) * p.C;
-        const float* c10 = pc + ((size_t)y0 * p.w + x1) * p.C;
-        const float* c01 = pc + ((size_t)y1 * p.w + x0) * p.C;
-        const float* c11 = pc + ((size_t)y1 * p.w + x1) * p.C;
+        const float* c00 = pc + ((size_t)t.y0 * p.w + t.x0) * p.C;
+        const float* c10 = pc + ((size_t)t.y0 * p.w + t.x1) * p.C;
+        const float* c01 = pc + ((size_t)t.y1 * p.w + t.x0) * p.C;
+        const float* c11 = pc + ((size_t)t.y1 * p.w + t.x1) * p.C;
         for (int c = 0; c < p.C; ++c) {
             // torch's bilinear kernel sums nw, ne, sw, se in this order
-            const float f = c00[c] * w00 + c10[c] * w10 + c01[c] * w01 + c11[c] * w11;
+            const float f = c00[c] * t.w[0] + c10[c] * t.w[1] + c01[c] * t.w[2] + c11[c] * t.w[3];
+            if (ws_feat) ws_feat[c * 3 + pl] = f;
             const float* wr = p.base_wT + (size_t)(c * 3 + pl) * H;
 #pragma unroll
             for (int j = 0; j < H; ++j) acc[j] = fmaf(wr[j], f, acc[j]);
@@ -75,6 +82,7 @@ __global__ __launch_bounds__(WAVE) void k_triplane_decode(const TriParams p, con
         hash_encode<NL>(p.hg, x[0], x[1], p.flip_z ? -x[2] : x[2], enc);          // the hash grid sees the un-flipped point
 #pragma unroll
         for (int e = 0; e < 2 * NL; ++e) {
+            if (ws_enc) ws_enc[e] = enc[e];
             const float* wr = p.ingp_wT + (size_t)e * H;
 #pragma unroll
             for (int j = 0; j < H; ++j) acc[j] = fmaf(wr[j], enc[e], acc[j]);
@@ -82,6 +90,43 @@ __global__ __launch_bounds__(WAVE) void k_triplane_decode(const TriParams p, con
 #pragma unroll
         for (int j = 0; j < H; ++j) acc[j] += p.ingp_b[j];
     }
+}
+
+// acc (base_x) += dir_b + dir_net weights . SH_4(direction of point ii); the encoding goes to ws_sh (16 floats) when given.  The 16 SH values
+// go through shs (LDS [16][WAVE], each lane reads back its own column: no barrier) so that the loop over them stays a run-time loop like the
+// default topology's second layer: fully unrolled (16 x H FMAs on scalar weight loads) the H = 64 kernels spilled ~690 VGPRs to scratch.
+template <int H>
+__device__ __forceinline__ void tri_add_dir_net(const TriParams& p, const ShK16& kk, int ii, int lane, float* shs, float (&acc)[H], float* ws_sh) {
+    {
+        float sh[16];
+        she_eval(kk.k, p.dirs[3 * ii], p.dirs[3 * ii + 1], p.dirs[3 * ii + 2], 4, sh, nullptr);
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            shs[k * WAVE + lane] = sh[k];
+            if (ws_sh) ws_sh[k] = sh[k];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < H; ++j) acc[j] += p.dir_b[j];
+#pragma unroll 1
+    for (int k = 0; k < 16; ++k) {
+        const float a = shs[k * WAVE + lane];
+        const float* wr = p.dir_wT + (size_t)k * H;
+#pragma unroll
+        for (int j = 0; j < H; ++j) acc[j] = fmaf(wr[j], a, acc[j]);
+    }
+}
+
+template <int H, int H2, int NL>
+__global__ __launch_bounds__(WAVE) void k_triplane_decode(const TriParams p, const ShK16 kk) {
+    __shared__ float hid[(H + 16) * WAVE];            // activated hidden vector + SH encoding, [k][lane]
+    const int lane = threadIdx.x;
+    const int i = blockIdx.x * WAVE + lane;
+    const bool live = i < p.N;
+    const int ii = live ? i : p.N - 1;
+    const float x[3] = {p.xyz[3 * ii], p.xyz[3 * ii + 1], p.flip_z ? -p.xyz[3 * ii + 2] : p.xyz[3 * ii + 2]};
+    float acc[H];
+    tri_base_x<H, NL>(p, x, acc);             // plane features (and hash-grid levels), accumulated into the first layer as they come
     // ---- density head; activated hidden vector to LDS ------------------------------------------------------------------------
     float sg = p.dens_b[0];
 #pragma unroll
@@ -121,6 +166,40 @@ __global__ __launch_bounds__(WAVE) void k_triplane_decode(const TriParams p, con
     }
 }
 
+// The dir-net topology (dir_layers = [16, H], color_layers = [H, 3]: every config file of the reference): the first layer as above; the density
+// head reads act(base_x); the 16 x H dir_net product is added to the PRE-activation accumulator in registers, and the one-Linear colour net
+// reads act of that.  There is no second hidden layer to loop over at run time, so the hidden vector is not staged in LDS (only the 16 SH
+// values are, see tri_add_dir_net).  The sigma path does not depend
+// on p.dirs: the density-only call gives the full call's sigmas bit for bit.
+template <int H, int NL>
+__global__ __launch_bounds__(WAVE) void k_triplane_dirnet_decode(const TriParams p, const ShK16 kk) {
+    __shared__ float shs[16 * WAVE];                  // the SH encoding only, [k][lane] (tri_add_dir_net)
+    const int lane = threadIdx.x;
+    const int i = blockIdx.x * WAVE + lane;
+    const bool live = i < p.N;
+    const int ii = live ? i : p.N - 1;
+    const float x[3] = {p.xyz[3 * ii], p.xyz[3 * ii + 1], p.flip_z ? -p.xyz[3 * ii + 2] : p.xyz[3 * ii + 2]};
+    float acc[H];
+    tri_base_x<H, NL>(p, x, acc);
+    float sg = p.dens_b[0];
+#pragma unroll
+    for (int j = 0; j < H; ++j) sg = fmaf(p.dens_w[j], act_fn(p.activation, acc[j]), sg);
+    if (live) p.sigmas[i] = act_fn(p.sigma_activation, sg);
+    if (p.dirs == nullptr) return;
+    tri_add_dir_net<H>(p, kk, ii, lane, shs, acc, nullptr);
+    float o[3] = {p.col2_b[0], p.col2_b[1], p.col2_b[2]};
+#pragma unroll
+    for (int j = 0; j < H; ++j) {
+        const float a = act_fn(p.activation, acc[j]);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[c] = fmaf(p.col2_w[c * H + j], a, o[c]);
+    }
+    if (live) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) p.rgbs[3 * i + c] = (1.0f / (1.0f + __expf(-o[c]))) * (1.0f + 2.0f * p.sat) - p.sat;
+    }
+}
+
 // d act(x) / dx for the hidden activations and the density head (trunc_exp: lib/ops/activation.py:17-20, g * clamp(exp(x), 1e-6, 1e6))
 __device__ __forceinline__ float act_grad(int a, float x) {
     if (a == 0) return x > 0.f ? 1.f : 0.f;
@@ -140,6 +219,42 @@ struct TriBwd {
     float *ws_feat, *ws_enc, *ws_dbase, *ws_hid, *ws_da2, *ws_act2, *ws_do;      // [N][3C], [N][2NL], [N][H], [N][H+16], [N][H2], [N][H2], [N][4]
 };
 
+// The scatter both backward kernels end with, acc holding d base_x of a live point: d feature (c, plane) = base_wT[c * 3 + plane][:] . d base_x
+// into the code planes with the bilinear weights, d encoding = ingp_wT . d base_x into the hash table (float atomics)
+template <int H, int NL>
+__device__ __forceinline__ void tri_scatter(const TriParams& p, const TriBwd& b, const float (&x)[3], const TriTap (&taps)[3], const float (&acc)[H]) {
+    if (b.g_code) {
+        for (int pl = 0; pl < 3; ++pl) {
+            const TriTap& t = taps[pl];
+            float* gp = b.g_code + (size_t)pl * p.h * p.w * p.C;
+            for (int c = 0; c < p.C; ++c) {
+                const float* wr = p.base_wT + (size_t)(c * 3 + pl) * H;
+                float g = 0.f;
+#pragma unroll
+                for (int j = 0; j < H; ++j) g = fmaf(wr[j], acc[j], g);
+                atomicAdd(gp + ((size_t)t.y0 * p.w + t.x0) * p.C + c, g * t.w[0]);
+                atomicAdd(gp + ((size_t)t.y0 * p.w + t.x1) * p.C + c, g * t.w[1]);
+                atomicAdd(gp + ((size_t)t.y1 * p.w + t.x0) * p.C + c, g * t.w[2]);
+                atomicAdd(gp + ((size_t)t.y1 * p.w + t.x1) * p.C + c, g * t.w[3]);
+            }
+        }
+    }
+    if constexpr (NL > 0) {
+        if (b.g_table) {
+            float denc[2 * NL];
+#pragma unroll
+            for (int e = 0; e < 2 * NL; ++e) {
+                const float* wr = p.ingp_wT + (size_t)e * H;
+                float g = 0.f;
+#pragma unroll
+                for (int j = 0; j < H; ++j) g = fmaf(wr[j], acc[j], g);
+                denc[e] = g;
+            }
+            hash_scatter<NL>(p.hg, x[0], x[1], p.flip_z ? -x[2] : x[2], denc, b.g_table);
+        }
+    }
+}
+
 template <int H, int H2, int NL>
 __global__ __launch_bounds__(WAVE) void k_triplane_backward(const TriParams p, const TriBwd b, const ShK16 kk) {
     __shared__ float hid[(H + 16) * WAVE];
@@ -151,48 +266,8 @@ __global__ __launch_bounds__(WAVE) void k_triplane_backward(const TriParams p, c
     const float x[3] = {p.xyz[3 * ii], p.xyz[3 * ii + 1], p.flip_z ? -p.xyz[3 * ii + 2] : p.xyz[3 * ii + 2]};
     const int F3 = 3 * p.C;
     float acc[H];
-#pragma unroll
-    for (int j = 0; j < H; ++j) acc[j] = p.base_b[j];
-    // plane taps of this point: kept for the scatter at the end
-    int tx0[3], tx1[3], ty0[3], ty1[3];
-    float tw[3][4];
-    for (int pl = 0; pl < 3; ++pl) {
-        const float u = x[p.axes[2 * pl]], v = x[p.axes[2 * pl + 1]];
-        float fx = ((u + 1.0f) * (float)p.w - 1.0f) * 0.5f, fy = ((v + 1.0f) * (float)p.h - 1.0f) * 0.5f;
-        fx = fminf(fmaxf(fx, 0.f), (float)(p.w - 1));
-        fy = fminf(fmaxf(fy, 0.f), (float)(p.h - 1));
-        const float x0f = floorf(fx), y0f = floorf(fy);
-        const int x0 = (int)x0f, y0 = (int)y0f;
-        const int x1 = x0 + 1 < p.w ? x0 + 1 : p.w - 1, y1 = y0 + 1 < p.h ? y0 + 1 : p.h - 1;
-        const float tx = fx - x0f, ty = fy - y0f;
-        tx0[pl] = x0; tx1[pl] = x1; ty0[pl] = y0; ty1[pl] = y1;
-        tw[pl][0] = (1.f - tx) * (1.f - ty); tw[pl][1] = tx * (1.f - ty); tw[pl][2] = (1.f - tx) * ty; tw[pl][3] = tx * ty;
-        const float* pc = p.code + (size_t)pl * p.h * p.w * p.C;
-        const float* c00 = pc + ((size_t)y0 * p.w + x0) * p.C;
-        const float* c10 = pc + ((size_t)y0 * p.w + x1) * p.C;
-        const float* c01 = pc + ((size_t)y1 * p.w + x0) * p.C;
-        const float* c11 = pc + ((size_t)y1 * p.w + x1) * p.C;
-        for (int c = 0; c < p.C; ++c) {
-            const float f = c00[c] * tw[pl][0] + c10[c] * tw[pl][1] + c01[c] * tw[pl][2] + c11[c] * tw[pl][3];
-            if (live) b.ws_feat[(size_t)i * F3 + c * 3 + pl] = f;
-            const float* wr = p.base_wT + (size_t)(c * 3 + pl) * H;
-#pragma unroll
-            for (int j = 0; j < H; ++j) acc[j] = fmaf(wr[j], f, acc[j]);
-        }
-    }
-    if constexpr (NL > 0) {
-        float enc[2 * NL];
-        hash_encode<NL>(p.hg, x[0], x[1], p.flip_z ? -x[2] : x[2], enc);
-#pragma unroll
-        for (int e = 0; e < 2 * NL; ++e) {
-            if (live) b.ws_enc[(size_t)i * (2 * NL) + e] = enc[e];
-            const float* wr = p.ingp_wT + (size_t)e * H;
-#pragma unroll
-            for (int j = 0; j < H; ++j) acc[j] = fmaf(wr[j], enc[e], acc[j]);
-        }
-#pragma unroll
-        for (int j = 0; j < H; ++j) acc[j] += p.ingp_b[j];
-    }
+    TriTap taps[3];                           // plane taps of this point: kept for the scatter at the end
+    tri_base_x<H, NL>(p, x, acc, taps, live ? b.ws_feat + (size_t)i * F3 : nullptr, live ? b.ws_enc + (size_t)i * (2 * NL) : nullptr);
     float sg = p.dens_b[0];
 #pragma unroll
     for (int j = 0; j < H; ++j) {
@@ -257,36 +332,73 @@ __global__ __launch_bounds__(WAVE) void k_triplane_backward(const TriParams p, c
         if (live) b.ws_dbase[(size_t)i * H + k] = g;
     }
     if (!live) return;
-    // ---- code planes: d feature (c, plane) = base_wT[c * 3 + plane][:] . d base_x, scattered with the bilinear weights ----------------------
-    if (b.g_code) {
-        for (int pl = 0; pl < 3; ++pl) {
-            float* gp = b.g_code + (size_t)pl * p.h * p.w * p.C;
-            for (int c = 0; c < p.C; ++c) {
-                const float* wr = p.base_wT + (size_t)(c * 3 + pl) * H;
-                float g = 0.f;
+    tri_scatter<H, NL>(p, b, x, taps, acc);
+}
+
+// Backward of k_triplane_dirnet_decode, in the design of k_triplane_backward: forward recomputed, per-point factors to the workspace.  The
+// sections are the default topology's under other names: ws_hid [N][H + 16] holds act(base_x) | SH, ws_da2 [N][H] holds d z (z = base_x +
+// dir_net(SH), the colour net's pre-activation), ws_act2 [N][H] holds act(z).  d base_x = dens_w d_sg act'(base_x) + d z.
+template <int H, int NL>
+__global__ __launch_bounds__(WAVE) void k_triplane_dirnet_backward(const TriParams p, const TriBwd b, const ShK16 kk) {
+    __shared__ float shs[16 * WAVE];
+    const int lane = threadIdx.x;
+    const int i = blockIdx.x * WAVE + lane;
+    const bool live = i < p.N;
+    const int ii = live ? i : p.N - 1;
+    const float x[3] = {p.xyz[3 * ii], p.xyz[3 * ii + 1], p.flip_z ? -p.xyz[3 * ii + 2] : p.xyz[3 * ii + 2]};
+    const int F3 = 3 * p.C;
+    float acc[H], gb[H];                      // base_x, then z, then d base_x; the density head's part of d base_x
+    TriTap taps[3];
+    tri_base_x<H, NL>(p, x, acc, taps, live ? b.ws_feat + (size_t)i * F3 : nullptr, live ? b.ws_enc + (size_t)i * (2 * NL) : nullptr);
+    float* hid = live ? b.ws_hid + (size_t)i * (H + 16) : nullptr;
+    float sg = p.dens_b[0];
 #pragma unroll
-                for (int j = 0; j < H; ++j) g = fmaf(wr[j], acc[j], g);
-                atomicAdd(gp + ((size_t)ty0[pl] * p.w + tx0[pl]) * p.C + c, g * tw[pl][0]);
-                atomicAdd(gp + ((size_t)ty0[pl] * p.w + tx1[pl]) * p.C + c, g * tw[pl][1]);
-                atomicAdd(gp + ((size_t)ty1[pl] * p.w + tx0[pl]) * p.C + c, g * tw[pl][2]);
-                atomicAdd(gp + ((size_t)ty1[pl] * p.w + tx1[pl]) * p.C + c, g * tw[pl][3]);
-            }
+    for (int j = 0; j < H; ++j) {
+        const float a = act_fn(p.activation, acc[j]);
+        if (live) hid[j] = a;
+        sg = fmaf(p.dens_w[j], a, sg);
+    }
+    const float d_sg = live ? b.g_sigma[i] * act_grad(p.sigma_activation, sg) : 0.f;
+#pragma unroll
+    for (int j = 0; j < H; ++j) gb[j] = p.dens_w[j] * d_sg * act_grad(p.activation, acc[j]);
+    float d_o[3] = {0.f, 0.f, 0.f};
+    const bool colour = p.dirs != nullptr && b.g_rgb != nullptr;
+    if (colour) {
+        tri_add_dir_net<H>(p, kk, ii, lane, shs, acc, live ? hid + H : nullptr);
+        float o[3] = {p.col2_b[0], p.col2_b[1], p.col2_b[2]};
+#pragma unroll
+        for (int j = 0; j < H; ++j) {
+            const float a = act_fn(p.activation, acc[j]);
+            if (live) b.ws_act2[(size_t)i * H + j] = a;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) o[c] = fmaf(p.col2_w[c * H + j], a, o[c]);
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float s = 1.0f / (1.0f + __expf(-o[c]));
+            d_o[c] = live ? b.g_rgb[3 * (size_t)i + c] * (1.0f + 2.0f * p.sat) * s * (1.0f - s) : 0.f;
         }
     }
-    if constexpr (NL > 0) {
-        if (b.g_table) {
-            float denc[2 * NL];
+    if (live) reinterpret_cast<f32x4*>(b.ws_do)[i] = f32x4{d_o[0], d_o[1], d_o[2], d_sg};
 #pragma unroll
-            for (int e = 0; e < 2 * NL; ++e) {
-                const float* wr = p.ingp_wT + (size_t)e * H;
-                float g = 0.f;
+    for (int j = 0; j < H; ++j) {
+        float g = gb[j];
+        if (colour) {
+            float dz = 0.f;
 #pragma unroll
-                for (int j = 0; j < H; ++j) g = fmaf(wr[j], acc[j], g);
-                denc[e] = g;
-            }
-            hash_scatter<NL>(p.hg, x[0], x[1], p.flip_z ? -x[2] : x[2], denc, b.g_table);
+            for (int c = 0; c < 3; ++c) dz = fmaf(p.col2_w[c * H + j], d_o[c], dz);
+            dz *= act_grad(p.activation, acc[j]);
+            if (live) b.ws_da2[(size_t)i * H + j] = dz;
+            g += dz;
         }
+        acc[j] = g;
+        if (live) b.ws_dbase[(size_t)i * H + j] = g;
     }
+    if (!live) return;
+    // the scatter reads base_wT / ingp_wT a second time; the fence keeps those loads from being merged with (or hoisted into) the first pass.
+    // OPEN: H = 64 with a hash branch still spills (NL = 12: 1255 VGPRs, 5 KB of scratch per lane; none at H = 64 without one, 200-380 VGPRs at H = 128)
+    asm volatile("" ::: "memory");
+    tri_scatter<H, NL>(p, b, x, taps, acc);
 }
 
 // out[pi][qi] = sum_m X[m][pi] Y[m][qi] and colsum[pi] = sum_m X[m][pi], for column windows of two row-major workspaces (leading dimensions
@@ -378,6 +490,34 @@ int launch_nl(const TriParams& p, const ShK16& kk, int n_levels, hipStream_t s) 
     return MVE_OK;
 }
 
+template <int H>
+int launch_dirnet_nl(const TriParams& p, const ShK16& kk, int n_levels, hipStream_t s) {
+    const unsigned grid = mve_cdiv((unsigned)p.N, WAVE);
+    switch (n_levels) {
+        case 0: k_triplane_dirnet_decode<H, 0><<<grid, WAVE, 0, s>>>(p, kk); break;
+        case 12: k_triplane_dirnet_decode<H, 12><<<grid, WAVE, 0, s>>>(p, kk); break;
+        case 14: k_triplane_dirnet_decode<H, 14><<<grid, WAVE, 0, s>>>(p, kk); break;
+        case 16: k_triplane_dirnet_decode<H, 16><<<grid, WAVE, 0, s>>>(p, kk); break;
+        default: mve_set_error("triplane_decode: n_levels must be 0 (no hash grid), 12, 14 or 16 (got %d)", n_levels); return MVE_ERR_ARG;
+    }
+    MVE_LAUNCH_CHECK();
+    return MVE_OK;
+}
+
+template <int H>
+int launch_dirnet_bwd_nl(const TriParams& p, const TriBwd& b, const ShK16& kk, int n_levels, hipStream_t s) {
+    const unsigned grid = mve_cdiv((unsigned)p.N, WAVE);
+    switch (n_levels) {
+        case 0: k_triplane_dirnet_backward<H, 0><<<grid, WAVE, 0, s>>>(p, b, kk); break;
+        case 12: k_triplane_dirnet_backward<H, 12><<<grid, WAVE, 0, s>>>(p, b, kk); break;
+        case 14: k_triplane_dirnet_backward<H, 14><<<grid, WAVE, 0, s>>>(p, b, kk); break;
+        case 16: k_triplane_dirnet_backward<H, 16><<<grid, WAVE, 0, s>>>(p, b, kk); break;
+        default: mve_set_error("triplane_backward: n_levels must be 0 (no hash grid), 12, 14 or 16 (got %d)", n_levels); return MVE_ERR_ARG;
+    }
+    MVE_LAUNCH_CHECK();
+    return MVE_OK;
+}
+
 }  // namespace
 
 namespace {
@@ -386,17 +526,26 @@ namespace {
 int fill_tri(const char* who, const MveTriplaneDesc* d, TriParams& p, int* nl_out) {
     MVE_CHECK(d->d_xyz && d->d_code && d->d_base_wT && d->d_base_b && d->d_dens_w && d->d_dens_b, MVE_ERR_ARG, "%s: null pointer", who);
     MVE_CHECK(d->N > 0 && d->C > 0 && d->h > 0 && d->w > 0, MVE_ERR_ARG, "%s: bad sizes N=%d C=%d h=%d w=%d", who, d->N, d->C, d->h, d->w);
-    MVE_CHECK((d->hidden == 64 || d->hidden == 128) && (d->hidden2 == 64 || d->hidden2 == 128), MVE_ERR_ARG,
-              "%s: hidden widths must be 64 or 128 (got %d, %d)", who, d->hidden, d->hidden2);
+    MVE_CHECK(d->topology == MVE_TRIPLANE_DEFAULT || d->topology == MVE_TRIPLANE_DIRNET, MVE_ERR_ARG, "%s: unknown topology %d", who, d->topology);
+    const bool dirnet = d->topology == MVE_TRIPLANE_DIRNET;
+    if (dirnet) {            // hidden2 is not read
+        MVE_CHECK(d->hidden == 64 || d->hidden == 128, MVE_ERR_ARG, "%s: the hidden width must be 64 or 128 (got %d)", who, d->hidden);
+        MVE_CHECK(d->d_dir_wT && d->d_dir_b, MVE_ERR_ARG, "%s: the dir-net topology needs d_dir_wT and d_dir_b", who);
+    } else {
+        MVE_CHECK((d->hidden == 64 || d->hidden == 128) && (d->hidden2 == 64 || d->hidden2 == 128), MVE_ERR_ARG,
+                  "%s: hidden widths must be 64 or 128 (got %d, %d)", who, d->hidden, d->hidden2);
+        MVE_CHECK(!d->d_dir_wT && !d->d_dir_b, MVE_ERR_ARG, "%s: dir_net pointers given with the default topology (set topology = MVE_TRIPLANE_DIRNET)", who);
+    }
     MVE_CHECK(d->activation >= 0 && d->activation <= 2 && d->sigma_activation >= 0 && d->sigma_activation <= 3, MVE_ERR_ARG, "%s: bad activation code", who);
     for (int k = 0; k < 6; ++k) MVE_CHECK(d->axes[k] >= 0 && d->axes[k] < 3, MVE_ERR_ARG, "%s: bad plane axis %d", who, d->axes[k]);
-    if (d->d_dirs) MVE_CHECK(d->d_col1_wT && d->d_col1_b && d->d_col2_w && d->d_col2_b, MVE_ERR_ARG, "%s: null colour-net pointer", who);
+    if (d->d_dirs) MVE_CHECK((dirnet || (d->d_col1_wT && d->d_col1_b)) && d->d_col2_w && d->d_col2_b, MVE_ERR_ARG, "%s: null colour-net pointer", who);
     memset(&p, 0, sizeof(p));
     p.xyz = d->d_xyz; p.dirs = d->d_dirs; p.code = d->d_code; p.N = d->N; p.C = d->C; p.h = d->h; p.w = d->w;
     for (int k = 0; k < 6; ++k) p.axes[k] = d->axes[k];
     p.flip_z = d->flip_z;
     p.base_wT = d->d_base_wT; p.base_b = d->d_base_b; p.ingp_wT = d->d_ingp_wT; p.ingp_b = d->d_ingp_b;
     p.dens_w = d->d_dens_w; p.dens_b = d->d_dens_b; p.col1_wT = d->d_col1_wT; p.col1_b = d->d_col1_b; p.col2_w = d->d_col2_w; p.col2_b = d->d_col2_b;
+    p.dir_wT = d->d_dir_wT; p.dir_b = d->d_dir_b;
     p.activation = d->activation; p.sigma_activation = d->sigma_activation; p.sat = d->sigmoid_saturation;
     p.sigmas = d->d_sigmas; p.rgbs = d->d_rgbs;
     int nl = 0;
@@ -428,6 +577,7 @@ extern "C" int mve_triplane_decode(const MveTriplaneDesc* d, void* stream) {
     ShK16 kk;
     she_constants(kk.k);
     hipStream_t s = (hipStream_t)stream;
+    if (d->topology == MVE_TRIPLANE_DIRNET) return d->hidden == 128 ? launch_dirnet_nl<128>(p, kk, nl, s) : launch_dirnet_nl<64>(p, kk, nl, s);
     if (d->hidden == 128 && d->hidden2 == 128) return launch_nl<128, 128>(p, kk, nl, s);
     if (d->hidden == 128 && d->hidden2 == 64) return launch_nl<128, 64>(p, kk, nl, s);
     if (d->hidden == 64 && d->hidden2 == 128) return launch_nl<64, 128>(p, kk, nl, s);
@@ -438,21 +588,28 @@ extern "C" size_t mve_triplane_backward_workspace_bytes(int N, int C, int hidden
     return sizeof(float) * tri_ws_floats((size_t)(N > 0 ? N : 0), C, hidden, hidden2, n_levels);
 }
 
+// the dir-net topology's sections are the default's with hidden2 = hidden (k_triplane_dirnet_backward)
+extern "C" size_t mve_triplane_dirnet_backward_workspace_bytes(int N, int C, int hidden, int n_levels) {
+    return sizeof(float) * tri_ws_floats((size_t)(N > 0 ? N : 0), C, hidden, hidden, n_levels);
+}
+
 extern "C" int mve_triplane_backward(const MveTriplaneDesc* d, const float* d_grad_sigmas, const float* d_grad_rgbs, const MveTriplaneGrads* g,
                                      void* d_workspace, size_t workspace_bytes, void* stream) {
     MVE_CHECK(d && g, MVE_ERR_ARG, "triplane_backward: null descriptor");
     MVE_CHECK(g->d_base_w && g->d_base_b && g->d_dens_w && g->d_dens_b, MVE_ERR_ARG, "triplane_backward: null gradient output");
     hipStream_t s = (hipStream_t)stream;
-    const int H = d->hidden, H2 = d->hidden2, F3 = 3 * d->C;
+    const bool dirnet = d->topology == MVE_TRIPLANE_DIRNET;
+    const int H = d->hidden, H2 = dirnet ? d->hidden : d->hidden2, F3 = 3 * d->C;
     const bool colour = d->d_dirs != nullptr && d_grad_rgbs != nullptr;
-    if (colour) MVE_CHECK(g->d_col1_w && g->d_col1_b && g->d_col2_w && g->d_col2_b, MVE_ERR_ARG, "triplane_backward: null colour-net gradient output");
+    if (colour && dirnet) MVE_CHECK(g->d_dir_w && g->d_dir_b && g->d_col2_w && g->d_col2_b, MVE_ERR_ARG, "triplane_backward: null dir-net / colour-net gradient output");
+    if (colour && !dirnet) MVE_CHECK(g->d_col1_w && g->d_col1_b && g->d_col2_w && g->d_col2_b, MVE_ERR_ARG, "triplane_backward: null colour-net gradient output");
     if (d->N == 0) return MVE_OK;
     TriParams p;
     int nl = 0;
     if (int rc = fill_tri("triplane_backward", d, p, &nl)) return rc;
     if (nl) MVE_CHECK(g->d_ingp_w && g->d_ingp_b, MVE_ERR_ARG, "triplane_backward: null hash-branch gradient output");
     MVE_CHECK(d_grad_sigmas && d_workspace, MVE_ERR_ARG, "triplane_backward: null pointer");
-    MVE_CHECK(workspace_bytes >= mve_triplane_backward_workspace_bytes(d->N, d->C, H, H2, nl), MVE_ERR_NOMEM, "triplane_backward: workspace too small");
+    MVE_CHECK(workspace_bytes >= mve_triplane_backward_workspace_bytes(d->N, d->C, H, H2, nl), MVE_ERR_NOMEM, "triplane_backward: workspace too small");      // (dir-net: H2 = H)
     const size_t N = (size_t)d->N;
     float* ws = (float*)d_workspace;
     TriBwd b;
@@ -472,7 +629,8 @@ extern "C" int mve_triplane_backward(const MveTriplaneDesc* d, const float* d_gr
     ShK16 kk;
     she_constants(kk.k);
     int rc;
-    if (H == 128 && H2 == 128) rc = launch_bwd_nl<128, 128>(p, b, kk, nl, s);
+    if (dirnet) rc = H == 128 ? launch_dirnet_bwd_nl<128>(p, b, kk, nl, s) : launch_dirnet_bwd_nl<64>(p, b, kk, nl, s);
+    else if (H == 128 && H2 == 128) rc = launch_bwd_nl<128, 128>(p, b, kk, nl, s);
     else if (H == 128 && H2 == 64) rc = launch_bwd_nl<128, 64>(p, b, kk, nl, s);
     else if (H == 64 && H2 == 128) rc = launch_bwd_nl<64, 128>(p, b, kk, nl, s);
     else rc = launch_bwd_nl<64, 64>(p, b, kk, nl, s);
@@ -484,7 +642,11 @@ extern "C" int mve_triplane_backward(const MveTriplaneDesc* d, const float* d_gr
         if ((rc = tri_xty(b.ws_dbase, H, H, b.ws_enc, 2 * nl, 2 * nl, M, g->d_ingp_w, 2 * nl, g->d_ingp_b, partial, s))) return rc;
     }
     if ((rc = tri_xty(b.ws_do + 3, 4, 1, b.ws_hid, H + 16, H, M, g->d_dens_w, H, g->d_dens_b, partial, s))) return rc;
-    if (colour) {
+    if (colour && dirnet) {
+        // dir_net.0.weight [H][16] = d z^T SH, bias = colsum(d z); color_net.0.weight [3][H] = d o^T act(z)
+        if ((rc = tri_xty(b.ws_da2, H, H, b.ws_hid + H, H + 16, 16, M, g->d_dir_w, 16, g->d_dir_b, partial, s))) return rc;
+        if ((rc = tri_xty(b.ws_do, 4, 3, b.ws_act2, H, H, M, g->d_col2_w, H, g->d_col2_b, partial, s))) return rc;
+    } else if (colour) {
         if ((rc = tri_xty(b.ws_da2, H2, H2, b.ws_hid, H + 16, H + 16, M, g->d_col1_w, H + 16, g->d_col1_b, partial, s))) return rc;
         if ((rc = tri_xty(b.ws_do, 4, 3, b.ws_act2, H2, H2, M, g->d_col2_w, H2, g->d_col2_b, partial, s))) return rc;
     }

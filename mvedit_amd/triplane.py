@@ -2,8 +2,16 @@
 `point_density_decode` (lib/models/decoders/triplane_decoder.py:107-204) and `TriPlaneiNGPDecoder.point_decode`
 (lib/models/decoders/triplane_ingp_decoder.py:142-212) -> mve_triplane_decode (csrc/triplane.hip): plane fetches, the base / density /
 colour MLPs, the SH direction encoding and (iNGP variant) the hash-grid branch in ONE launch, one wave per 64 points.
-Supported topology = the classes' defaults (one Linear in base_net / density_net / ingp_base_net, Linear-act-Linear colour net over
-cat[act(base), SH_4(dir)], dir_layers=None, no scene_base / code dropout); anything else raises.
+Two topologies are built, recognised from the state dict's keys (or from the layer lists of `from_config`):
+  default   the classes' constructor defaults: one Linear in base_net / density_net / ingp_base_net, Linear-act-Linear colour net over
+            cat[act(base), SH_4(dir)], dir_layers=None;
+  dir-net   what every config file of the reference asks for (base_layers=[3C, H], density_layers=[H, 1], color_layers=[H, 3],
+            dir_layers=[16, H]): dir_net = Linear(16 -> H), rgb = sat(sigmoid(color_net(act(base_x + dir_net(SH_4(dir)))))), color_net = one
+            Linear(H -> 3).  H in {64, 128}.
+Anything else (deeper stacks, a mixture of the two, scene_base, code dropout, other widths) raises NotImplementedError -- it is never computed
+another way.  Out of scope: the `preprocessor` (VAEDecoder) / code_activation in front of point_decode (the planes handed in are already
+pre-processed, as in the reference's own point_decode), 16-bit code planes, more than one scene per call, a fused ray-march render over
+tri-planes, second-order grid_sample.
 Gradients: `point_decode_autograd` carries autograd history w.r.t. the code planes and `parameters()` (every Linear and the hash table)
 through mve_triplane_backward -- what nerf_optim (lib/pipelines/mvedit_3d_pipeline.py:507-633) needs to optimise a TriPlaneiNGPDecoder
 scene.  Plain `point_decode` is forward only and refuses tensors that require grad instead of silently cutting the graph.  No gradient
@@ -30,12 +38,17 @@ class _Desc(ctypes.Structure):
                 ('d_dens_w', ctypes.c_void_p), ('d_dens_b', ctypes.c_void_p), ('d_col1_wT', ctypes.c_void_p), ('d_col1_b', ctypes.c_void_p),
                 ('d_col2_w', ctypes.c_void_p), ('d_col2_b', ctypes.c_void_p),
                 ('activation', ctypes.c_int32), ('sigma_activation', ctypes.c_int32), ('sigmoid_saturation', ctypes.c_float),
-                ('d_sigmas', ctypes.c_void_p), ('d_rgbs', ctypes.c_void_p)]
+                ('d_sigmas', ctypes.c_void_p), ('d_rgbs', ctypes.c_void_p),
+                ('topology', ctypes.c_int32), ('d_dir_wT', ctypes.c_void_p), ('d_dir_b', ctypes.c_void_p)]
 
 
 class _Grads(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ('d_code', 'd_table', 'd_base_w', 'd_base_b', 'd_ingp_w', 'd_ingp_b', 'd_dens_w', 'd_dens_b',
-                                                'd_col1_w', 'd_col1_b', 'd_col2_w', 'd_col2_b')]
+                                                'd_col1_w', 'd_col1_b', 'd_col2_w', 'd_col2_b', 'd_dir_w', 'd_dir_b')]
+
+
+TOPOLOGY_DEFAULT, TOPOLOGY_DIRNET = 0, 1
+_NETS = ('base_net.', 'density_net.', 'color_net.', 'dir_net.', 'ingp_base_net.')
 
 
 class TriPlaneDecoder:
@@ -59,26 +72,99 @@ class TriPlaneDecoder:
               'color_net.2.weight': ('col2_w', False), 'color_net.2.bias': ('col2_b', False),
               'ingp_base_net.0.weight': ('ingp_wT', True), 'ingp_base_net.0.bias': ('ingp_b', False)}
 
+    # the dir-net topology: its one-Linear colour net is the kernel's output layer (col2), dir_net goes in transposed like every [in][out] weight
+    _NAMES_DIRNET = {'base_net.0.weight': ('base_wT', True), 'base_net.0.bias': ('base_b', False),
+                     'density_net.0.weight': ('dens_w', False), 'density_net.0.bias': ('dens_b', False),
+                     'dir_net.0.weight': ('dir_wT', True), 'dir_net.0.bias': ('dir_b', False),
+                     'color_net.0.weight': ('col2_w', False), 'color_net.0.bias': ('col2_b', False),
+                     'ingp_base_net.0.weight': ('ingp_wT', True), 'ingp_base_net.0.bias': ('ingp_b', False)}
+    _UNBUILT = ('only two tri-plane decoder topologies are built: the default (one Linear per base / density / ingp net, Linear-act-Linear colour '
+                'net over cat[act(base), SH], no dir_net) and the dir-net one (one Linear per base / density / ingp / dir / colour net); widths 64 '
+                'or 128, no scene_base')
+    topology, _names = TOPOLOGY_DEFAULT, _NAMES
+    cfg_layers = None                   # from_config: (topology, 3C, hidden, hidden2 or None) the state dict has to agree with
+
     def load_state_dict(self, sd):
-        self.params = {}                 # reference name -> fp32 tensor in the reference's own layout (the leaves of point_decode_autograd)
-        for name, t in sd.items():
-            if name in self._NAMES:
-                self.params[name] = t.detach().to(self.device, torch.float32).clone().contiguous()
-            elif name == 'encoder.params':
-                self.params[name] = t.detach().to(self.device, torch.float32).clone().contiguous()
-        self._pack()
-        for name in sd:
-            if name in self._NAMES or name == 'encoder.params':
-                continue
-            if name.startswith(('base_net.', 'density_net.', 'color_net.', 'dir_net.', 'ingp_base_net.', 'scene_base')):
-                raise NotImplementedError(f'{name}: only the default tri-plane decoder topology is built (one Linear per base / density / ingp '
-                                          'net, Linear-act-Linear colour net, no dir_net / scene_base)')
-        missing = [k for k in ('base_wT', 'base_b', 'dens_w', 'dens_b', 'col1_wT', 'col1_b', 'col2_w', 'col2_b') if k not in self.w]
+        keys = [k for k in sd if k.startswith(_NETS) or k.startswith('scene_base')]          # preprocessor.* and the like: not read by point_decode
+        for name in keys:
+            if name.startswith('scene_base'):
+                raise NotImplementedError(f'{name}: {self._UNBUILT}')
+        dirnet = any(k.startswith('dir_net.') for k in keys)
+        names = self._NAMES_DIRNET if dirnet else self._NAMES
+        for name in keys:
+            if name not in names:            # a deeper stack (base_net.2.*, dir_net.2.*, a third colour Linear) or, with dir_net.*, the default's color_net.2.*
+                raise NotImplementedError(f'{name}: {self._UNBUILT}')
+        need = [n for n in names if not n.startswith('ingp_base_net.') or self.hash is not None]
+        if self.hash is not None:
+            need.append('encoder.params')
+        missing = [n for n in need if n not in sd]
         if missing:
-            raise KeyError(f'tri-plane decoder: missing parameters {missing}')
-        H, H2 = self.w['base_wT'].shape[1], self.w['col1_wT'].shape[1]
-        assert self.w['col1_wT'].shape[0] == H + 16 and self.w['dens_w'].numel() == H and self.w['col2_w'].shape == (3, H2), 'unexpected layer widths'
+            raise KeyError(f'tri-plane decoder ({"dir-net" if dirnet else "default"} topology): missing parameters {missing}')
+        shp = {n: tuple(sd[n].shape) for n in need}
+        H = shp['base_net.0.weight'][0]
+        if H not in (64, 128):
+            raise NotImplementedError(f'base_net.0.weight: hidden width {H}; {self._UNBUILT}')
+        if dirnet:
+            if shp['color_net.0.weight'] != (3, H):
+                raise NotImplementedError(f'color_net.0.weight: shape {shp["color_net.0.weight"]}, expected (3, {H}); {self._UNBUILT}')
+            assert shp['dir_net.0.weight'] == (H, 16) and shp['dir_net.0.bias'] == (H,), 'unexpected dir_net widths'
+            H2 = None
+        else:
+            H2 = shp['color_net.0.weight'][0]
+            if H2 not in (64, 128):
+                raise NotImplementedError(f'color_net.0.weight: hidden width {H2}; {self._UNBUILT}')
+            assert shp['color_net.0.weight'][1] == H + 16 and shp['color_net.2.weight'] == (3, H2), 'unexpected layer widths'
+        assert int(np.prod(shp['density_net.0.weight'])) == H, 'unexpected layer widths'
+        if self.cfg_layers is not None:
+            got = (TOPOLOGY_DIRNET if dirnet else TOPOLOGY_DEFAULT, shp['base_net.0.weight'][1], H, H2)
+            if got != self.cfg_layers:
+                raise ValueError(f'tri-plane decoder: the state dict (topology, inputs, hidden, hidden2) = {got} does not match the config {self.cfg_layers}')
+        self.topology, self._names = (TOPOLOGY_DIRNET if dirnet else TOPOLOGY_DEFAULT), names
+        self.w = {}
+        # reference name -> fp32 tensor in the reference's own layout (the leaves of point_decode_autograd)
+        self.params = {n: sd[n].detach().to(self.device, torch.float32).clone().contiguous() for n in sd if n in names or n == 'encoder.params'}
+        self._packed_sig = None
+        self._pack()
         return self
+
+    @classmethod
+    def from_config(cls, cfg, device='cuda', **kwargs):
+        """The reference's decoder dict as its config files write it (configs/**: model.decoder) -> a decoder waiting for load_state_dict.
+        Read: plane_cfg, flip_z, base_layers, density_layers, color_layers, use_dir_enc, dir_layers, activation, sigma_activation,
+        sigmoid_saturation, interp_mode, bound (+ base_resolution, max_resolution, n_levels for TriPlaneiNGPDecoder).  What point_decode does not
+        read (type, preprocessor, code_reshape, preproc_size, max_steps, weight_culling_th, ...) is ignored; settings that change point_decode
+        and are not built are refused.  `kwargs` go to the constructor (e.g. log2_hashmap_size)."""
+        cfg = dict(cfg)
+        if not cfg.get('use_dir_enc', True):
+            raise NotImplementedError('use_dir_enc=False: the colour net without a direction encoding is not built')
+        if cfg.get('interp_mode', 'bilinear') != 'bilinear':
+            raise NotImplementedError(f'interp_mode={cfg["interp_mode"]!r}: only bilinear plane sampling is built')
+        if cfg.get('scene_base_size') is not None:
+            raise NotImplementedError('scene_base_size: scene_base is not built')
+        if cfg.get('code_dropout', 0.0) > 0:
+            raise NotImplementedError('code_dropout > 0 is not built (a training-time Dropout2d on the planes)')
+        if cfg.get('ingp_base_layers', 1) != 1:
+            raise NotImplementedError(f'ingp_base_layers={cfg["ingp_base_layers"]}: {cls._UNBUILT}')
+        base, dens = list(cfg.get('base_layers', [3 * 32, 128])), list(cfg.get('density_layers', [128, 1]))
+        col, dirl = list(cfg.get('color_layers', [128, 128, 3])), cfg.get('dir_layers')
+        H = base[-1]
+        ok = len(base) == 2 and base[0] % 3 == 0 and H in (64, 128) and dens == [H, 1]
+        if dirl is None:             # the constructor widens color_layers[0] by the 16 SH features itself
+            ok = ok and len(col) == 3 and col[0] == H and col[1] in (64, 128) and col[2] == 3
+            layers = (TOPOLOGY_DEFAULT, base[0], H, col[1] if ok else None)
+        else:
+            ok = ok and list(dirl) == [16, H] and col == [H, 3]
+            layers = (TOPOLOGY_DIRNET, base[0], H, None)
+        if not ok:
+            raise NotImplementedError(f'base_layers={base}, density_layers={dens}, color_layers={col}, dir_layers={dirl}: {cls._UNBUILT}')
+        kw = {k: cfg[k] for k in ('plane_cfg', 'activation', 'sigma_activation', 'sigmoid_saturation', 'flip_z', 'bound') if k in cfg}
+        if cls._HASH_KEYS:
+            kw.update({k: cfg[k] for k in cls._HASH_KEYS if k in cfg})
+        dec = cls(device=device, **kw, **kwargs)
+        dec.cfg_layers, dec.topology = layers, layers[0]
+        return dec
+
+    _HASH_KEYS = ()
 
     def _pack(self, tensors=None):
         """kernel-side copies of the parameters: weight matrices transposed to [in][out] (one input's fan-out = one contiguous scalar load).
@@ -96,8 +182,8 @@ class TriPlaneDecoder:
         else:
             self._packed_sig = None
         for name, t in src.items():
-            if name in self._NAMES:
-                key, transpose = self._NAMES[name]
+            if name in self._names:
+                key, transpose = self._names[name]
                 t = t.detach()
                 self.w[key] = t.t().clone(memory_format=torch.contiguous_format) if transpose else t.clone()      # (.t().contiguous() aliases a [1, N] weight)
             elif name == 'encoder.params':
@@ -157,7 +243,9 @@ class TriPlaneDecoder:
             ds.axes[k] = self.axes[k]
         ds.flip_z = int(self.flip_z)
         ds.d_base_wT, ds.d_base_b = W['base_wT'].data_ptr(), W['base_b'].data_ptr()
-        ds.hidden, ds.hidden2 = W['base_wT'].shape[1], W['col1_wT'].shape[1]
+        dirnet = self.topology == TOPOLOGY_DIRNET
+        ds.hidden = W['base_wT'].shape[1]
+        ds.hidden2 = 0 if dirnet else W['col1_wT'].shape[1]             # ignored by the dir-net topology
         keep = []
         if self.hash is not None:
             meta = self.hash['meta']
@@ -168,7 +256,11 @@ class TriPlaneDecoder:
             ds.n_levels, ds.bound = len(meta), self.bound
             ds.level_scale, ds.level_res, ds.level_offset, ds.level_size = (a.ctypes.data for a in arr)
         ds.d_dens_w, ds.d_dens_b = W['dens_w'].data_ptr(), W['dens_b'].data_ptr()
-        ds.d_col1_wT, ds.d_col1_b, ds.d_col2_w, ds.d_col2_b = (W[k].data_ptr() for k in ('col1_wT', 'col1_b', 'col2_w', 'col2_b'))
+        ds.d_col2_w, ds.d_col2_b = W['col2_w'].data_ptr(), W['col2_b'].data_ptr()
+        if dirnet:
+            ds.topology, ds.d_dir_wT, ds.d_dir_b = TOPOLOGY_DIRNET, W['dir_wT'].data_ptr(), W['dir_b'].data_ptr()
+        else:
+            ds.d_col1_wT, ds.d_col1_b = W['col1_wT'].data_ptr(), W['col1_b'].data_ptr()
         ds.activation, ds.sigma_activation, ds.sigmoid_saturation = self.activation, self.sigma_activation, self.sigmoid_saturation
         ds.d_sigmas, ds.d_rgbs = (sig.data_ptr() if sig is not None else None), (rgb.data_ptr() if rgb is not None else None)
         return ds, keep
@@ -187,11 +279,16 @@ class TriPlaneDecoder:
         """-> (grad code [1,3,C,h,w] or None, {reference name: gradient})"""
         xyz, d, cl, N, C, h, w = self._prep(xyz, d, code)
         dev, W = self.device, self.w
-        H, H2 = W['base_wT'].shape[1], W['col1_wT'].shape[1]
+        dirnet = self.topology == TOPOLOGY_DIRNET
+        H = W['base_wT'].shape[1]
         nl = len(self.hash['meta']) if self.hash is not None else 0
         z = lambda *sh: torch.zeros(*sh, dtype=torch.float32, device=dev)
-        g = {'base_net.0.weight': z(H, 3 * C), 'base_net.0.bias': z(H), 'density_net.0.weight': z(1, H), 'density_net.0.bias': z(1),
-             'color_net.0.weight': z(H2, H + 16), 'color_net.0.bias': z(H2), 'color_net.2.weight': z(3, H2), 'color_net.2.bias': z(3)}
+        g = {'base_net.0.weight': z(H, 3 * C), 'base_net.0.bias': z(H), 'density_net.0.weight': z(1, H), 'density_net.0.bias': z(1)}
+        if dirnet:
+            g.update({'dir_net.0.weight': z(H, 16), 'dir_net.0.bias': z(H), 'color_net.0.weight': z(3, H), 'color_net.0.bias': z(3)})
+        else:
+            H2 = W['col1_wT'].shape[1]
+            g.update({'color_net.0.weight': z(H2, H + 16), 'color_net.0.bias': z(H2), 'color_net.2.weight': z(3, H2), 'color_net.2.bias': z(3)})
         if nl:
             g.update({'ingp_base_net.0.weight': z(H, 2 * nl), 'ingp_base_net.0.bias': z(H), 'encoder.params': torch.zeros_like(self.params['encoder.params'])})
         g_code = z(3, h, w, C) if need_code else None
@@ -201,10 +298,17 @@ class TriPlaneDecoder:
         if nl:
             gs.d_ingp_w, gs.d_ingp_b = g['ingp_base_net.0.weight'].data_ptr(), g['ingp_base_net.0.bias'].data_ptr()
         gs.d_dens_w, gs.d_dens_b = g['density_net.0.weight'].data_ptr(), g['density_net.0.bias'].data_ptr()
-        gs.d_col1_w, gs.d_col1_b = g['color_net.0.weight'].data_ptr(), g['color_net.0.bias'].data_ptr()
-        gs.d_col2_w, gs.d_col2_b = g['color_net.2.weight'].data_ptr(), g['color_net.2.bias'].data_ptr()
+        if dirnet:
+            gs.d_dir_w, gs.d_dir_b = g['dir_net.0.weight'].data_ptr(), g['dir_net.0.bias'].data_ptr()
+            gs.d_col2_w, gs.d_col2_b = g['color_net.0.weight'].data_ptr(), g['color_net.0.bias'].data_ptr()
+        else:
+            gs.d_col1_w, gs.d_col1_b = g['color_net.0.weight'].data_ptr(), g['color_net.0.bias'].data_ptr()
+            gs.d_col2_w, gs.d_col2_b = g['color_net.2.weight'].data_ptr(), g['color_net.2.bias'].data_ptr()
         ds, keep = self._desc(xyz, d, cl, N, C, h, w, None, None)
-        nbytes = _lib.raw('mve_triplane_backward_workspace_bytes')(N, C, H, H2, nl)
+        if dirnet:
+            nbytes = _lib.raw('mve_triplane_dirnet_backward_workspace_bytes')(N, C, H, nl)
+        else:
+            nbytes = _lib.raw('mve_triplane_backward_workspace_bytes')(N, C, H, H2, nl)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         g_sig = g_sig.to(dev, torch.float32).contiguous()
         g_rgb = g_rgb.to(dev, torch.float32).contiguous() if (g_rgb is not None and d is not None) else None
@@ -221,6 +325,8 @@ class TriPlaneDecoder:
 class TriPlaneiNGPDecoder(TriPlaneDecoder):
     """+ the hash-grid branch: base_x = base_net(plane features) + ingp_base_net(HashGrid((xyz + bound) / (2 bound))); the level table follows
     the constructor (triplane_ingp_decoder.py:102-114: 2 features per level, log2_hashmap_size 19, Smoothstep)."""
+
+    _HASH_KEYS = ('base_resolution', 'max_resolution', 'n_levels')
 
     def __init__(self, *args, base_resolution=16, max_resolution=320, n_levels=12, log2_hashmap_size=19, **kwargs):
         super().__init__(*args, **kwargs)
