@@ -1479,6 +1479,18 @@ MVE_API size_t mve_triplane_backward_workspace_bytes(int N, int C, int hidden, i
 MVE_API size_t mve_triplane_dirnet_backward_workspace_bytes(int N, int C, int hidden, int n_levels);
 MVE_API int mve_triplane_backward(const MveTriplaneDesc* desc, const float* d_grad_sigmas, const float* d_grad_rgbs, const MveTriplaneGrads* grads,
                                   void* d_workspace, size_t workspace_bytes, void* stream);
+/* VolumeRenderer.forward, eval branch (lib/models/decoders/base_volume_renderer.py:264-329) over a tri-plane scene as ONE launch: near/far from
+ * the aabb, occupancy-grid march (cascade count 1, no contraction, noise 0), the decode of mve_triplane_decode per occupied sample (both
+ * topologies, hidden / hidden2 in {64, 128}, n_levels in {0, 12, 14, 16}) and compositing per ray with mve_nerf_render_rays' arithmetic and
+ * termination rules.  What depends on the ray's direction alone (SH_4(d) and its product with dir_net / the SH rows of color_net.0) is computed
+ * once per ray, so the sums run in another order than mve_triplane_decode's: close to, not bit-identical with, a render built on it.
+ * The descriptor is read as mve_triplane_decode reads it, except that d_xyz, d_dirs, N, d_sigmas and d_rgbs are ignored, the colour net is
+ * always needed and `bound` (the half-extent of the marched cube) must be set whether or not there is a hash grid.
+ * Outputs [N], [N] (sum of w / t), [N,3]; d_n_samples [N] optional.  Deterministic; a ray's result does not depend on the other rays. */
+MVE_API int mve_triplane_render_rays(const MveTriplaneDesc* desc, const float* d_rays_o, const float* d_rays_d, uint32_t N,
+                                     const uint8_t* d_bitfield, uint32_t grid_size, const float* d_aabb, float min_near, float dt_gamma,
+                                     uint32_t max_steps, float T_thresh, float* d_weights_sum, float* d_depth, float* d_image,
+                                     int32_t* d_n_samples, void* stream);
 
 /* Mip-mapped texture path: what the reference gets from nvdiffrast with MeshRenderer(texture_filter='linear-mipmap-linear') -- its default
  * (lib/models/decoders/mesh_renderer/base_mesh_renderer.py:196) -- in forward (:241, :260-264, :357-361), get_cam_weights_uv (:442, :466-475,

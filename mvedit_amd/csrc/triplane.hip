@@ -200,6 +200,148 @@ __global__ __launch_bounds__(WAVE) void k_triplane_dirnet_decode(const TriParams
     }
 }
 
+// ---- fused eval render (VolumeRenderer.forward's eval branch, lib/models/decoders/base_volume_renderer.py:264-329, over a tri-plane scene) ----
+// One launch: slab test, occupancy-grid DDA (GridWalker, raymarch_core.h), decode per occupied sample, front-to-back compositing with
+// nerf.hip's k_render_rays' arithmetic and stop rule.  One ray per lane, one wave per 64 consecutive rays, weights wave-uniform, no atomics, no
+// barrier: a ray's result depends on nothing but the ray.
+// What depends on the direction alone is computed ONCE PER RAY and kept in LDS ([j][lane], each lane reads back its own column):
+//   dir-net topology   v[j] = dir_b[j] + sum_k dir_wT[k][j] SH_k(d), H values; a sample adds it to base_x: z = base_x + v
+//   default topology   v[j] = col1_b[j] + sum_k col1_wT[H + k][j] SH_k(d), H2 values: the start of the first colour layer's accumulator
+// so a sample costs no SH evaluation and 16 x H (H2) fewer FMAs than point_decode, and the vector costs no VGPRs next to acc[H].  The sums
+// run in another order than k_triplane_(dirnet_)decode's (bias and direction part first), i.e. not bit-identical with point_decode.
+// LDS per wave: dir-net H * 256 B (16 / 32 KiB -> 10 / 5 waves per CU of 160 KiB); default (H2 + H) * 256 B (32 / 48 / 64 KiB -> 5 / 3 / 2).
+struct TriRender {
+    const float *rays_o, *rays_d, *aabb;
+    uint32_t N;
+    float min_near, T_thresh;
+    float *weights_sum, *depth, *image;
+    int32_t* n_samples;
+};
+
+// pre[j][lane] = b[j] + sum_k wT[k][j] SH_k(d), j < HV.  The 16 SH values are staged in the first 16 rows of pre itself (same lane, program
+// order) so that the loop over them stays a run-time loop (see tri_add_dir_net).
+template <int HV>
+__device__ __forceinline__ void tri_ray_dir_vector(const float* b, const float* wT, const ShK16& kk, const float3p d, int lane, float* pre) {
+    {
+        float sh[16];
+        she_eval(kk.k, d.x, d.y, d.z, 4, sh, nullptr);
+#pragma unroll
+        for (int k = 0; k < 16; ++k) pre[k * WAVE + lane] = sh[k];
+    }
+    float v[HV];
+#pragma unroll
+    for (int j = 0; j < HV; ++j) v[j] = b[j];
+#pragma unroll 1
+    for (int k = 0; k < 16; ++k) {
+        const float a = pre[k * WAVE + lane];
+        const float* wr = wT + (size_t)k * HV;
+#pragma unroll
+        for (int j = 0; j < HV; ++j) v[j] = fmaf(wr[j], a, v[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < HV; ++j) pre[j * WAVE + lane] = v[j];
+}
+
+__device__ __forceinline__ float tri_rgb_out(const TriParams& p, float o) { return (1.0f / (1.0f + __expf(-o))) * (1.0f + 2.0f * p.sat) - p.sat; }
+
+// one sample of the dir-net topology: k_triplane_dirnet_decode with the ray's vector in place of tri_add_dir_net
+template <int H, int NL>
+__device__ __forceinline__ void tri_dirnet_sample(const TriParams& p, const float (&x)[3], const float* pre, int lane, float& sigma, float (&c)[3]) {
+    float acc[H];
+    tri_base_x<H, NL>(p, x, acc);
+    float sg = p.dens_b[0];
+#pragma unroll
+    for (int j = 0; j < H; ++j) sg = fmaf(p.dens_w[j], act_fn(p.activation, acc[j]), sg);
+    sigma = act_fn(p.sigma_activation, sg);
+    float o[3] = {p.col2_b[0], p.col2_b[1], p.col2_b[2]};
+#pragma unroll
+    for (int j = 0; j < H; ++j) {
+        const float a = act_fn(p.activation, acc[j] + pre[j * WAVE + lane]);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) o[k] = fmaf(p.col2_w[k * H + j], a, o[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) c[k] = tri_rgb_out(p, o[k]);
+}
+
+// one sample of the default topology: k_triplane_decode with the first colour layer started from the ray's vector (hid: [H][WAVE])
+template <int H, int H2, int NL>
+__device__ __forceinline__ void tri_default_sample(const TriParams& p, const float (&x)[3], const float* pre, float* hid, int lane, float& sigma,
+                                                   float (&c)[3]) {
+    {
+        float acc[H];
+        tri_base_x<H, NL>(p, x, acc);
+        float sg = p.dens_b[0];
+#pragma unroll
+        for (int j = 0; j < H; ++j) {
+            const float a = act_fn(p.activation, acc[j]);
+            hid[j * WAVE + lane] = a;
+            sg = fmaf(p.dens_w[j], a, sg);
+        }
+        sigma = act_fn(p.sigma_activation, sg);
+    }
+    float a2[H2];
+#pragma unroll
+    for (int j = 0; j < H2; ++j) a2[j] = pre[j * WAVE + lane];
+    for (int k = 0; k < H; ++k) {
+        const float a = hid[k * WAVE + lane];
+        const float* wr = p.col1_wT + (size_t)k * H2;
+#pragma unroll
+        for (int j = 0; j < H2; ++j) a2[j] = fmaf(wr[j], a, a2[j]);
+    }
+    float o[3] = {p.col2_b[0], p.col2_b[1], p.col2_b[2]};
+#pragma unroll
+    for (int j = 0; j < H2; ++j) {
+        const float a = act_fn(p.activation, a2[j]);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) o[k] = fmaf(p.col2_w[k * H2 + j], a, o[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) c[k] = tri_rgb_out(p, o[k]);
+}
+
+template <int TOPO, int H, int H2, int NL>
+__global__ __launch_bounds__(WAVE) void k_triplane_render_rays(const TriParams p, const ShK16 kk, const MarchParams mp, const TriRender r) {
+    constexpr bool DIRNET = TOPO == MVE_TRIPLANE_DIRNET;
+    constexpr int HV = DIRNET ? H : H2;
+    __shared__ float lds[(HV + (DIRNET ? 0 : H)) * WAVE];          // the ray's direction vector [HV][lane] (+ default topology: act(base_x) [H][lane])
+    const int lane = threadIdx.x;
+    const uint32_t n = blockIdx.x * WAVE + lane;
+    if (n >= r.N) return;
+    const float3p o = reinterpret_cast<const float3p*>(r.rays_o)[n];
+    const float3p d = reinterpret_cast<const float3p*>(r.rays_d)[n];
+    float near, far;
+    near_far_one(o, d, r.aabb, r.min_near, near, far);
+    if (near < far) {                                  // a ray that misses the box takes no sample
+        if constexpr (DIRNET) tri_ray_dir_vector<HV>(p.dir_b, p.dir_wT, kk, d, lane, lds);
+        else tri_ray_dir_vector<HV>(p.col1_b, p.col1_wT + (size_t)H * H2, kk, d, lane, lds);
+    }
+    GridWalker w;
+    w.init(mp, r.rays_o + 3ull * n, r.rays_d + 3ull * n);
+    float ws = 0.f, dep = 0.f, cr = 0.f, cg = 0.f, cb = 0.f;
+    float t = near;
+    t += w.step_len(t) * 0.0f;                        // eval mode: noise = 0 (as k_render_rays)
+    const uint32_t cnt = w.walk(t, far, mp.max_steps, [&](float cx, float cy, float cz, float tn, float dt) {
+        const float x[3] = {cx, cy, p.flip_z ? -cz : cz};
+        float sigma, c[3];
+        if constexpr (DIRNET) tri_dirnet_sample<H, NL>(p, x, lds, lane, sigma, c);
+        else tri_default_sample<H, H2, NL>(p, x, lds, lds + HV * WAVE, lane, sigma, c);
+        const float alpha = 1.0f - __expf(-sigma * dt);         // kernel_composite_rays, raymarching.cu:877-899
+        const float T = 1 - ws;
+        const float wgt = alpha * T;
+        ws += wgt;
+        dep += wgt / tn;
+        cr += wgt * c[0];
+        cg += wgt * c[1];
+        cb += wgt * c[2];
+        return !(T < r.T_thresh);
+    });
+    r.weights_sum[n] = ws;
+    r.depth[n] = dep;
+    reinterpret_cast<float3p*>(r.image)[n] = float3p{cr, cg, cb};
+    if (r.n_samples) r.n_samples[n] = (int32_t)cnt;
+}
+
 // d act(x) / dx for the hidden activations and the density head (trunc_exp: lib/ops/activation.py:17-20, g * clamp(exp(x), 1e-6, 1e6))
 __device__ __forceinline__ float act_grad(int a, float x) {
     if (a == 0) return x > 0.f ? 1.f : 0.f;
@@ -523,9 +665,11 @@ int launch_dirnet_bwd_nl(const TriParams& p, const TriBwd& b, const ShK16& kk, i
 namespace {
 
 // validation shared by the forward and the backward; fills p, returns the number of hash-grid levels through *nl_out
-int fill_tri(const char* who, const MveTriplaneDesc* d, TriParams& p, int* nl_out) {
-    MVE_CHECK(d->d_xyz && d->d_code && d->d_base_wT && d->d_base_b && d->d_dens_w && d->d_dens_b, MVE_ERR_ARG, "%s: null pointer", who);
-    MVE_CHECK(d->N > 0 && d->C > 0 && d->h > 0 && d->w > 0, MVE_ERR_ARG, "%s: bad sizes N=%d C=%d h=%d w=%d", who, d->N, d->C, d->h, d->w);
+// (render: the fused ray-march render brings its own sample points and directions -- d_xyz, d_dirs, N, d_sigmas and d_rgbs are not read, the
+// colour net is always needed)
+int fill_tri(const char* who, const MveTriplaneDesc* d, TriParams& p, int* nl_out, bool render = false) {
+    MVE_CHECK((render || d->d_xyz) && d->d_code && d->d_base_wT && d->d_base_b && d->d_dens_w && d->d_dens_b, MVE_ERR_ARG, "%s: null pointer", who);
+    MVE_CHECK((render || d->N > 0) && d->C > 0 && d->h > 0 && d->w > 0, MVE_ERR_ARG, "%s: bad sizes N=%d C=%d h=%d w=%d", who, d->N, d->C, d->h, d->w);
     MVE_CHECK(d->topology == MVE_TRIPLANE_DEFAULT || d->topology == MVE_TRIPLANE_DIRNET, MVE_ERR_ARG, "%s: unknown topology %d", who, d->topology);
     const bool dirnet = d->topology == MVE_TRIPLANE_DIRNET;
     if (dirnet) {            // hidden2 is not read
@@ -538,16 +682,16 @@ int fill_tri(const char* who, const MveTriplaneDesc* d, TriParams& p, int* nl_ou
     }
     MVE_CHECK(d->activation >= 0 && d->activation <= 2 && d->sigma_activation >= 0 && d->sigma_activation <= 3, MVE_ERR_ARG, "%s: bad activation code", who);
     for (int k = 0; k < 6; ++k) MVE_CHECK(d->axes[k] >= 0 && d->axes[k] < 3, MVE_ERR_ARG, "%s: bad plane axis %d", who, d->axes[k]);
-    if (d->d_dirs) MVE_CHECK((dirnet || (d->d_col1_wT && d->d_col1_b)) && d->d_col2_w && d->d_col2_b, MVE_ERR_ARG, "%s: null colour-net pointer", who);
+    if (d->d_dirs || render) MVE_CHECK((dirnet || (d->d_col1_wT && d->d_col1_b)) && d->d_col2_w && d->d_col2_b, MVE_ERR_ARG, "%s: null colour-net pointer", who);
     memset(&p, 0, sizeof(p));
-    p.xyz = d->d_xyz; p.dirs = d->d_dirs; p.code = d->d_code; p.N = d->N; p.C = d->C; p.h = d->h; p.w = d->w;
+    if (!render) { p.xyz = d->d_xyz; p.dirs = d->d_dirs; p.N = d->N; p.sigmas = d->d_sigmas; p.rgbs = d->d_rgbs; }
+    p.code = d->d_code; p.C = d->C; p.h = d->h; p.w = d->w;
     for (int k = 0; k < 6; ++k) p.axes[k] = d->axes[k];
     p.flip_z = d->flip_z;
     p.base_wT = d->d_base_wT; p.base_b = d->d_base_b; p.ingp_wT = d->d_ingp_wT; p.ingp_b = d->d_ingp_b;
     p.dens_w = d->d_dens_w; p.dens_b = d->d_dens_b; p.col1_wT = d->d_col1_wT; p.col1_b = d->d_col1_b; p.col2_w = d->d_col2_w; p.col2_b = d->d_col2_b;
     p.dir_wT = d->d_dir_wT; p.dir_b = d->d_dir_b;
     p.activation = d->activation; p.sigma_activation = d->sigma_activation; p.sat = d->sigmoid_saturation;
-    p.sigmas = d->d_sigmas; p.rgbs = d->d_rgbs;
     int nl = 0;
     if (d->d_ingp_wT) {
         nl = d->n_levels;
@@ -651,4 +795,50 @@ extern "C" int mve_triplane_backward(const MveTriplaneDesc* d, const float* d_gr
         if ((rc = tri_xty(b.ws_do, 4, 3, b.ws_act2, H2, H2, M, g->d_col2_w, H2, g->d_col2_b, partial, s))) return rc;
     }
     return MVE_OK;
+}
+
+namespace {
+
+template <int TOPO, int H, int H2>
+int launch_render_nl(const TriParams& p, const ShK16& kk, const MarchParams& mp, const TriRender& r, int n_levels, hipStream_t s) {
+    const unsigned grid = mve_cdiv(r.N, (uint32_t)WAVE);
+    switch (n_levels) {
+        case 0: k_triplane_render_rays<TOPO, H, H2, 0><<<grid, WAVE, 0, s>>>(p, kk, mp, r); break;
+        case 12: k_triplane_render_rays<TOPO, H, H2, 12><<<grid, WAVE, 0, s>>>(p, kk, mp, r); break;
+        case 14: k_triplane_render_rays<TOPO, H, H2, 14><<<grid, WAVE, 0, s>>>(p, kk, mp, r); break;
+        case 16: k_triplane_render_rays<TOPO, H, H2, 16><<<grid, WAVE, 0, s>>>(p, kk, mp, r); break;
+        default: return MVE_ERR_ARG;          // (checked by the caller before any launch)
+    }
+    MVE_LAUNCH_CHECK();
+    return MVE_OK;
+}
+
+}  // namespace
+
+extern "C" int mve_triplane_render_rays(const MveTriplaneDesc* d, const float* d_rays_o, const float* d_rays_d, uint32_t N, const uint8_t* d_bitfield,
+                                        uint32_t grid_size, const float* d_aabb, float min_near, float dt_gamma, uint32_t max_steps, float T_thresh,
+                                        float* d_weights_sum, float* d_depth, float* d_image, int32_t* d_n_samples, void* stream) {
+    if (N == 0) return MVE_OK;
+    MVE_CHECK(d, MVE_ERR_ARG, "triplane_render_rays: null descriptor");
+    MVE_CHECK(d_rays_o && d_rays_d && d_bitfield && d_aabb && d_weights_sum && d_depth && d_image, MVE_ERR_ARG, "triplane_render_rays: null pointer");
+    MVE_CHECK(grid_size > 0 && grid_size <= 1024 && max_steps > 0, MVE_ERR_ARG, "triplane_render_rays: bad grid (grid_size %u, max_steps %u)", grid_size, max_steps);
+    MVE_CHECK(d->bound > 0.f, MVE_ERR_ARG, "triplane_render_rays: the descriptor's bound must be positive (got %g)", (double)d->bound);
+    TriParams p;
+    int nl = 0;
+    if (int rc = fill_tri("triplane_render_rays", d, p, &nl, true)) return rc;
+    MVE_CHECK(nl == 0 || nl == 12 || nl == 14 || nl == 16, MVE_ERR_ARG, "triplane_render_rays: n_levels must be 0 (no hash grid), 12, 14 or 16 (got %d)", nl);
+    MarchParams mp;
+    mp.grid = d_bitfield; mp.bound = d->bound; mp.contract = 0; mp.dt_gamma = dt_gamma; mp.max_steps = max_steps; mp.C = 1; mp.H = grid_size;
+    TriRender r;
+    r.rays_o = d_rays_o; r.rays_d = d_rays_d; r.aabb = d_aabb; r.N = N; r.min_near = min_near; r.T_thresh = T_thresh;
+    r.weights_sum = d_weights_sum; r.depth = d_depth; r.image = d_image; r.n_samples = d_n_samples;
+    ShK16 kk;
+    she_constants(kk.k);
+    hipStream_t s = (hipStream_t)stream;
+    if (d->topology == MVE_TRIPLANE_DIRNET)
+        return d->hidden == 128 ? launch_render_nl<MVE_TRIPLANE_DIRNET, 128, 128>(p, kk, mp, r, nl, s) : launch_render_nl<MVE_TRIPLANE_DIRNET, 64, 64>(p, kk, mp, r, nl, s);
+    if (d->hidden == 128 && d->hidden2 == 128) return launch_render_nl<MVE_TRIPLANE_DEFAULT, 128, 128>(p, kk, mp, r, nl, s);
+    if (d->hidden == 128 && d->hidden2 == 64) return launch_render_nl<MVE_TRIPLANE_DEFAULT, 128, 64>(p, kk, mp, r, nl, s);
+    if (d->hidden == 64 && d->hidden2 == 128) return launch_render_nl<MVE_TRIPLANE_DEFAULT, 64, 128>(p, kk, mp, r, nl, s);
+    return launch_render_nl<MVE_TRIPLANE_DEFAULT, 64, 64>(p, kk, mp, r, nl, s);
 }

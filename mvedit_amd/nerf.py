@@ -303,7 +303,10 @@ class NeRFRenderer:
         dt_gamma = float(cfg.get('dt_gamma_scale', 0.0) * 2 / (intr[:, 0] + intr[:, 1]).mean())      # base_nerf.py:503-504
         rays_o, rays_d, dir_norm = camera_rays(intr, pose, h, w)
         bits = density_bitfield.reshape(-1)
-        ws, depth, image = decoder.render_rays(rays_o, rays_d, bits, self.grid_size, dt_gamma)
+        if getattr(decoder, 'takes_code', False):          # a tri-plane decoder (mvedit_amd.triplane): the scene is the code, not the decoder
+            ws, depth, image = decoder.render_rays(rays_o, rays_d, code, bits, self.grid_size, dt_gamma)
+        else:                                               # INGPDecoderParams: `code` is not read
+            ws, depth, image = decoder.render_rays(rays_o, rays_d, bits, self.grid_size, dt_gamma)
         depth = depth.view(b, h, w)
         if cfg.get('inverse_z_depth', True):
             depth = depth * dir_norm                                                                   # 1/r -> 1/z

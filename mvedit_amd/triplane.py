@@ -10,8 +10,13 @@ Two topologies are built, recognised from the state dict's keys (or from the lay
             Linear(H -> 3).  H in {64, 128}.
 Anything else (deeper stacks, a mixture of the two, scene_base, code dropout, other widths) raises NotImplementedError -- it is never computed
 another way.  Out of scope: the `preprocessor` (VAEDecoder) / code_activation in front of point_decode (the planes handed in are already
-pre-processed, as in the reference's own point_decode), 16-bit code planes, more than one scene per call, a fused ray-march render over
-tri-planes, second-order grid_sample.
+pre-processed, as in the reference's own point_decode), 16-bit code planes, more than one scene per call, second-order grid_sample.
+Rendering: `render_rays` is VolumeRenderer.forward's eval branch (lib/models/decoders/base_volume_renderer.py:264-329) as ONE launch
+(mve_triplane_render_rays: march + decode + composite per ray, the direction-only part of the colour path computed once per ray), which is
+what `NeRFRenderer.render(decoder, code, ...)` calls for a tri-plane decoder; `render_rays(..., fused=False)` is the reference-shaped host loop
+over march_rays / point_decode / composite_rays / compact_alive.  `TriPlaneVolumeRenderer` adds the training branch (march -> density ->
+cull -> decode -> composite) and `update_extra_state(code, ...)`; it refuses capacity=, compute_normal in training, more than one scene and
+pre_gamma / post_gamma.
 Gradients: `point_decode_autograd` carries autograd history w.r.t. the code planes and `parameters()` (every Linear and the hash table)
 through mve_triplane_backward -- what nerf_optim (lib/pipelines/mvedit_3d_pipeline.py:507-633) needs to optimise a TriPlaneiNGPDecoder
 scene.  Plain `point_decode` is forward only and refuses tensors that require grad instead of silently cutting the graph.  No gradient
@@ -55,15 +60,19 @@ class TriPlaneDecoder:
     """plane_cfg / flip_z / activation / sigma_activation / sigmoid_saturation as the reference constructor; weights come in through
     load_state_dict with the reference module's names (base_net.0.*, density_net.0.*, color_net.0.*, color_net.2.*)."""
 
+    takes_code = True                   # NeRFRenderer.render hands `code` to render_rays
+
     def __init__(self, plane_cfg=('xy', 'xz', 'yz'), activation='silu', sigma_activation='trunc_exp', sigmoid_saturation=0.001, flip_z=False,
-                 bound=1.0, device='cuda'):
+                 bound=1.0, min_near=0.2, max_steps=256, device='cuda'):
         assert len(plane_cfg) == 3 and all(len(p) == 2 and set(p) <= set('xyz') for p in plane_cfg), plane_cfg
         self.axes = [dict(x=0, y=1, z=2)[a] for p in plane_cfg for a in p]
         self.activation, self.sigma_activation = _ACT[activation.lower()], _ACT[sigma_activation.lower()]
         assert self.activation < 3
         self.sigmoid_saturation, self.flip_z, self.bound, self.device = float(sigmoid_saturation), bool(flip_z), float(bound), torch.device(device)
+        self.min_near, self.max_steps = float(min_near), int(max_steps)          # VolumeRenderer's defaults (base_volume_renderer.py:35-36)
         self.w = {}
         self.hash = None
+        self._aabb = None
 
     # ---- parameters ------------------------------------------------------------------------------------------------------------
     _NAMES = {'base_net.0.weight': ('base_wT', True), 'base_net.0.bias': ('base_b', False),
@@ -131,8 +140,8 @@ class TriPlaneDecoder:
     def from_config(cls, cfg, device='cuda', **kwargs):
         """The reference's decoder dict as its config files write it (configs/**: model.decoder) -> a decoder waiting for load_state_dict.
         Read: plane_cfg, flip_z, base_layers, density_layers, color_layers, use_dir_enc, dir_layers, activation, sigma_activation,
-        sigmoid_saturation, interp_mode, bound (+ base_resolution, max_resolution, n_levels for TriPlaneiNGPDecoder).  What point_decode does not
-        read (type, preprocessor, code_reshape, preproc_size, max_steps, weight_culling_th, ...) is ignored; settings that change point_decode
+        sigmoid_saturation, interp_mode, bound, min_near, max_steps (+ base_resolution, max_resolution, n_levels for TriPlaneiNGPDecoder).  What
+        point_decode and render_rays do not read (type, preprocessor, code_reshape, preproc_size, weight_culling_th, ...) is ignored; settings that change point_decode
         and are not built are refused.  `kwargs` go to the constructor (e.g. log2_hashmap_size)."""
         cfg = dict(cfg)
         if not cfg.get('use_dir_enc', True):
@@ -157,7 +166,7 @@ class TriPlaneDecoder:
             layers = (TOPOLOGY_DIRNET, base[0], H, None)
         if not ok:
             raise NotImplementedError(f'base_layers={base}, density_layers={dens}, color_layers={col}, dir_layers={dirl}: {cls._UNBUILT}')
-        kw = {k: cfg[k] for k in ('plane_cfg', 'activation', 'sigma_activation', 'sigmoid_saturation', 'flip_z', 'bound') if k in cfg}
+        kw = {k: cfg[k] for k in ('plane_cfg', 'activation', 'sigma_activation', 'sigmoid_saturation', 'flip_z', 'bound', 'min_near', 'max_steps') if k in cfg}
         if cls._HASH_KEYS:
             kw.update({k: cfg[k] for k in cls._HASH_KEYS if k in cfg})
         dec = cls(device=device, **kw, **kwargs)
@@ -237,7 +246,7 @@ class TriPlaneDecoder:
     def _desc(self, xyz, d, cl, N, C, h, w, sig, rgb):
         W = self.w
         ds = _Desc()
-        ds.d_xyz, ds.d_dirs, ds.d_code = xyz.data_ptr(), (d.data_ptr() if d is not None else None), cl.data_ptr()
+        ds.d_xyz, ds.d_dirs, ds.d_code = (xyz.data_ptr() if xyz is not None else None), (d.data_ptr() if d is not None else None), cl.data_ptr()
         ds.N, ds.C, ds.h, ds.w = N, C, h, w
         for k in range(6):
             ds.axes[k] = self.axes[k]
@@ -253,8 +262,9 @@ class TriPlaneDecoder:
                    np.array([m[2] for m in meta], np.uint32), np.array([m[3] for m in meta], np.uint32))
             keep.append(arr)
             ds.d_ingp_wT, ds.d_ingp_b, ds.d_table = W['ingp_wT'].data_ptr(), W['ingp_b'].data_ptr(), W['table'].data_ptr()
-            ds.n_levels, ds.bound = len(meta), self.bound
+            ds.n_levels = len(meta)
             ds.level_scale, ds.level_res, ds.level_offset, ds.level_size = (a.ctypes.data for a in arr)
+        ds.bound = self.bound               # the hash grid's normalisation and the marched cube of mve_triplane_render_rays
         ds.d_dens_w, ds.d_dens_b = W['dens_w'].data_ptr(), W['dens_b'].data_ptr()
         ds.d_col2_w, ds.d_col2_b = W['col2_w'].data_ptr(), W['col2_b'].data_ptr()
         if dirnet:
@@ -321,6 +331,78 @@ class TriPlaneDecoder:
         sigmas, _, num_points = self.point_decode(xyzs, None, code, density_only=True, **kwargs)
         return sigmas, num_points
 
+    # ---- VolumeRenderer.forward, eval branch --------------------------------------------------------------------------------------
+    @property
+    def aabb(self):
+        if self._aabb is None:
+            self._aabb = torch.tensor([-self.bound] * 3 + [self.bound] * 3, dtype=torch.float32, device=self.device)
+        return self._aabb
+
+    def render_rays(self, rays_o, rays_d, code, density_bitfield, grid_size, dt_gamma=0.0, T_thresh=1e-2, return_counts=False, fused=None):
+        """rays_o, rays_d [N,3] of one scene, code [1, 3, C, h, w], density_bitfield [grid_size^3 / 8] u8 -> (weights_sum [N], depth [N] (sum of
+        w / t), image [N,3][, counts [N] int32]).  Forward only.  fused=None takes the faster form as measured (profiles/triplane_render.txt): the
+        fused launch without a hash branch (1.9 against 2.0 ms), the host loop with one (the H = 64 hash instantiations spill 5-7 KB per lane to
+        scratch: 17.9 against 3.5 ms, untuned); True / False force one.  fused=True: one launch (mve_triplane_render_rays); counts are the samples
+        each ray decoded.  fused=False: the reference's host loop (base_volume_renderer.py:286-322) on march_rays / point_decode /
+        composite_rays / compact_alive, one host read per chunk of at most 8 steps; counts are the samples marched, which include those a
+        chunk marched past a ray's termination."""
+        assert code.dim() == 5 and code.shape[0] == 1, 'one scene per call (as every MVEdit pipeline)'
+        for t in (rays_o, rays_d, code):
+            if torch.is_grad_enabled() and t.requires_grad:
+                raise NotImplementedError('tri-plane decoders: render_rays is the forward only -- the differentiable path is '
+                                          'TriPlaneVolumeRenderer.forward in training mode (or call under torch.no_grad())')
+        rays_o = rays_o.detach().to(self.device, torch.float32).contiguous().view(-1, 3)
+        rays_d = rays_d.detach().to(self.device, torch.float32).contiguous().view(-1, 3)
+        N = rays_o.shape[0]
+        assert rays_d.shape[0] == N
+        bits = density_bitfield.to(self.device).contiguous().view(-1)
+        assert bits.dtype == torch.uint8 and bits.numel() * 8 == int(grid_size) ** 3, (bits.dtype, bits.numel(), grid_size)
+        self._pack()
+        if fused is None:
+            fused = self.hash is None
+        if not fused:
+            return self._render_rays_loop(rays_o, rays_d, code, bits, int(grid_size), float(dt_gamma), float(T_thresh), return_counts)
+        ws = torch.empty(N, dtype=torch.float32, device=self.device)
+        depth = torch.empty(N, dtype=torch.float32, device=self.device)
+        image = torch.empty(N, 3, dtype=torch.float32, device=self.device)
+        counts = torch.empty(N, dtype=torch.int32, device=self.device) if return_counts else None
+        _, _, C, h, w = code.shape
+        cl = code[0].detach().to(self.device, torch.float32).permute(0, 2, 3, 1).contiguous()      # [3][h][w][C]
+        assert self.w['base_wT'].shape[0] == 3 * C, (self.w['base_wT'].shape, C)
+        ds, keep = self._desc(None, None, cl, 0, C, h, w, None, None)
+        with torch.cuda.device(self.device):
+            _lib.call('mve_triplane_render_rays', ctypes.byref(ds), _lib.ptr(rays_o), _lib.ptr(rays_d), N, _lib.ptr(bits), int(grid_size),
+                      _lib.ptr(self.aabb), self.min_near, float(dt_gamma), int(self.max_steps), float(T_thresh), _lib.ptr(ws), _lib.ptr(depth),
+                      _lib.ptr(image), _lib.ptr(counts), _lib.stream_ptr(self.device))
+        del keep
+        return (ws, depth, image, counts) if return_counts else (ws, depth, image)
+
+    def _render_rays_loop(self, rays_o, rays_d, code, bits, grid_size, dt_gamma, T_thresh, return_counts):
+        from . import raymarching as rm
+        dev, N = self.device, rays_o.shape[0]
+        ws = torch.zeros(N, dtype=torch.float32, device=dev)
+        depth = torch.zeros(N, dtype=torch.float32, device=dev)
+        image = torch.zeros(N, 3, dtype=torch.float32, device=dev)
+        counts = torch.zeros(N, dtype=torch.int32, device=dev) if return_counts else None
+        if N == 0:
+            return (ws, depth, image, counts) if return_counts else (ws, depth, image)
+        nears, fars = rm.near_far_from_aabb(rays_o, rays_d, self.aabb, self.min_near)
+        rays_alive = torch.arange(N, dtype=torch.int32, device=dev)
+        rays_t = nears.clone()
+        n_alive, step = N, 0
+        while step < self.max_steps and n_alive > 0:
+            n_step = min(max(N // n_alive, 1), 8)
+            xyzs, dirs, ts = rm.march_rays(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, self.bound, bits, 1, grid_size, nears, fars,
+                                           False, dt_gamma, self.max_steps)
+            if return_counts:
+                counts.index_add_(0, rays_alive[:n_alive].long().repeat_interleave(n_step), (ts[:, 1] > 0).int())
+            sigmas, rgbs, _ = self._forward(xyzs, dirs, code)
+            rm.composite_rays(n_alive, n_step, rays_alive, rays_t, sigmas, rgbs, ts, ws, depth, image, T_thresh)
+            rays_alive, n_kept = rm.compact_alive(rays_alive, n_alive)
+            n_alive = int(n_kept.item())              # the reference's boolean-mask compaction reads the count here as well
+            step += n_step
+        return (ws, depth, image, counts) if return_counts else (ws, depth, image)
+
 
 class TriPlaneiNGPDecoder(TriPlaneDecoder):
     """+ the hash-grid branch: base_x = base_net(plane features) + ingp_base_net(HashGrid((xyz + bound) / (2 bound))); the level table follows
@@ -367,3 +449,106 @@ class _TriDecodeFn(torch.autograd.Function):
         g_code, g = dec._backward(xyz, dirs if ctx.has_dirs else None, code, g_sig, g_rgb if ctx.has_dirs else None, ctx.needs_input_grad[4])
         out = [g[n].reshape(p.shape) if ctx.needs_input_grad[5 + k] else None for k, (n, p) in enumerate(zip(ctx.names, params))]
         return (None, None, None, None, g_code.to(code.dtype) if g_code is not None else None, *out)
+
+
+class TriPlaneVolumeRenderer:
+    """Mirror of the reference's VolumeRenderer.forward(rays_o, rays_d, code, density_bitfield, grid_size, dt_gamma, perturb)
+    (lib/models/decoders/base_volume_renderer.py:179-343) and update_extra_state (:105-177) for ONE scene over a tri-plane decoder
+    (nerf.VolumeRenderer is the iNGP decoder's and stays as it is).  Eval: the decoder's render_rays.  Training: march_rays_train ->
+    point_density_decode under no_grad -> composite -> cull_samples -> point_decode -> batch_composite_rays_train; the last decode carries
+    autograd history (point_decode_autograd, native backward) when `code` or any of the decoder's parameters() requires grad.
+    Refused with NotImplementedError: capacity= (the host-read-free form needs a counted tri-plane decode, which does not exist),
+    compute_normal=True in training (second-order grid_sample), more than one scene, pre_gamma / post_gamma."""
+
+    def __init__(self, decoder, weight_culling_th=1e-3, pre_gamma=None, post_gamma=None):
+        if pre_gamma is not None or post_gamma is not None:
+            raise NotImplementedError('pre_gamma / post_gamma: the gamma pair around the eval compositing is not built')
+        self.decoder = decoder
+        self.bound, self.min_near, self.max_steps = decoder.bound, decoder.min_near, decoder.max_steps
+        self.weight_culling_th = weight_culling_th
+        self.training = False
+
+    @staticmethod
+    def _one_scene(code, *per_scene):
+        """code [1, 3, C, h, w]; rays and the bitfield with or without the leading scene axis -> the single scene's tensors"""
+        if not (torch.is_tensor(code) and code.dim() == 5 and code.shape[0] == 1):
+            raise NotImplementedError(f'code: one scene of shape [1, 3, C, h, w] per call (got {tuple(code.shape) if torch.is_tensor(code) else type(code)})')
+        out = []
+        for name, t, nd in per_scene:
+            if isinstance(t, (list, tuple)) or t.dim() == nd + 1:
+                if len(t) != 1:
+                    raise NotImplementedError(f'{name}: more than one scene ({len(t)}) is not built')
+                t = t[0]
+            out.append(t)
+        return out
+
+    def update_extra_state(self, code, density_grid, density_bitfield, iter_density, density_thresh=0.01, decay=0.9, S=128):
+        """nerf.VolumeRenderer.update_extra_state with point_density_decode(xyzs, code) as the density source: density_grid [1, H^3] f32 and
+        density_bitfield [1, H^3/8] u8 are updated IN PLACE; returns iter_density + 1 and the threshold used.  Random draws (jitter,
+        partial-update cells) come from torch's generator, as in the reference."""
+        from . import raymarching as rm
+        dec, dev = self.decoder, self.decoder.device
+        self._one_scene(code)
+        assert density_grid.shape[0] == 1 and density_grid.dtype == torch.float32 and density_grid.is_contiguous()
+        n_cells = density_grid.shape[-1]
+        H = int(round(n_cells ** (1.0 / 3.0)))
+        tmp = torch.full_like(density_grid, -1)
+        if iter_density < 16:                                         # full update, one launch over the whole grid
+            N, coords = n_cells, None
+        else:                                                         # partial update: N random cells + N occupied cells
+            N = n_cells // 4
+            coords = torch.randint(0, H, (N, 3), device=dev)
+            occ = torch.nonzero(density_grid[0] > 0).squeeze(-1)
+            occ = occ[torch.randint(0, occ.shape[0], [N], dtype=torch.long, device=dev)]
+            coords = torch.cat([coords.int(), rm.morton3D_invert(occ.int())], dim=0).contiguous()
+            N = coords.shape[0]
+        noise = torch.rand(N, 3, dtype=torch.float32, device=dev)
+        xyzs = torch.empty(N, 3, dtype=torch.float32, device=dev)
+        indices = torch.empty(N, dtype=torch.int32, device=dev)
+        mean = torch.empty(1, dtype=torch.float32, device=dev)
+        scratch = torch.empty(_lib.raw('mve_density_grid_scratch_bytes')(n_cells), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.call('mve_density_grid_points', _lib.ptr(coords), _lib.ptr(noise), N, H, self.bound, _lib.ptr(xyzs),
+                      _lib.ptr(indices), _lib.stream_ptr(dev))
+            with torch.no_grad():
+                sigmas, _ = dec.point_density_decode([xyzs], code)
+            _lib.call('mve_density_grid_update', _lib.ptr(density_grid), _lib.ptr(tmp), n_cells, _lib.ptr(sigmas), _lib.ptr(indices),
+                      N, float(decay), _lib.ptr(mean), _lib.ptr(scratch), _lib.stream_ptr(dev))
+        thresh = min(float(mean.item()), density_thresh)              # the reference reads the mean on the host too (:171-174)
+        rm.packbits(density_grid, thresh, density_bitfield)
+        return iter_density + 1, thresh
+
+    def forward(self, rays_o, rays_d, code, density_bitfield, grid_size, dt_gamma=0.0, perturb=False, noises=None, capacity=None,
+                compute_normal=False):
+        """rays_o, rays_d [N,3] (or [1,N,3]) of one scene, code [1, 3, C, h, w].  Returns the reference's result dict (weights, weights_sum,
+        depth, image, rays, normal, ts; lists of one entry where the reference returns per-scene lists).  `noises` ([N], training) overrides
+        the internally drawn perturbation."""
+        from . import raymarching as rm
+        if capacity is not None:
+            raise NotImplementedError('capacity=: the host-read-free training form needs a counted tri-plane decode, which is not built')
+        if compute_normal and self.training:
+            raise NotImplementedError('compute_normal=True in training needs second-order grid_sample, which is not built')
+        rays_o, rays_d, density_bitfield = self._one_scene(code, ('rays_o', rays_o, 2), ('rays_d', rays_d, 2), ('density_bitfield', density_bitfield, 1))
+        if isinstance(grid_size, (list, tuple)):
+            grid_size = self._one_scene(code, ('grid_size', grid_size, 0))[0]
+        if isinstance(dt_gamma, (list, tuple)):
+            dt_gamma = self._one_scene(code, ('dt_gamma', dt_gamma, 0))[0]
+        dec = self.decoder
+        if not self.training:
+            ws, depth, image = dec.render_rays(rays_o, rays_d, code, density_bitfield, grid_size, float(dt_gamma))
+            return dict(weights=None, weights_sum=[ws], depth=[depth], image=[image], rays=None, normal=[None], ts=None)
+        nears, fars = rm.near_far_from_aabb(rays_o, rays_d, dec.aabb, self.min_near)
+        xyzs, dirs, ts, rays = rm.march_rays_train(rays_o, rays_d, self.bound, density_bitfield, 1, grid_size, nears, fars,
+                                                   perturb=perturb, dt_gamma=float(dt_gamma), max_steps=self.max_steps, noises=noises)
+        if self.weight_culling_th > 0:
+            with torch.no_grad():                                      # base_volume_renderer.py:223
+                sigmas, _ = dec.point_density_decode([xyzs], code)
+                weights, _, _, _ = rm.batch_composite_rays_train(sigmas, sigmas.new_zeros(sigmas.shape[0], 3), [ts], [rays], [ts.shape[0]])
+                xyzs, dirs, ts, rays = rm.cull_samples(weights, self.weight_culling_th, xyzs, dirs, ts, rays)
+        differentiable = torch.is_grad_enabled() and (code.requires_grad or any(t.requires_grad for t in dec.parameters().values()))
+        if differentiable:
+            sigmas, rgbs, _ = dec.point_decode_autograd([xyzs], [dirs], code)
+        else:
+            sigmas, rgbs, _ = dec.point_decode([xyzs], [dirs], code)
+        weights, weights_sum, depth, image = rm.batch_composite_rays_train(sigmas, rgbs, [ts], [rays], [ts.shape[0]])
+        return dict(weights=weights, weights_sum=weights_sum, depth=depth, image=image, rays=[rays], normal=None, ts=[ts])
